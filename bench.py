@@ -11,6 +11,11 @@ actions) are resident in HBM.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: starts its N ranks itself through torch.distributed.run)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ the last timed lock-step's outputs as .npy)
+
+With --reps 1, the default, the headline leg times exactly K lock-steps (the past-L3, epsilon and extra-config legs one
+region of K each as well; only n1_same_run, rank 0 alone in an N > 1 job, still repeats its region for 0.6 s);
+`ms_per_step` is the headline leg's milliseconds per lock-step.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): whole-job env steps/s, plus
 `roofline` (dominant kernel = bpp_step; algorithmic bytes / HIP-event-measured launch duration vs the
@@ -30,6 +35,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 HBM_ACHIEVABLE_GBS = 6290.0  # same guide: what a float4 copy kernel reaches (79 % of the spec peak)
 LOG_INTERVAL = 50            # lock-steps between two statistics all-reduces inside the timed regions
+DUMP_BYTES = 48 << 20        # --dump-outputs: at most this many bytes of arrays (a seeded sample of the bins beyond it)
 
 
 def algorithmic_bytes_per_env_step(A, M):
@@ -65,12 +71,18 @@ def parse():
     ap.add_argument("--stream-depth", type=int, default=32, help="--stream: ring rows per bin")
     ap.add_argument("--stream-refill", type=int, default=14,
                     help="--stream: lock-steps between refills (with depth >= 2 * refill + 3 the refills run beside the lock-steps)")
-    ap.add_argument("--reps", type=int, default=0,
-                    help="repetitions of the timed K-step region; the MEDIAN repetition is reported (0 = auto: as many as "
-                         "it takes for --gpu-seconds of timed GPU work, so that a small --steps is not a 1 ms sample)")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="repetitions of each leg's timed K-step region (not n1_same_run's); the MEDIAN repetition is reported.  "
+                         "The default, 1, times exactly --steps lock-steps; 0 = auto: as many as it takes for --gpu-seconds of timed GPU work "
+                         "(at least three), so that a small --steps is not a 1 ms sample")
     ap.add_argument("--gpu-seconds", type=float, default=3.0,
-                    help="timed GPU work of the headline leg (the past-L3 leg gets two thirds of it): long enough for an "
-                         "outside utilisation sampler to see the device busy; the median repetition is what is reported")
+                    help="--reps 0: timed GPU work of the headline leg (the past-L3 leg gets two thirds of it): long enough for "
+                         "an outside utilisation sampler to see the device busy; the median repetition is what is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed lock-steps, write what the headline leg's last lock-step returned (observation, mask, "
+                         "reward, done, counter, ratio, episode return / length, next action) as DIR/<name>.npy in float32 / "
+                         "float64, for a fixed seeded sample of the bins when all of them exceed %d MB (bin.npy: their global "
+                         "ids); identical from run to run for identical arguments with --reps > 0" % (DUMP_BYTES >> 20))
     ap.add_argument("--launcher", choices=("auto", "direct", "spawn"), default="auto",
                     help="auto: --gpus N > 1 started without torch.distributed.run launches its N ranks itself; spawn: do "
                          "that for N = 1 as well")
@@ -441,6 +453,36 @@ def parity_gate(ctx, env, spec, actions, bins=256, lock_steps=24, seed=7):
     return rec
 
 
+OUTPUT_FIELDS = ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len")
+
+
+def output_sample(torch, res, actions, env_id_base=0, max_bytes=DUMP_BYTES):
+    """--dump-outputs: what one lock-step handed its caller -- the StepTensors fields and the next actions the step drew --
+    as host arrays, float32 where the device holds float32 or bytes, float64 otherwise (exact for every integer output).
+    All bins when they fit in `max_bytes`, else a fixed sample drawn with seed 0, in ascending bin order; `bin` holds
+    the global ids of the bins kept."""
+    import numpy as np
+    fields = [(k, getattr(res, k)) for k in OUTPUT_FIELDS] + [("next_action", actions)]
+    fields = [(k, t, np.float32 if t.dtype in (torch.float32, torch.uint8) else np.float64) for k, t in fields if t is not None]
+    E = actions.numel()
+    per_bin = 8 + sum(t.numel() // E * np.dtype(d).itemsize for _, t, d in fields)
+    n = min(E, max_bytes // per_bin)
+    idx = np.arange(E) if n == E else np.sort(np.random.RandomState(0).choice(E, n, replace=False))
+    sel = torch.from_numpy(idx).to(actions.device)
+    out = {k: t.reshape(E, -1)[sel].cpu().numpy().astype(d).reshape((n,) + tuple(t.shape[1:])) for k, t, d in fields}
+    out["bin"] = (idx + int(env_id_base)).astype(np.float64)
+    return out
+
+
+def write_outputs(directory, outputs):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+    return {"dir": directory, "bins": int(outputs["bin"].shape[0]), "files": sorted(k + ".npy" for k in outputs),
+            "bytes": int(sum(v.nbytes for v in outputs.values()))}
+
+
 def run_workload(ctx, spec):
     """Every leg of ONE workload (a BASELINE config): parity gate, warm-up, the timed K-step regions with one output set,
     the same with the outputs rotated past the Infinity Cache, optionally the epsilon variant, the Python-driven loop."""
@@ -470,9 +512,9 @@ def run_workload(ctx, spec):
 
     def drive(n, sets=None, eps=0.0):
         if stream:
-            env.rollout_uniform(seed=1, step0=state["t"], nsteps=n, actions=actions)
+            state["last"] = env.rollout_uniform(seed=1, step0=state["t"], nsteps=n, actions=actions)
         else:
-            env.rollout_uniform_sets(1, state["t"], n, actions, sets=sets, resume=state["primed"], eps=eps)
+            state["last"] = env.rollout_uniform_sets(1, state["t"], n, actions, sets=sets, resume=state["primed"], eps=eps)
             state["primed"] = True
         state["t"] += n
 
@@ -539,12 +581,13 @@ def run_workload(ctx, spec):
         return time.perf_counter() - t0
 
     def repeat_for(target_s, sets=None, log=True, kind=None, eps=0.0):
-        """Repetitions of the timed K-step region until their sum reaches `target_s` (three to begin with -- the first
-        one runs cold --, then as many as the fastest of those says are still needed; every rank runs the same number)."""
-        samples = [timed_region(sets, log, kind, eps) for _ in range(3)]
+        """Exactly --reps repetitions of the timed K-step region; with --reps 0, repetitions until their sum reaches
+        `target_s` (three to begin with -- the first one runs cold --, then as many as the fastest of those says are
+        still needed; every rank runs the same number)."""
         if args.reps > 0:
-            more = max(0, args.reps - 3)
+            samples, more = [], args.reps
         else:
+            samples = [timed_region(sets, log, kind, eps) for _ in range(3)]
             more = max(0, min(20000, int((target_s - sum(samples)) / max(min(samples), 1e-6)) + 1))
         if world > 1:
             rt = torch.tensor([more], dtype=torch.int64, device=device)
@@ -555,6 +598,7 @@ def run_workload(ctx, spec):
 
     samples = repeat_for(spec["gpu_seconds"], only_sets)
     dt = sorted(samples)[len(samples) // 2]
+    outputs = output_sample(torch, state["last"], actions, env.env_id_base) if spec.get("dump") else None
     log_point()   # whatever finished since the last logging point (outside the timed regions)
 
     # dominant kernel (bpp_step) launch duration: HIP events on the launch stream around n_ev lock-steps enqueued back
@@ -590,6 +634,7 @@ def run_workload(ctx, spec):
         kern_b2b_ms = None
     else:
         kern_b2b_ms = sorted(event_timed(n_ev, only_sets) for _ in range(3))[1]      # n_ev launches back to back, one event pair
+        # (no region carries events when there are fewer than two: the back-to-back figure stands in, and the line says so)
         kern_avg_ms = region_launch_ms("headline") or kern_b2b_ms
 
     # ---- past the Infinity Cache: the same lock-steps writing R rotating output sets (> 1 GB span), so that no output
@@ -602,9 +647,11 @@ def run_workload(ctx, spec):
         drive(2 * R, sets)
         s_l3 = repeat_for(spec["l3_seconds"], sets, log=False)
         dt_l3 = sorted(s_l3)[len(s_l3) // 2]
-        kern_l3_ms = region_launch_ms("past_l3") or sorted(event_timed(n_ev, sets) for _ in range(3))[1]
+        kern_l3_region_ms = region_launch_ms("past_l3")
+        kern_l3_ms = kern_l3_region_ms or sorted(event_timed(n_ev, sets) for _ in range(3))[1]
         past = {"output_sets": R, "output_span_MB": round(R * set_bytes / 1e6, 1), "reps": len(s_l3),
-                "ms_per_step": dt_l3 / args.steps * 1e3, "value": world * E * args.steps / dt_l3, "launch_us": kern_l3_ms * 1e3}
+                "ms_per_step": dt_l3 / args.steps * 1e3, "value": world * E * args.steps / dt_l3, "launch_us": kern_l3_ms * 1e3,
+                "launch_us_is": "timed regions" if kern_l3_region_ms else "back to back (no timed region carried events)"}
         del sets
 
     # same K lock-steps driven step by step from Python (what a Python RL loop pays per step)
@@ -645,7 +692,8 @@ def run_workload(ctx, spec):
                "episodes_finished": es["episodes"], "mean_episode_length": round(es["mean_length"], 2), "mean_ratio": round(es["mean_ratio"], 4)}
 
     res = {"spec": spec, "A": A, "M": M, "E": E, "samples": samples, "dt": dt, "past": past, "kern_avg_ms": kern_avg_ms,
-           "kern_b2b_ms": kern_b2b_ms, "dt_py": dt_py, "summary": summary, "shards": shards, "eps": eps, "parity": parity,
+           "kern_from_regions": not stream and region_launch_ms("headline") is not None,
+           "kern_b2b_ms": kern_b2b_ms, "dt_py": dt_py, "summary": summary, "shards": shards, "eps": eps, "parity": parity, "outputs": outputs,
            "only_sets": only_sets is not None,
            "kernel_name": bpp_amd._lib.launch_info(E, size, rotation)["kernel_name"],
            "stream_spec": dict(env.stream_spec) if stream else None,
@@ -686,10 +734,12 @@ def roofline_block(ctx, res):
             "valu_utilisation": (ev or {}).get("valu_utilisation"),
             "limiter": limiter(moved_l3, (ev or {}).get("valu_utilisation")),
             "bytes_per_env_step": b_alg, "launch_us": kern_avg_ms * 1e3,
-            "launch_us_is": ("HIP events on the launch stream around the K step-kernel launches of every 16th timed region, median "
-                             "over the regions of elapsed / K (at small K this includes the idle gap in front of a region's "
-                             "first kernel; launch_us_back_to_back = one event pair around >= 200 queued launches)" if not spec.get("stream") else
-                             "HIP event pairs around single launches (refill kernels run beside the lock-steps)"),
+            "launch_us_is": ("HIP event pairs around single launches (refill kernels run beside the lock-steps)" if spec.get("stream") else
+                             "HIP events on the launch stream around the K step-kernel launches of timed regions 2-4 and every 16th, "
+                             "median over the regions of elapsed / K (at small K this includes the idle gap in front of a region's "
+                             "first kernel; launch_us_back_to_back = one event pair around >= 200 queued launches)" if res["kern_from_regions"] else
+                             "launch_us_back_to_back: one event pair around >= 200 step-kernel launches queued back to back outside the "
+                             "timed regions (with fewer than two timed regions per leg -- the default --reps 1 -- none carries events)"),
             "launch_us_back_to_back": kern_b2b_ms * 1e3 if kern_b2b_ms else None}
 
 
@@ -762,7 +812,8 @@ def main():
                  "pool": pool, "pool_source": args.pool_file or "generated CUT-2 (sequences.cut2_pool, seed 0)", "stream": stream,
                  "gpu_seconds": args.gpu_seconds, "l3_seconds": args.gpu_seconds * 2.0 / 3.0, "parity": not args.no_parity,
                  "parity_steps": 24 if size[0] * size[1] <= 100 else 48,
-                 "eps_seconds": args.eps_seconds if headline and not args.only_headline and args.eps > 0 else 0.0}
+                 "eps_seconds": args.eps_seconds if headline and not args.only_headline and args.eps > 0 else 0.0,
+                 "dump": bool(args.dump_outputs) and rank == 0}
     extra_specs = []
     if headline and not args.only_headline and not args.pool_file and not args.past_l3_only:
         xs, xl = args.extra_seconds, args.extra_seconds * 0.7
@@ -875,6 +926,8 @@ def main():
                     "python_loop_ms_per_step": r["dt_py"] / args.steps * 1e3,
                     "episodes_finished": s2["episodes"], "mean_ratio": round(s2["mean_ratio"], 4), "mean_episode_length": round(s2["mean_length"], 2),
                     "roofline": roofline_block(ctx, r), "parity": r["parity"]}
+        if res["outputs"] is not None:      # rank 0's bins: its own shard of the job
+            out["dump_outputs"] = write_outputs(args.dump_outputs, res["outputs"])
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
         if n1 is not None:

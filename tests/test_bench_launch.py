@@ -78,7 +78,7 @@ def test_self_launch_command_line(monkeypatch):
 def test_gpu_bench_two_ranks_without_a_launcher():
     """`python bench.py --gpus 2` (no torchrun): it starts its two ranks itself; on this 1-GPU box both ranks share
     device 0 (BPP_BENCH_ONE_DEVICE=1 -> gloo for the barrier and the 32-byte statistics all-reduce)."""
-    d = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--only-headline"], BPP_BENCH_ONE_DEVICE="1")
+    d = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--reps", "0", "--only-headline"], BPP_BENCH_ONE_DEVICE="1")
     assert d["n_gpus"] == 2 and d["config"]["total_envs"] == 131072 and d["steps"] == 20 and d["warmup"] == 5
     assert d["config"]["launcher"] == "self-launched torch.distributed.run"
     assert d["value"] > 1e8 and d["scaling"] == "weak"
@@ -89,27 +89,28 @@ def test_gpu_bench_two_ranks_without_a_launcher():
 
 
 @pytest.mark.gpu
-def test_gpu_bench_eight_ranks_on_one_device_shard_by_global_id():
-    """SURVEY 8e without an 8-GPU box: `python bench.py --gpus 8 --envs 8192` self-launched, all eight ranks on device 0
-    over gloo.  Rank r owns the global bins from r * E (rank 7: 7 * 8192), the job has 65 536 bins, every rank's parity gate
-    ran on its own shard, and the all-reduced statistics record is the sum of the eight shards' fixed-order reductions
-    (counts exactly; the float sums up to the association of the seven final adds)."""
+def test_gpu_bench_four_ranks_on_one_device_shard_by_global_id():
+    """SURVEY 8e without a multi-GPU box: `python bench.py --gpus 4 --envs 16384` self-launched, all four ranks on device 0
+    over gloo (four, not eight: a shared device takes only a few processes at a time).  Rank r owns the global bins from
+    r * E (rank 3: 3 * 16384), the job has 65 536 bins, every rank's parity gate ran on its own shard, and the all-reduced
+    statistics record is the sum of the four shards' fixed-order reductions (counts exactly; the float sums up to the
+    association of the three final adds)."""
     import numpy as np
-    d = _run(["--gpus", "8", "--envs", "8192", "--steps", "20", "--warmup", "5", "--gpu-seconds", "0.3", "--no-past-l3"],
+    d = _run(["--gpus", "4", "--envs", "16384", "--steps", "20", "--warmup", "5", "--reps", "0", "--gpu-seconds", "0.3", "--no-past-l3"],
              BPP_BENCH_ONE_DEVICE="1")
-    assert d["n_gpus"] == 8 and d["config"]["total_envs"] == 65536 and d["config"]["envs_per_gpu"] == 8192
-    assert "8 rank(s)" in d["config"]["sharding"] and "gloo" in d["config"]["sharding"]
+    assert d["n_gpus"] == 4 and d["config"]["total_envs"] == 65536 and d["config"]["envs_per_gpu"] == 16384
+    assert "4 rank(s)" in d["config"]["sharding"] and "gloo" in d["config"]["sharding"]
     shards = d["config"]["shards"]
-    assert [s["rank"] for s in shards] == list(range(8))
-    assert [s["env_id_base"] for s in shards] == [r * 8192 for r in range(8)] and shards[7]["env_id_base"] == 7 * 8192
+    assert [s["rank"] for s in shards] == list(range(4))
+    assert [s["env_id_base"] for s in shards] == [r * 16384 for r in range(4)] and shards[3]["env_id_base"] == 3 * 16384
     parts, whole = np.array([s["sums"] for s in shards]), np.array(d["config"]["episode_sums"])
     assert (parts[:, 3] > 0).all()                                       # every shard finished episodes of its own
     np.testing.assert_array_equal(parts[:, 2:].sum(axis=0), whole[2:])   # lengths and episode counts: integers, exact
     np.testing.assert_allclose(parts[:, :2].sum(axis=0), whole[:2], rtol=1e-13, atol=0)
     assert d["config"]["episodes_finished"] == int(whole[3])
-    assert d["parity"]["mismatches"] == 0 and d["parity"]["checked_bins"] == 8 * 256 and d["parity"]["per_workload"]["10x10x10"]["ranks"] == 8
-    assert d["value"] > 1e7      # (eight processes taking turns on one device: ~6e7 measured)
-    _check_multi_rank_line(d, 8)
+    assert d["parity"]["mismatches"] == 0 and d["parity"]["checked_bins"] == 4 * 256 and d["parity"]["per_workload"]["10x10x10"]["ranks"] == 4
+    assert d["value"] > 1e7      # (processes taking turns on one device: eight of them measured ~6e7)
+    _check_multi_rank_line(d, 4)
     assert "self-launching parent" in d["cpu_baseline"]["timed_by"]
 
 
@@ -136,7 +137,7 @@ def test_gpu_bench_launcher_started_ranks_time_the_reference_on_rank0():
     import bench
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(bench.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--only-headline", "--gpu-seconds", "0.5", "--cpu-seconds", "8"]
+           "--only-headline", "--reps", "0", "--gpu-seconds", "0.5", "--cpu-seconds", "8"]
     rc, out, err = _communicate(cmd, _clean_env(BPP_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="1"))
     assert rc == 0, err[-3000:]
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
@@ -151,8 +152,8 @@ def test_gpu_bench_launcher_started_ranks_time_the_reference_on_rank0():
 def test_gpu_bench_spawned_single_rank_equals_direct_run():
     """N = 1 through the self-launch path gives the same line as the direct run (same workload, value within noise),
     and the line carries both roofline fractions (L3-assisted and past the Infinity Cache)."""
-    a = _run(["--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--only-headline"])
-    b = _run(["--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--only-headline", "--launcher", "spawn"])
+    a = _run(["--steps", "100", "--warmup", "20", "--reps", "0", "--no-cpu-baseline", "--only-headline"])
+    b = _run(["--steps", "100", "--warmup", "20", "--reps", "0", "--no-cpu-baseline", "--only-headline", "--launcher", "spawn"])
     assert a["config"]["launcher"] == "direct" and b["config"]["launcher"] == "self-launched torch.distributed.run"
     assert a["n_gpus"] == b["n_gpus"] == 1 and a["config"]["total_envs"] == b["config"]["total_envs"] == 65536
     assert abs(a["value"] / b["value"] - 1.0) < 0.1
@@ -171,7 +172,7 @@ def test_gpu_bench_default_line_carries_every_single_gpu_config_and_the_parity_g
     CPU baseline): value = BASELINE config 2; `configs` holds config 3 (rotation), config 4 (20x20x20, 32 768 bins) and
     config 2 on the reference's own dataset pool, each with value, value_past_l3 and a roofline block; `parity` is the
     in-run gate against the oracle (0 mismatches or no line at all); `epsilon_variant` is SURVEY 8d's failure-path leg."""
-    d = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--gpu-seconds", "0.6", "--extra-seconds", "0.3",
+    d = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--reps", "0", "--no-cpu-baseline", "--gpu-seconds", "0.6", "--extra-seconds", "0.3",
               "--eps-seconds", "0.2"])
     assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"] and d["config"]["envs_per_gpu"] == 65536
     assert set(d["configs"]) == {"10x10x10_rot", "20x20x20", "10x10x10_dataset_cut2"}
@@ -188,3 +189,67 @@ def test_gpu_bench_default_line_carries_every_single_gpu_config_and_the_parity_g
     assert p["mismatches"] == 0 and p["checked_bins"] == 4 * 256 and set(p["per_workload"]) == {"10x10x10"} | set(d["configs"])
     e = d["epsilon_variant"]
     assert e["epsilon"] == 0.01 and e["value"] > 1e8 and e["mean_episode_length"] < d["config"]["mean_episode_length"]
+
+
+def test_output_sample_is_a_fixed_float_sample_within_the_byte_cap():
+    """No GPU needed: --dump-outputs' sampler on host tensors.  Every array is float32 / float64 and equals the source rows
+    exactly; all bins are kept while they fit, and beyond the cap the same seeded, ascending subset of bins every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    E, A = 1000, 100
+    g = torch.Generator().manual_seed(3)
+    res = bench.argparse.Namespace(obs=torch.rand((E, 4 * A), generator=g), mask=(torch.rand((E, A), generator=g) < 0.3).float(),
+                                   reward=torch.rand((E, 1), generator=g), done=torch.randint(0, 2, (E,), dtype=torch.uint8, generator=g),
+                                   counter=torch.randint(0, 40, (E,), dtype=torch.int32, generator=g),
+                                   ratio=torch.rand(E, dtype=torch.float64, generator=g), ep_ret=torch.rand(E, dtype=torch.float64, generator=g),
+                                   ep_len=torch.randint(0, 40, (E,), dtype=torch.int32, generator=g))
+    actions = torch.randint(0, A, (E,), dtype=torch.int64, generator=g)
+    full = bench.output_sample(torch, res, actions, env_id_base=7)
+    assert set(full) == set(bench.OUTPUT_FIELDS) | {"next_action", "bin"}
+    np.testing.assert_array_equal(full["bin"], np.arange(7, 7 + E))
+    cap = 200 * 1024
+    a = bench.output_sample(torch, res, actions, env_id_base=7, max_bytes=cap)
+    b = bench.output_sample(torch, res, actions, env_id_base=7, max_bytes=cap)
+    n = a["bin"].shape[0]
+    assert 0 < n < E and sum(v.nbytes for v in a.values()) <= cap
+    idx = a["bin"].astype(np.int64) - 7
+    assert (np.diff(idx) > 0).all()
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and v.shape[0] == n, k
+        np.testing.assert_array_equal(v, b[k])
+        np.testing.assert_array_equal(v, full[k][idx])
+    src = dict(vars(res), next_action=actions)
+    for k in src:
+        np.testing.assert_array_equal(full[k], src[k].numpy().astype(full[k].dtype))
+    assert full["obs"].dtype == full["mask"].dtype == full["done"].dtype == np.float32 and full["next_action"].dtype == np.float64
+
+
+@pytest.mark.gpu
+def test_gpu_bench_times_exactly_steps_and_dumps_the_same_outputs_every_run(tmp_path, oracle):
+    """--steps K with the default --reps 1 times ONE region of exactly K lock-steps (ms_per_step = its duration / K), and
+    --dump-outputs writes the last timed lock-step's outputs: float32 / float64 arrays under 64 MB, bit-identical in two
+    runs with the same arguments, each observation's mask the oracle's mask of it, each next action a feasible one."""
+    import numpy as np
+    dirs = [str(tmp_path / n) for n in ("a", "b")]
+    lines = [_run(["--gpus", "1", "--steps", "40", "--warmup", "5", "--only-headline", "--no-cpu-baseline", "--no-past-l3",
+                   "--dump-outputs", d]) for d in dirs]
+    for d, path in zip(lines, dirs):
+        assert d["steps"] == 40 and d["reps"] == 1 and d["parity"]["mismatches"] == 0
+        assert abs(d["ms_per_step"] - d["timed_gpu_work_ms"] / 40) < 1e-9 * d["ms_per_step"]
+        assert d["dump_outputs"]["dir"] == path and d["dump_outputs"]["bytes"] <= 64 << 20
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(lines[0]["dump_outputs"]["files"]) == sorted(os.listdir(dirs[1]))
+    out = {n[:-4]: np.load(os.path.join(dirs[0], n)) for n in names}
+    for n in names:
+        assert out[n[:-4]].dtype in (np.float32, np.float64), n
+        np.testing.assert_array_equal(out[n[:-4]], np.load(os.path.join(dirs[1], n)), err_msg=n)
+    assert sum(os.path.getsize(os.path.join(dirs[0], n)) for n in names) <= 64 << 20
+    bins = out["bin"].astype(np.int64)
+    assert len(bins) == lines[0]["dump_outputs"]["bins"] and (np.diff(bins) > 0).all() and 0 <= bins[0] and bins[-1] < 65536
+    assert out["obs"].shape == (len(bins), 400) and out["mask"].shape == (len(bins), 100)
+    np.testing.assert_array_equal(out["mask"], oracle.mask_from_obs(out["obs"], (10, 10, 10), False))
+    a = out["next_action"].astype(np.int64)
+    has = out["mask"].any(axis=1)
+    assert has.mean() > 0.5 and (out["mask"][np.arange(len(a)), a][has] == 1.0).all()

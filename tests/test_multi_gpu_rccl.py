@@ -3,6 +3,7 @@ where torch.cuda.device_count() >= 2 (a multi-GPU driver box); the build-lock te
 
 RCCL with more than one rank has never executed in this project's own runs -- these tests are what will execute it the
 first time a box with two devices runs `pytest -m gpu`."""
+import functools
 import json
 import os
 import subprocess
@@ -15,12 +16,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@functools.lru_cache(maxsize=None)
 def _devices():
-    try:
-        import torch
-        return torch.cuda.device_count() if torch.cuda.is_available() else 0
-    except Exception:  # noqa: BLE001
-        return 0
+    """HIP devices visible, counted in a child process: collecting this module does not open the device in the test process
+    (every process holding it counts against what a shared GPU host admits, and the one-device multi-rank bench tests run
+    next to the test process).  A broken torch is an error here, not a "needs two devices" skip."""
+    p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300, check=True)
+    return int(p.stdout.split()[-1])
 
 
 def _clean_env(**extra):
@@ -52,8 +55,8 @@ def _bench(args):
 def test_bench_two_gpus_over_rccl_scales():
     """`python bench.py --gpus 2` on a box with two devices: one rank per GPU over real RCCL (no BPP_BENCH_ONE_DEVICE),
     weak scaling -- twice the bins, at least 1.8x the N = 1 throughput."""
-    one = _bench(["--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--no-past-l3", "--gpu-seconds", "1"])
-    two = _bench(["--gpus", "2", "--steps", "100", "--warmup", "20", "--no-past-l3", "--gpu-seconds", "1"])
+    one = _bench(["--steps", "100", "--warmup", "20", "--reps", "0", "--no-cpu-baseline", "--no-past-l3", "--gpu-seconds", "1"])
+    two = _bench(["--gpus", "2", "--steps", "100", "--warmup", "20", "--reps", "0", "--no-past-l3", "--gpu-seconds", "1"])
     assert two["n_gpus"] == 2 and two["config"]["total_envs"] == 2 * one["config"]["total_envs"]
     assert "RCCL" in two["config"]["sharding"] and "2 rank(s)" in two["config"]["sharding"]
     assert two["scaling"] == "weak"
