@@ -59,11 +59,12 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *mask, int64_t 
 // bound, not memory bound -- 65 536 rows of M = 100 are 16 waves per SIMD, and round 1's 680 instructions per wave
 // (38 ds_bpermute shuffles with their address arithmetic, two IEEE divisions, logf, per-element range predicates) were 16.2 us
 // for 53 MB.  Now: row maximum, softmax denominator, probability total, the inclusive scan of the CDF and the index
-// reductions run on the DPP data path (row_ror / row_shr: one VALU instruction each, no LDS), the reciprocals and the
-// logarithm are the hardware's (v_rcp_f32 / v_log_f32, 1 ulp: far inside the 5e-6 log-probability tolerance the torch
-// reference is held to), a quad past the end of the row is a -inf logit instead of a predicate per element, the sampled
-// entry is found by COUNTING the cumulative sums below the target, and the lane that owns the chosen entry writes the outputs
-// (no broadcast of its probability): ~340 instructions per wave.
+// reductions run on the DPP data path (row_ror / row_shr: one VALU instruction each, no LDS), the exponential, the
+// reciprocals and the logarithm are the hardware's (v_exp_f32 / v_rcp_f32 / v_log_f32, ~1 ulp: inside the 5e-6
+// log-probability budget the kernel is held to against a float64 reference of the formula, tests/test_policy_head_f64.py),
+// a quad past the end of the row is a -inf logit instead of a predicate per element, the sampled entry is found by
+// COUNTING the cumulative sums below the target, and the lane that owns the chosen entry writes the outputs (no broadcast
+// of its probability): ~340 instructions per wave.
 // row_ror:n rotates within every 16-lane row; row_shr:n shifts, lanes without a source keep `old`
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v, float old) {
@@ -129,13 +130,17 @@ __global__ __launch_bounds__(256) void masked_act_kernel(const float *logits, co
         mx = fmaxf(fmaxf(mx, fmaxf(z[k][0], z[k][1])), fmaxf(z[k][2], z[k][3]));
     }
     mx = row16_max(mx);
-    const float mxl = mx * 1.44269504088896340736f;
     float part = 0.0f;
 #pragma unroll
     for (int k = 0; k < PER; ++k)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            z[k][t] = __builtin_amdgcn_exp2f(z[k][t] * 1.44269504088896340736f - mxl);   // exp(z - mx); exp2(-inf) = 0
+            // exp(z - mx); exp2(-inf) = 0.  The maximum is subtracted BEFORE the scaling: z * log2e - mx * log2e rounds
+            // mx * log2e on its own, an error of ~1 ulp of 1.44 |mx| that does not cancel, so logits offset by a constant C
+            // (a drifting bias) moved the log-probabilities by up to 7e-5 at |C| = 1000.  z - mx is exact for every entry
+            // within a factor of 2 of the maximum, and otherwise rounds relative to the difference itself, the only thing
+            // the softmax depends on (tests/test_policy_head_f64.py, shifted family)
+            z[k][t] = __builtin_amdgcn_exp2f((z[k][t] - mx) * 1.44269504088896340736f);
             part += z[k][t];
         }
     const float inv_sum = __builtin_amdgcn_rcpf(row16_sum(part));

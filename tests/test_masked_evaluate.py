@@ -34,19 +34,29 @@ def case(E, M, seed):
     return x, m, a, w
 
 
+def forward_tolerances(M):
+    """|diff| allowed for (log-probability, entropy, bad mass) of a row of M entries: sequential sums of M terms in the
+    oracle, a sum of M products in the entropy."""
+    return max(5e-6, 2.5e-8 * M), max(2e-5, 1e-7 * M), 2e-6
+
+
+GRAD_TOL = (1e-4, 2e-6)                                                 # (rtol, atol) of the gradient
+
+
 def check(fwd, bwd, E, M, seed):
     x, m, a, w = case(E, M, seed)
     lp0, h0, b0, g0 = torch_reference(x, m, a, w)
     lp, h, b = fwd(x, m, a)
-    np.testing.assert_allclose(lp, lp0, rtol=0, atol=max(5e-6, 2.5e-8 * M))       # sequential sums of M terms in the oracle
-    np.testing.assert_allclose(h, h0, rtol=0, atol=max(2e-5, 1e-7 * M))
-    np.testing.assert_allclose(b, b0, rtol=0, atol=2e-6)
+    tol = forward_tolerances(M)
+    np.testing.assert_allclose(lp, lp0, rtol=0, atol=tol[0])
+    np.testing.assert_allclose(h, h0, rtol=0, atol=tol[1])
+    np.testing.assert_allclose(b, b0, rtol=0, atol=tol[2])
     g = bwd(x, m, a, *w)
-    np.testing.assert_allclose(g, g0, rtol=1e-4, atol=2e-6)
+    np.testing.assert_allclose(g, g0, rtol=GRAD_TOL[0], atol=GRAD_TOL[1])
     # each output on its own (catches a term leaking into another one's gradient)
     for i in range(3):
         wi = tuple(w[j] if j == i else np.zeros(E, np.float32) for j in range(3))
-        np.testing.assert_allclose(bwd(x, m, a, *wi), torch_reference(x, m, a, wi)[3], rtol=1e-4, atol=2e-6)
+        np.testing.assert_allclose(bwd(x, m, a, *wi), torch_reference(x, m, a, wi)[3], rtol=GRAD_TOL[0], atol=GRAD_TOL[1])
 
 
 SHAPES = [(300, 100), (130, 200), (50, 400), (64, 8), (20, 800), (5, 37)]
