@@ -1,12 +1,14 @@
 // bpp_kernels.hip -- MI355X (gfx950 / CDNA4) kernels + C ABI of the vectorised 3D bin-packing
 // environment step (include/bpp_abi.h).  Hand-written for wave64; integer/indexing work, no MFMA.
 //
-// Two implementations of the same step share this file:
-//   * bpp_fast_kernel<W,L,K,ROT,MODE>  the production path: compile-time geometry for 10x10 and 20x20 bins,
-//                                      W = L = 0 instantiates the same code with runtime geometry for any
-//                                      other bin with W*L % 4 == 0 and H <= 22;
-//   * bpp_kernel<VEC,MODE>             any W*L <= 1024 (also W*L % 4 != 0, H up to 255), the fallback.
-// Work decomposition of the fast path:
+// Three implementations of the same step (bpp_launch_info tells which one a geometry gets):
+//   * bpp_tile_kernel<W,L,K,ROT,MODE,EPW,NIT>  the production path: compile-time geometry for 10x10 and 20x20 bins
+//                                              (bpp_tile_kernel.inl);
+//   * bpp_fast_kernel<K,ROT,MODE>              the same algorithm with runtime geometry, for any other bin with
+//                                              W*L % 4 == 0 and H <= 22 (bpp_rt_kernels.inl);
+//   * bpp_kernel<VEC,MODE>                     any W*L <= 1024 (also W*L % 4 != 0, H up to 255), the fallback.
+// All three run the per-bin step chain stated once in this file (next_row ... step_outcome).
+// Work decomposition of the prefix-image kernels:
 //   * a workgroup of 4 waves owns 4*EPW consecutive bins (EPW = 4 for the 10x10 bin, 1 for 20x20); the
 //     bins of a wave are contiguous in every tensor ([E][A] byte heightmap, [E][4A] observation, [E][M]
 //     mask), so each chunk is streamed with full-width accesses whatever the geometry;
@@ -313,6 +315,18 @@ __device__ __forceinline__ void wave_sync() {
 struct Win {
     int mh, ma, c, sc;
 };
+// The window's (max_h, max_area), scanned by the caller, completed with the corner counts of the window whose first cell
+// is hb (space.py:117-125).
+__device__ __forceinline__ Win corner_win(const uint8_t *hb, int L, int x, int y, int mh, int ma) {
+    const int r00 = hb[0], r10 = hb[(x - 1) * L], r01 = hb[y - 1], r11 = hb[(x - 1) * L + y - 1];
+    const int rm = max(max(r00, r10), max(r01, r11));
+    Win w;
+    w.mh = mh;
+    w.ma = ma;
+    w.c = (r00 == mh) + (r10 == mh) + (r01 == mh) + (r11 == mh);
+    w.sc = (r00 == rm) + (r10 == rm) + (r01 == rm) + (r11 == rm);
+    return w;
+}
 __device__ __forceinline__ Win scan_window(const uint8_t *hm, int L, int lx, int ly, int x, int y) {
     const uint8_t *p = hm + lx * L + ly;
     int mh = 0, ma = 0;
@@ -324,14 +338,7 @@ __device__ __forceinline__ Win scan_window(const uint8_t *hm, int L, int lx, int
             mh = v > mh ? v : mh;
         }
     }
-    int r00 = p[0], r10 = p[(x - 1) * L], r01 = p[y - 1], r11 = p[(x - 1) * L + y - 1];
-    int rm = max(max(r00, r10), max(r01, r11));
-    Win w;
-    w.mh = mh;
-    w.ma = ma;
-    w.c = (r00 == mh) + (r10 == mh) + (r01 == mh) + (r11 == mh);
-    w.sc = (r00 == rm) + (r10 == rm) + (r01 == rm) + (r11 == rm);
-    return w;
+    return corner_win(p, L, x, y, mh, ma);
 }
 
 // Integer form of the float64 tests `max_area/area > 0.95 / 0.85 / 0.50` (exhaustively
@@ -360,6 +367,125 @@ __device__ __forceinline__ uint32_t mix32(uint32_t base, uint32_t gid) {
     h *= 0x846CA68Bu;
     h ^= h >> 16;
     return h;
+}
+
+// ---- the per-bin step chain: one statement of the environment's rules for the three step kernels ------------------------
+// Each kernel scans the placement window its own way and stores the results where and when it needs them; what a step
+// means for the bin is stated here once.
+
+// The pool row a bin plays after row s (include/bpp_abi.h: bpp_env_state.seq).
+__device__ __forceinline__ int next_row(const Params &p, int s) {
+    const int n = s + p.seq_stride;
+    return n >= p.P ? n - p.P : n;
+}
+
+// An action applied to the item on display (bin3D.py:96-105, space.py:153-172).  ok: the footprint lies inside the bin
+// (space.py:112-115) -- the placement rule on the window [lx, lx + x) x [ly, ly + y) is still to be checked.
+struct Placement {
+    bool ok, noop;
+    int lx, ly, x, y, z;
+};
+// div_l(n) = n / L, however the kernel divides.  active == false: a lane without a bin, never placed.
+template <typename DivL>
+__device__ __forceinline__ Placement decode_action(int64_t act, uint32_t item, bool rot, bool active, int W, int L, DivL div_l) {
+    const int ix = item & 255, iy = (item >> 8) & 255, iz = (item >> 16) & 255;
+    const int A = W * L;
+    Placement pl;
+    pl.noop = act == BPP_ACTION_NOOP;                  // include/bpp_abi.h: the bin is left alone
+    int64_t idx = act;
+    const bool flag = rot && idx > A;                  // rotated iff idx > area (strict)
+    if (flag) idx -= A;
+    pl.x = flag ? iy : ix, pl.y = flag ? ix : iy, pl.z = iz;
+    pl.ok = active && (uint64_t)idx < (uint64_t)(W + 1) * L;   // 0 <= idx < (W + 1) * L
+    pl.lx = 0, pl.ly = 0;
+    if (pl.ok) {
+        pl.lx = div_l((int)idx);
+        pl.ly = (int)idx - pl.lx * L;
+        pl.ok = (pl.lx + pl.x <= W) && (pl.ly + pl.y <= L);
+    }
+    return pl;
+}
+
+// A new episode on pool row seq (shmem_vec_env.py:128-129 auto-reset, bin3D.py:55-59): an empty bin, the counters
+// cleared, the items on display taken from the row.  (The episode number is the caller's.)
+__device__ __forceinline__ void begin_episode(bpp_env_state &st, int seq, uint32_t item_cur, uint32_t item_next, uint32_t item_reset) {
+    st.seq = seq;
+    st.cursor = 0;
+    st.n_boxes = 0;
+    st.vol_sum = 0;
+    st.ep_ret = 0.0;
+    st.ep_len = 0;
+    st.item_cur = item_cur;
+    st.item_next = item_next;
+    st.item_reset = item_reset;
+    st.hmax = 0;
+}
+
+// The state record a reset launch leaves for bin e: episode 0 on the bin's first row, or the bin's next episode.
+template <int MODE>
+__device__ __forceinline__ bpp_env_state reset_state(const Params &p, int e) {
+    bpp_env_state st;
+    int seq;
+    if (MODE == kResetInit) {
+        st.episode = 0;
+        seq = (int32_t)(((uint32_t)p.base_mod + (uint32_t)e) % (uint32_t)p.P);
+    } else {
+        st = p.state[e];
+        st.episode += 1;
+        seq = next_row(p, st.seq);
+    }
+    const int sn = next_row(p, seq);
+    const uint32_t item_cur = p.pool[(size_t)seq * p.T + p.ring2];
+    const uint32_t item_next = p.pool[(size_t)seq * p.T + p.ring2 + min(1, p.T - 1 - p.ring2)];
+    begin_episode(st, seq, item_cur, item_next, p.pool[(size_t)sn * p.T + p.ring2]);
+    return st;
+}
+
+// What a step reports for the bin: the totals after it, before an auto-reset.
+struct StepOutcome {
+    double rew, ratio, ret;
+    int len, boxes;
+    bool fin;   // the episode ended: a failed placement that was not a no-op
+};
+// Books a step (ok: placed at height top) into the state record: reward and Monitor sums, then the next item on success
+// or the next episode on failure.  sp_ok / sp_f1 / sp_f2: the look-ahead pool entries of the two outcomes (look_ahead_at).
+__device__ __forceinline__ StepOutcome step_outcome(const Params &p, bpp_env_state &st, bool ok, bool noop, int top, int seq_n,
+                                                    uint32_t sp_ok, uint32_t sp_f1, uint32_t sp_f2) {
+    const uint32_t it = st.item_cur;
+    const int vol = (int)(it & 255u) * (int)((it >> 8) & 255u) * (int)((it >> 16) & 255u);
+    StepOutcome o;
+    o.rew = ok ? ((double)vol / p.binvol) * 10.0 : 0.0;     // bin3D.py:44-46,108-121: float64, 0.0 on failure
+    st.n_boxes += ok ? 1 : 0;
+    st.vol_sum += ok ? vol : 0;
+    st.ep_ret = st.ep_ret + o.rew;                           // bench/monitor.py:58-62 (sum in step order)
+    st.ep_len += noop ? 0 : 1;
+    o.ratio = (double)st.vol_sum / p.binvol;                 // space.py:146-151
+    o.ret = st.ep_ret;
+    o.len = st.ep_len;
+    o.boxes = st.n_boxes;                                    // bin3D.py:111,124
+    o.fin = !ok && !noop;
+    if (ok) {
+        st.cursor += 1;                                      // bin3D.py:116-117
+        st.item_cur = st.item_next;
+        st.item_next = sp_ok;
+        st.hmax = max(st.hmax, (uint32_t)top);               // highest cell of the bin (space.py:42-45)
+    } else if (!noop) {
+        st.episode += 1;
+        begin_episode(st, seq_n, st.item_reset, sp_f1, sp_f2);
+    }
+    return o;
+}
+
+// Byte tiles: four heights per dword, clamped to a byte on the way in.
+__device__ __forceinline__ uint32_t byte_quad(int4 v) {
+    return min((uint32_t)v.x, 255u) | (min((uint32_t)v.y, 255u) << 8) | (min((uint32_t)v.z, 255u) << 16) | (min((uint32_t)v.w, 255u) << 24);
+}
+__device__ __forceinline__ uint32_t byte_quad(float4 v) {
+    return min((uint32_t)(int)v.x, 255u) | (min((uint32_t)(int)v.y, 255u) << 8) | (min((uint32_t)(int)v.z, 255u) << 16) |
+           (min((uint32_t)(int)v.w, 255u) << 24);
+}
+__device__ __forceinline__ float4 quad_floats(uint32_t v) {
+    return make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u), (float)(v >> 24));
 }
 
 #include "bpp_rt_kernels.inl"
@@ -404,9 +530,9 @@ int check_geometry(int E, int W, int L, int H, int rotation, int rule) {
 // LDS under ~32 KiB (>= 5 blocks = 20 waves per CU), at most 16.
 struct Launch {
     Params p;
-    bool vec;
-    int fast;  // kRuntimeGeo + K - 1: prefix-image kernel with runtime geometry, -1 = generic kernel
-    int tile;  // index into kTileGeo (compile-time geometry, default launch shape), -1 = not the tile kernel
+    int kind;  // BPP_KERNEL_* (include/bpp_abi.h)
+    int K;     // prefix-image kernels: 64-bit histogram words per entry
+    int tile;  // BPP_KERNEL_TILE: index into kTileGeo
     int nit;   // tile kernel: groups of bins a wave walks through (1, 2 or 4)
     int wpb;   // waves per workgroup (waves are independent; this only sets the LDS/dispatch granule)
     int blocks;
@@ -428,7 +554,19 @@ struct TileGeoEntry {
 constexpr TileGeoEntry kTileGeo[] = {{10, 10, 1, 4, 1, 2, 2}, {20, 20, 1, 1, 1, 4, 4}, {20, 20, 2, 1, 1, 4, 4}, {10, 10, 2, 4, 1, 2, 2}};
 constexpr size_t kOutputsPastL3 = 300u * 1000u * 1000u;   // obs + mask bytes per launch
 constexpr int kNumTileGeo = sizeof(kTileGeo) / sizeof(kTileGeo[0]);
-constexpr int kRuntimeGeo = 100;  // l.fast == kRuntimeGeo (K = 1) or kRuntimeGeo + 1 (K = 2)
+
+// f(std::integral_constant<int, g>{}) for the kTileGeo entry g == tile: the one place that turns the table into kernel
+// template arguments (launch and bpp_launch_info).
+template <typename F>
+void with_tile_geo(int tile, F &&f) {
+    static_assert(kNumTileGeo == 4, "one case per kTileGeo entry");
+    switch (tile) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
 
 // Tuning knobs (include/bpp_abi.h: bpp_knobs).  Initialised ONCE per process from the environment
 // (BPP_EPW, BPP_WPB, BPP_XCD, BPP_FORCE_GENERIC, BPP_ABLATE), afterwards only bpp_set_knobs changes them:
@@ -471,38 +609,40 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule) {
     p.rotation = rotation;
     p.M = p.A * (1 + rotation);
     p.rule = rule;
-    l.vec = (p.A % 4) == 0;
+    const bool vec = (p.A % 4) == 0;
     const bpp_knobs kn = current_knobs();
     int epw = 16;
     if (kn.bins_per_wave > 0) epw = kn.bins_per_wave > 64 ? 64 : kn.bins_per_wave;
     else
         while (epw > 1 && (size_t)kWavesPerBlock * (epw * (p.A + p.M + 16)) > 32 * 1024) epw >>= 1;
-    l.fast = -1;
+    l.kind = BPP_KERNEL_CELLSCAN;
+    l.K = 0;
     l.tile = -1;
     l.nit = 1;
-    const bool gen = kn.force_generic != 0;
-    if (!gen && !kn.legacy_fast && kn.bins_per_wave <= 0 && kn.waves_per_group <= 0)
-        for (int g = 0; g < kNumTileGeo; ++g)
-            if (kTileGeo[g].W == W && kTileGeo[g].L == L && H + 2 <= kLevelsPerWord * kTileGeo[g].K) {
-                l.tile = g;
-                break;
-            }
-    // any other bin whose area is a multiple of 4 and whose heights fit two histogram words runs the same
-    // algorithm with runtime geometry (kRuntimeGeo + K - 1)
-    int rt_k = 0;
-    if (!gen && l.fast < 0 && l.vec && H + 2 <= kLevelsPerWord * 2) {
-        rt_k = H + 2 <= kLevelsPerWord ? 1 : 2;
-        l.fast = kRuntimeGeo + rt_k - 1;
+    // any bin whose area is a multiple of 4 and whose heights fit two histogram words runs the prefix-image algorithm:
+    // the tile kernel where it is compiled for the geometry and the launch shape is the default, else with runtime geometry
+    if (!kn.force_generic && vec && H + 2 <= kLevelsPerWord * 2) {
+        l.kind = BPP_KERNEL_PREFIX_RT;
+        l.K = H + 2 <= kLevelsPerWord ? 1 : 2;
+        if (!kn.legacy_fast && kn.bins_per_wave <= 0 && kn.waves_per_group <= 0)
+            for (int g = 0; g < kNumTileGeo; ++g)
+                if (kTileGeo[g].W == W && kTileGeo[g].L == L && H + 2 <= kLevelsPerWord * kTileGeo[g].K) {
+                    l.kind = BPP_KERNEL_TILE;
+                    l.K = kTileGeo[g].K;
+                    l.tile = g;
+                    break;
+                }
     }
-    const int pn_bytes = l.fast >= 0 ? (W + 1) * (L + 1) * 8 * rt_k : 0;
-    if (l.fast >= 0 && kn.bins_per_wave <= 0) {
+    const bool prefix = l.kind != BPP_KERNEL_CELLSCAN;
+    const int pn_bytes = prefix ? (W + 1) * (L + 1) * 8 * l.K : 0;
+    if (prefix && kn.bins_per_wave <= 0) {
         // prefix image dominates LDS: keep a 4-wave block under 24 KiB (>= 6 blocks = 24 waves per CU).
         // Measured on MI355X: 10x10: EPW=4 39 us vs 43 us at EPW=8 and 50 us at EPW=2; 10x10 + rotation
         // (21 KiB at EPW=4): 51 us vs 59 us at EPW=2; 20x20: EPW=1 85 us vs 116 us at EPW=2.
         epw = 16;
         while (epw > 1 && (size_t)kWavesPerBlock * (epw * (p.A + p.M + 48 + pn_bytes)) > 24 * 1024) epw >>= 1;
     }
-    if (l.fast >= 0) {  // sub-groups of 64/epw lanes per bin: epw must be a power of two <= 64
+    if (prefix) {  // sub-groups of 64/epw lanes per bin: epw must be a power of two <= 64
         int sh = 0;
         while ((2 << sh) <= epw && sh < 6) ++sh;
         epw = 1 << sh;
@@ -514,24 +654,24 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule) {
     p.off_mk = (epw * p.A + 15) & ~15;
     p.off_rec = (p.off_mk + epw * p.M + 15) & ~15;
     p.off_ori = p.off_rec + epw * (int)sizeof(BinRec);
-    p.off_P = p.off_ori + (l.fast >= 0 ? epw * 2 * (int)sizeof(OriRec) : 0);
+    p.off_P = p.off_ori + (prefix ? epw * 2 * (int)sizeof(OriRec) : 0);
     p.lds_per_wave = p.off_P + epw * pn_bytes;
     p.divL = make_fastdiv(L);
     p.divA = make_fastdiv(p.A);
     p.divM = make_fastdiv(p.M);
-    p.divA4 = make_fastdiv(l.vec ? p.A / 4 : p.A);
+    p.divA4 = make_fastdiv(vec ? p.A / 4 : p.A);
     p.divW = make_fastdiv(W);
     p.divM4 = make_fastdiv(p.M / 4 > 0 ? p.M / 4 : 1);
     p.divPWW = make_fastdiv(L + 1 + W);
     p.binvol = (double)W * (double)L * (double)H;
     const int waves = (E + epw - 1) / epw;
     l.wpb = kWavesPerBlock;
-    if (kn.waves_per_group >= 1 && kn.waves_per_group <= (l.fast >= 0 ? kMaxFastWavesPerBlock : kWavesPerBlock))
+    if (kn.waves_per_group >= 1 && kn.waves_per_group <= (prefix ? kMaxFastWavesPerBlock : kWavesPerBlock))
         l.wpb = kn.waves_per_group;
-    if (l.fast >= 0 && l.wpb * epw > kWave) l.wpb = kWave / epw;  // wave 0 carries one bin per lane
+    if (prefix && l.wpb * epw > kWave) l.wpb = kWave / epw;  // wave 0 carries one bin per lane
     l.blocks = (waves + l.wpb - 1) / l.wpb;
     l.lds = (size_t)l.wpb * p.lds_per_wave;
-    if (l.tile >= 0) {   // the tile kernel's launch shape is part of its type; only the grid depends on E
+    if (l.kind == BPP_KERNEL_TILE) {   // the tile kernel's launch shape is part of its type; only the grid depends on E
         const bool past_l3 = (size_t)E * (size_t)(16 * p.A + 4 * p.M) > kOutputsPastL3;
         l.nit = (kn.tile_groups == 1 || kn.tile_groups == 2 || kn.tile_groups == 4)
                     ? kn.tile_groups : (past_l3 ? (rotation ? kTileGeo[l.tile].nit_big_rot : kTileGeo[l.tile].nit_big) : kTileGeo[l.tile].nit);
@@ -539,14 +679,14 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule) {
         p.epw = kTileGeo[l.tile].epw;
         l.wpb = kTileWaves;
         l.blocks = (E + nb - 1) / nb;
-        l.lds = 0;       // taken from TileGeo<...>::LDS_BLOCK at launch
+        l.lds = 0;       // taken from TileGeo<...>::LDS_BLOCK at launch (tile_lds_block)
     }
     return l;
 }
 
-template <int W, int L, int K, bool ROT, int MODE>
+template <int K, bool ROT, int MODE>
 void launch_fast_rot(const Launch &l, hipStream_t s) {
-    auto kern = bpp_fast_kernel<W, L, K, ROT, MODE>;
+    auto kern = bpp_fast_kernel<K, ROT, MODE>;
     if (l.lds > 64 * 1024) {  // large workgroups: opt in to more than 64 KiB of dynamic LDS, once per kernel AND device
         static std::atomic<uint64_t> raised{0};
         int dev = 0;
@@ -560,12 +700,12 @@ void launch_fast_rot(const Launch &l, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
 }
 
-template <int W, int L, int K, int MODE>
+template <int K, int MODE>
 void launch_fast(const Launch &l, hipStream_t s) {
     if (l.p.rotation)
-        launch_fast_rot<W, L, K, true, MODE>(l, s);
+        launch_fast_rot<K, true, MODE>(l, s);
     else
-        launch_fast_rot<W, L, K, false, MODE>(l, s);
+        launch_fast_rot<K, false, MODE>(l, s);
 }
 
 template <int W, int L, int K, int MODE, int EPW, int NIT>
@@ -612,22 +752,29 @@ void launch_tile(const Launch &l, hipStream_t s) {
         launch_tile_nit<W, L, K, MODE, EPW, 1>(l, s);
 }
 
+// LDS of the tile step kernel's workgroup for the launch shape of l (bpp_launch_info)
+template <int W, int L, int K, int EPW>
+size_t tile_lds_block(const Launch &l) {
+    if (l.p.rotation)
+        return l.nit == 4 ? TileGeo<W, L, K, true, EPW, 4>::LDS_BLOCK
+                          : (l.nit == 2 ? TileGeo<W, L, K, true, EPW, 2>::LDS_BLOCK : TileGeo<W, L, K, true, EPW, 1>::LDS_BLOCK);
+    return l.nit == 4 ? TileGeo<W, L, K, false, EPW, 4>::LDS_BLOCK
+                      : (l.nit == 2 ? TileGeo<W, L, K, false, EPW, 2>::LDS_BLOCK : TileGeo<W, L, K, false, EPW, 1>::LDS_BLOCK);
+}
+
 template <int MODE>
 int launch(const Launch &l, hipStream_t s) {
-    if (l.lds > (l.fast >= 0 ? 160 : 64) * 1024) return fail(BPP_E_TOOLARGE, "LDS request per workgroup too large");
-    if (l.tile == 0)
-        launch_tile<10, 10, 1, MODE, 4>(l, s);
-    else if (l.tile == 1)
-        launch_tile<20, 20, 1, MODE, 1>(l, s);
-    else if (l.tile == 2)
-        launch_tile<20, 20, 2, MODE, 1>(l, s);
-    else if (l.tile == 3)
-        launch_tile<10, 10, 2, MODE, 4>(l, s);
-    else if (l.fast == kRuntimeGeo)
-        launch_fast<0, 0, 1, MODE>(l, s);
-    else if (l.fast == kRuntimeGeo + 1)
-        launch_fast<0, 0, 2, MODE>(l, s);
-    else if (l.vec)
+    if (l.lds > (l.kind == BPP_KERNEL_PREFIX_RT ? 160 : 64) * 1024) return fail(BPP_E_TOOLARGE, "LDS request per workgroup too large");
+    if (l.kind == BPP_KERNEL_TILE)
+        with_tile_geo(l.tile, [&](auto g) {
+            constexpr TileGeoEntry t = kTileGeo[decltype(g)::value];
+            launch_tile<t.W, t.L, t.K, MODE, t.epw>(l, s);
+        });
+    else if (l.kind == BPP_KERNEL_PREFIX_RT && l.K == 1)
+        launch_fast<1, MODE>(l, s);
+    else if (l.kind == BPP_KERNEL_PREFIX_RT)
+        launch_fast<2, MODE>(l, s);
+    else if (l.p.A % 4 == 0)
         hipLaunchKernelGGL((bpp_kernel<true, MODE>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
     else
         hipLaunchKernelGGL((bpp_kernel<false, MODE>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
@@ -748,20 +895,18 @@ int bpp_launch_info(int32_t E, int32_t W, int32_t L, int32_t H, int32_t rotation
     int rc = check_geometry(E, W, L, H, rotation, BPP_RULE_UTILS);
     if (rc) return rc;
     const Launch l = configure(E, W, L, H, rotation, BPP_RULE_UTILS);
-    out[0] = l.tile >= 0 ? BPP_KERNEL_TILE : (l.fast >= 0 ? BPP_KERNEL_PREFIX_RT : BPP_KERNEL_CELLSCAN);
-    out[1] = l.tile >= 0 ? kTileGeo[l.tile].K : (l.fast >= 0 ? l.fast - kRuntimeGeo + 1 : 0);
+    out[0] = l.kind;
+    out[1] = l.K;
     out[2] = l.p.epw;
     out[3] = l.wpb;
     out[4] = l.blocks;
     size_t lds = l.lds;
-    if (l.tile >= 0) {   // step kernel shape (TileGeo<...>::LDS_BLOCK restated for runtime arguments)
-        const TileGeoEntry &g = kTileGeo[l.tile];
-        const int A = W * L, M = A * (1 + rotation), npass = (A + kWave - 1) / kWave, nbw = g.epw * l.nit;
-        const int off_mk = round16(nbw * A), off_rec = round16(off_mk + g.epw * M);
-        const int off_bal = (off_rec + nbw * (int)sizeof(TileRec) + 7) & ~7;
-        const int off_p = round16(off_bal + (npass > 2 ? g.epw * 2 * npass * 8 : 0));
-        lds = (size_t)kTileWaves * (off_p + g.epw * (W + 1) * (L + 1) * 8 * (g.epw == 1 ? 1 : g.K));   // TileGeo::KP
-        out[2] = nbw;
+    if (l.kind == BPP_KERNEL_TILE) {   // step kernel shape
+        with_tile_geo(l.tile, [&](auto g) {
+            constexpr TileGeoEntry t = kTileGeo[decltype(g)::value];
+            lds = tile_lds_block<t.W, t.L, t.K, t.epw>(l);
+        });
+        out[2] = l.p.epw * l.nit;
     }
     out[5] = (int32_t)lds;
     return 0;
@@ -795,9 +940,9 @@ int bpp_step(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out
     if (rc) return rc;
     if (out->next_action && !out->mask) return fail(BPP_E_BADARG, "bpp_step: next_action needs mask");
     l.p.actions = actions;
-    if (l.fast < 0) l.p.next_action = nullptr;  // the generic kernel has no fused sampler ...
+    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;  // the generic kernel has no fused sampler ...
     rc = launch<kStep>(l, (hipStream_t)stream);
-    if (rc == 0 && l.fast < 0 && out->next_action)  // ... a separate launch draws from the mask it wrote
+    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action)  // ... a separate launch draws from the mask it wrote
         rc = bpp_sample_feasible(out->mask, out->next_action, b->num_envs, b->W * b->L * (1 + b->rotation),
                                  b->env_id_base, out->sample_seed, out->sample_step, stream);
     return rc;

@@ -1,7 +1,7 @@
 // bpp_rt_kernels.inl -- the two step / reset / mask kernels with RUNTIME geometry, included by bpp_kernels.hip inside its anonymous
-// namespace (round 6: moved out of that file unchanged): bpp_kernel (cell scan: any W*L <= 1024) and bpp_fast_kernel (packed-histogram
-// prefix image: W*L % 4 == 0, H <= 22), plus the prefix-image primitives (Ent, code_of, top_of, window_top, build_prefix_one_bin) that
-// the compile-time-geometry kernels of bpp_tile_kernel.inl share.  Params, the helpers above them and the host side: bpp_kernels.hip.
+// namespace: bpp_kernel (cell scan: any W*L <= 1024) and bpp_fast_kernel (packed-histogram prefix image: W*L % 4 == 0, H <= 22),
+// plus the prefix-image primitives (Ent, code_of, top_of, window_top, build_prefix_one_bin) that the compile-time-geometry
+// kernels of bpp_tile_kernel.inl share.  Params, the per-bin step chain and the other helpers: bpp_kernels.hip.
 
 template <bool VEC, int MODE>
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Params p) {
@@ -30,11 +30,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
     } else if (MODE == kMaskHmap) {
         const int32_t *gh = p.hmap_in + (size_t)e0 * A;
         if (VEC) {
-            for (int q = lane; q < ncell / 4; q += kWave) {
-                int4 v = ((const int4 *)gh)[q];
-                ((uint32_t *)hm)[q] = min((uint32_t)v.x, 255u) | (min((uint32_t)v.y, 255u) << 8) | (min((uint32_t)v.z, 255u) << 16) |
-                                      (min((uint32_t)v.w, 255u) << 24);
-            }
+            for (int q = lane; q < ncell / 4; q += kWave) ((uint32_t *)hm)[q] = byte_quad(((const int4 *)gh)[q]);
         } else {
             for (int c = lane; c < ncell; c += kWave) hm[c] = (uint8_t)min((uint32_t)gh[c], 255u);
         }
@@ -43,9 +39,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
         if (VEC) {
             for (int q = lane; q < ncell / 4; q += kWave) {
                 uint32_t el = p.divA4.div(q);  // bin within the wave (A/4 quads per bin)
-                float4 v = ((const float4 *)(p.obs_in + (size_t)(e0 + el) * 4 * A))[q - el * (A / 4)];
-                ((uint32_t *)hm)[q] = min((uint32_t)(int)v.x, 255u) | (min((uint32_t)(int)v.y, 255u) << 8) |
-                                      (min((uint32_t)(int)v.z, 255u) << 16) | (min((uint32_t)(int)v.w, 255u) << 24);
+                ((uint32_t *)hm)[q] = byte_quad(((const float4 *)(p.obs_in + (size_t)(e0 + el) * 4 * A))[q - el * (A / 4)]);
             }
         } else {
             for (int c = lane; c < ncell; c += kWave) {
@@ -78,103 +72,42 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
             // BoxCreator.preview(1)[0] (binCreator.py:15-18): the current item, the one after it and the
             // first item of the next episode are cached in the state record; the entries the NEXT step
             // will need are fetched here, speculatively for both outcomes, off the critical path.
-            const int T = p.T;
-            int seq_n = st.seq + p.seq_stride;
-            seq_n = seq_n >= p.P ? seq_n - p.P : seq_n;
-            int seq_nn = seq_n + p.seq_stride;
-            seq_nn = seq_nn >= p.P ? seq_nn - p.P : seq_nn;
-            const uint32_t it_cur = st.item_cur, it_nxt = st.item_next, it_rst = st.item_reset;
+            const int seq_n = next_row(p, st.seq), seq_nn = next_row(p, seq_n);
             const LookAheadAt la = look_ahead_at(p, st.seq, seq_n, seq_nn, st.cursor);
             const uint32_t sp_ok = p.pool[la.ok], sp_f1 = p.pool[la.f1], sp_f2 = p.pool[la.f2];
-            const int ix = it_cur & 255, iy = (it_cur >> 8) & 255, iz = (it_cur >> 16) & 255;
-            // bin3D.py:96-105: rotated iff idx > area (strict)
-            const bool noop = act == BPP_ACTION_NOOP;   // include/bpp_abi.h: the bin is left alone
-            int64_t idx = act;
-            const bool flag = p.rotation && idx > A;
-            if (flag) idx -= A;
-            const int x = flag ? iy : ix, y = flag ? ix : iy, z = iz;  // space.py:166-172
-            bool ok = idx >= 0 && idx < (int64_t)(p.W + 1) * L;
-            int lx = 0, ly = 0, top = 0;
-            if (ok) {
-                lx = (int)p.divL.div((uint32_t)idx);  // space.py:153-156
-                ly = (int)idx - lx * L;
-                ok = (lx + x <= p.W) && (ly + y <= L);  // space.py:112-115
+            Placement pl = decode_action(act, st.item_cur, p.rotation, true, p.W, L, [&](int n) { return (int)p.divL.div((uint32_t)n); });
+            int top = 0;
+            if (pl.ok) {
+                Win w = scan_window(hm + lane * A, L, pl.lx, pl.ly, pl.x, pl.y);
+                pl.ok = feasible(w, pl.x * pl.y, pl.z, p.H, BPP_RULE_SPACE);  // space.py:117-144
+                top = w.mh + pl.z;                                          // space.py:42-45 with lz = max_h
             }
-            if (ok) {
-                Win w = scan_window(hm + lane * A, L, lx, ly, x, y);
-                ok = feasible(w, x * y, z, p.H, BPP_RULE_SPACE);  // space.py:117-144
-                top = w.mh + z;                                   // space.py:42-45 with lz = max_h
-            }
-            const int vol = ix * iy * iz;
-            // bin3D.py:44-46,108-121: float64 (vol / binvol) * 10, 0.0 on failure
-            const double rew = ok ? ((double)vol / p.binvol) * 10.0 : 0.0;
-            st.n_boxes += ok ? 1 : 0;
-            st.vol_sum += ok ? vol : 0;
-            st.ep_ret = st.ep_ret + rew;  // bench/monitor.py:58-62 (sum in step order)
-            st.ep_len += noop ? 0 : 1;
-            p.reward[e] = (float)rew;     // acktr/envs.py:192
-            p.done[e] = (ok || noop) ? 0 : 1;
+            const StepOutcome o = step_outcome(p, st, pl.ok, pl.noop, top, seq_n, sp_ok, sp_f1, sp_f2);
+            p.reward[e] = (float)o.rew;     // acktr/envs.py:192
+            p.done[e] = (pl.ok || pl.noop) ? 0 : 1;
             if (p.host_reward) {
-                p.host_reward[e] = (float)rew;
-                p.host_done[e] = (ok || noop) ? 0 : 1;
+                p.host_reward[e] = (float)o.rew;
+                p.host_done[e] = (pl.ok || pl.noop) ? 0 : 1;
             }
-            p.counter[e] = st.n_boxes;    // bin3D.py:111,124
-            p.ratio[e] = (double)st.vol_sum / p.binvol;  // space.py:146-151
-            p.ep_ret[e] = st.ep_ret;
-            p.ep_len[e] = st.ep_len;
-            fin = !ok && !noop;
-            fin_ret = st.ep_ret;
-            fin_ratio = (double)st.vol_sum / p.binvol;
-            fin_len = st.ep_len;
-            if (ok) {
-                st.cursor += 1;  // bin3D.py:116-117
-                st.item_cur = it_nxt;
-                st.item_next = sp_ok;
-                st.hmax = max(st.hmax, (uint32_t)top);   // highest cell of the bin
-                r.item = it_nxt;
-                r.place = (uint32_t)lx | ((uint32_t)ly << 8) | ((uint32_t)x << 16) | ((uint32_t)y << 24);
+            p.counter[e] = o.boxes;
+            p.ratio[e] = o.ratio;
+            p.ep_ret[e] = o.ret;
+            p.ep_len[e] = o.len;
+            fin = o.fin;
+            fin_ret = o.ret;
+            fin_ratio = o.ratio;
+            fin_len = o.len;
+            r.item = st.item_cur;
+            if (pl.ok) {
+                r.place = (uint32_t)pl.lx | ((uint32_t)pl.ly << 8) | ((uint32_t)pl.x << 16) | ((uint32_t)pl.y << 24);
                 r.flags = 1u | ((uint32_t)top << 8);
-            } else if (noop) {
-                r.item = it_cur;
-            } else {  // shmem_vec_env.py:128-129 auto-reset; bin3D.py:55-59
-                st.episode += 1;
-                st.seq = seq_n;
-                st.cursor = 0;
-                st.n_boxes = 0;
-                st.vol_sum = 0;
-                st.ep_ret = 0.0;
-                st.ep_len = 0;
-                st.item_cur = it_rst;
-                st.item_next = sp_f1;
-                st.item_reset = sp_f2;
-                st.hmax = 0;
-                r.item = it_rst;
+            } else if (!pl.noop) {
                 r.flags = 2u;
             }
             p.state[e] = st;
             if (p.cache != nullptr) row_cache_drop(p, e);
         } else if (MODE == kResetInit || MODE == kResetAdvance) {
-            bpp_env_state st;
-            if (MODE == kResetInit) {
-                st.episode = 0;
-                st.seq = (int32_t)(((uint32_t)p.base_mod + (uint32_t)e) % (uint32_t)p.P);
-            } else {
-                st = p.state[e];
-                st.episode += 1;
-                int s = st.seq + p.seq_stride;
-                st.seq = s >= p.P ? s - p.P : s;
-            }
-            st.cursor = 0;
-            st.n_boxes = 0;
-            st.vol_sum = 0;
-            st.ep_ret = 0.0;
-            st.ep_len = 0;
-            int sn = st.seq + p.seq_stride;
-            sn = sn >= p.P ? sn - p.P : sn;
-            st.item_cur = p.pool[(size_t)st.seq * p.T + p.ring2];
-            st.item_next = p.pool[(size_t)st.seq * p.T + p.ring2 + min(1, p.T - 1 - p.ring2)];
-            st.item_reset = p.pool[(size_t)sn * p.T + p.ring2];
-            st.hmax = 0;
+            const bpp_env_state st = reset_state<MODE>(p, e);
             p.state[e] = st;
             if (p.cache != nullptr) row_cache_drop(p, e);
             r.item = st.item_cur;
@@ -231,8 +164,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
                     if (VEC) {
                         const uint32_t v = ((uint32_t *)hm)[el * per_plane + k];
                         ((uint32_t *)gh)[el * per_plane + k] = v;
-                        ((float4 *)go)[g] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u),
-                                                        (float)(v >> 24));
+                        ((float4 *)go)[g] = quad_floats(v);
                     } else {
                         const int v = hm[el * A + k];
                         gh[el * A + k] = (uint8_t)v;
@@ -275,9 +207,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
             const int per = M / 4;
             for (int g = lane; g < nenv * per; g += kWave) {
                 const uint32_t el = p.divA4.div(p.rotation ? (g >> 1) : g);  // g / (M/4)
-                const uint32_t v = rec[el].any ? ((uint32_t *)mk)[g] : 0x01010101u;
-                ((float4 *)gm)[g] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u),
-                                                (float)(v >> 24));
+                ((float4 *)gm)[g] = quad_floats(rec[el].any ? ((uint32_t *)mk)[g] : 0x01010101u);
             }
         } else {
             for (int c = lane; c < nenv * M; c += kWave) {
@@ -290,7 +220,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
 
 
 // =================================================================================================
-// Fast path: compile-time geometry + packed-histogram integral image
+// Prefix-image path: packed-histogram integral image
 // =================================================================================================
 // The generic kernel above walks every candidate's x*y window cell by cell (14 instructions and one
 // LDS round trip per cell).  Here every cell of height h is coded as the 64-bit integer 1 << (5*h)
@@ -533,19 +463,16 @@ __device__ __forceinline__ OriRec make_ori(int W, int L, int x, int y, int z, in
     return o;
 }
 
-template <int W, int L, int K, bool ROT, int MODE>
+// Sizes come from the launch parameters, divisions by them from their precomputed magic numbers (Params::div*).
+template <int K, bool ROT, int MODE>
 __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel(const Params p) {
-    // W == 0 selects the runtime-geometry instantiation: sizes come from the launch parameters and the
-    // divisions below use their precomputed magic numbers; with W, L > 0 everything folds to constants.
-    constexpr bool RT = (W == 0);
-    static_assert(RT || (W * L) % 4 == 0, "fast path needs W*L % 4 == 0");
-    const int Wv = RT ? p.W : W, Lv = RT ? p.L : L;
-    const int A = Wv * Lv, A4 = A / 4, M = ROT ? 2 * A : A, M4 = M / 4, PW = Lv + 1, PN = (Wv + 1) * (Lv + 1);
-    auto div_a4 = [&](int n) { return RT ? (int)p.divA4.div((uint32_t)n) : n / A4; };
-    auto div_m4 = [&](int n) { return RT ? (int)p.divM4.div((uint32_t)n) : n / M4; };
-    auto div_l = [&](int n) { return RT ? (int)p.divL.div((uint32_t)n) : n / Lv; };
-    auto div_w = [&](int n) { return RT ? (int)p.divW.div((uint32_t)n) : n / Wv; };
-    auto div_pww = [&](int n) { return RT ? (int)p.divPWW.div((uint32_t)n) : n / (PW + Wv); };
+    const int W = p.W, L = p.L;
+    const int A = W * L, A4 = A / 4, M = ROT ? 2 * A : A, M4 = M / 4, PW = L + 1, PN = (W + 1) * (L + 1);
+    auto div_a4 = [&](int n) { return (int)p.divA4.div((uint32_t)n); };
+    auto div_m4 = [&](int n) { return (int)p.divM4.div((uint32_t)n); };
+    auto div_l = [&](int n) { return (int)p.divL.div((uint32_t)n); };
+    auto div_w = [&](int n) { return (int)p.divW.div((uint32_t)n); };
+    auto div_pww = [&](int n) { return (int)p.divPWW.div((uint32_t)n); };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = threadIdx.x >> 6;
@@ -579,17 +506,11 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
         for (int q = lane; q < (BPP_ABL(p, 64) ? 0 : nenv * A4); q += kWave) hm32[q] = gh[q];
     } else if (MODE == kMaskHmap) {
         const int4 *gh = (const int4 *)(p.hmap_in + (size_t)e0 * A);
-        for (int q = lane; q < nenv * A4; q += kWave) {
-            const int4 v = gh[q];
-            hm32[q] = min((uint32_t)v.x, 255u) | (min((uint32_t)v.y, 255u) << 8) | (min((uint32_t)v.z, 255u) << 16) |
-                      (min((uint32_t)v.w, 255u) << 24);
-        }
+        for (int q = lane; q < nenv * A4; q += kWave) hm32[q] = byte_quad(gh[q]);
     } else if (MODE == kMaskObs) {
         for (int q = lane; q < nenv * A4; q += kWave) {
             const int el = div_a4(q);
-            const float4 v = ((const float4 *)(p.obs_in + (size_t)(e0 + el) * 4 * A))[q - el * A4];
-            hm32[q] = min((uint32_t)(int)v.x, 255u) | (min((uint32_t)(int)v.y, 255u) << 8) |
-                      (min((uint32_t)(int)v.z, 255u) << 16) | (min((uint32_t)(int)v.w, 255u) << 24);
+            hm32[q] = byte_quad(((const float4 *)(p.obs_in + (size_t)(e0 + el) * 4 * A))[q - el * A4]);
         }
     } else {
         for (int q = lane; q < nenv * A4; q += kWave) hm32[q] = 0u;  // space.py:22
@@ -617,33 +538,16 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
         r.any = 0;
         if (MODE == kStep) {
             bpp_env_state st = st0;                                    // loaded before the tile was staged
-            const int64_t act = act0;
             // binCreator.py:15-18: current / next / first-of-next-episode items come from the state record;
             // the pool entries the NEXT step needs are fetched speculatively for both outcomes.
-            const int T = p.T;
-            int seq_n = st.seq + p.seq_stride;
-            seq_n = seq_n >= p.P ? seq_n - p.P : seq_n;
-            int seq_nn = seq_n + p.seq_stride;
-            seq_nn = seq_nn >= p.P ? seq_nn - p.P : seq_nn;
-            const uint32_t it_cur = st.item_cur, it_nxt = st.item_next, it_rst = st.item_reset;
+            const int seq_n = next_row(p, st.seq), seq_nn = next_row(p, seq_n);
             const LookAheadAt la = look_ahead_at(p, st.seq, seq_n, seq_nn, st.cursor);
             const uint32_t sp_ok = p.pool[la.ok], sp_f1 = p.pool[la.f1], sp_f2 = p.pool[la.f2];
-            const int ix = it_cur & 255, iy = (it_cur >> 8) & 255, iz = (it_cur >> 16) & 255;
-            const bool noop = act == BPP_ACTION_NOOP;                  // include/bpp_abi.h: the bin is left alone
-            int64_t idx = act;                                         // bin3D.py:96-105
-            const bool flag = ROT && idx > A;
-            if (flag) idx -= A;
-            const int x = flag ? iy : ix, y = flag ? ix : iy, z = iz;  // space.py:166-172
-            bool ok = active && idx >= 0 && idx < (int64_t)(Wv + 1) * Lv;
-            int lx = 0, ly = 0;
-            if (ok) {
-                lx = div_l((int)idx);                                  // space.py:153-156
-                ly = (int)idx - lx * Lv;
-                ok = (lx + x <= Wv) && (ly + y <= Lv);                 // space.py:112-115
-            }
+            Placement pl = decode_action(act0, st.item_cur, ROT, active, W, L, div_l);
+            const int x = pl.x, y = pl.y;
             int top = 0;
-            if (ok) {
-                const uint8_t *hb = ohm + lx * Lv + ly;
+            if (pl.ok) {
+                const uint8_t *hb = ohm + pl.lx * L + pl.ly;
                 int mh = 0, ma = 0;                                    // space.py:127-129
                 if (x <= 5 && y <= 5) {
                     // common item sizes: 25 predicated independent LDS reads instead of a divergent loop
@@ -651,7 +555,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
 #pragma unroll
                     for (int a = 0; a < 5; ++a)
 #pragma unroll
-                        for (int b = 0; b < 5; ++b) v[a][b] = (a < x && b < y) ? (int)hb[a * Lv + b] : -1;
+                        for (int b = 0; b < 5; ++b) v[a][b] = (a < x && b < y) ? (int)hb[a * L + b] : -1;
 #pragma unroll
                     for (int a = 0; a < 5; ++a)
 #pragma unroll
@@ -663,93 +567,42 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
                 } else {
                     for (int a = 0; a < x; ++a)
                         for (int b = 0; b < y; ++b) {
-                            const int v = hb[a * Lv + b];
+                            const int v = hb[a * L + b];
                             ma = v > mh ? 1 : ma + (v == mh);
                             mh = max(mh, v);
                         }
                 }
-                const int r00 = hb[0], r10 = hb[(x - 1) * Lv], r01 = hb[y - 1], r11 = hb[(x - 1) * Lv + y - 1];
-                const int rm = max(max(r00, r10), max(r01, r11));      // space.py:117-125
-                Win w;
-                w.mh = mh;
-                w.ma = ma;
-                w.c = (r00 == mh) + (r10 == mh) + (r01 == mh) + (r11 == mh);
-                w.sc = (r00 == rm) + (r10 == rm) + (r01 == rm) + (r11 == rm);
-                ok = feasible(w, x * y, z, p.H, BPP_RULE_SPACE);       // space.py:131-144
-                top = mh + z;                                          // space.py:42-45 with lz = max_h
+                pl.ok = feasible(corner_win(hb, L, x, y, mh, ma), x * y, pl.z, p.H, BPP_RULE_SPACE);   // space.py:131-144
+                top = mh + pl.z;                                       // space.py:42-45 with lz = max_h
             }
-            const int vol = ix * iy * iz;
-            const double rew = ok ? ((double)vol / p.binvol) * 10.0 : 0.0;  // bin3D.py:44-46,108-121
-            st.n_boxes += ok ? 1 : 0;
-            st.vol_sum += ok ? vol : 0;
-            st.ep_ret = st.ep_ret + rew;                               // bench/monitor.py:58-62
-            st.ep_len += noop ? 0 : 1;
-            const double ratio = (double)st.vol_sum / p.binvol;        // space.py:146-151
+            const StepOutcome o = step_outcome(p, st, pl.ok, pl.noop, top, seq_n, sp_ok, sp_f1, sp_f2);
             if (active) {
-                p.reward[e] = (float)rew;                              // acktr/envs.py:192
-                p.done[e] = (ok || noop) ? 0 : 1;
+                p.reward[e] = (float)o.rew;                            // acktr/envs.py:192
+                p.done[e] = (pl.ok || pl.noop) ? 0 : 1;
                 if (p.host_reward) {
-                    p.host_reward[e] = (float)rew;
-                    p.host_done[e] = (ok || noop) ? 0 : 1;
+                    p.host_reward[e] = (float)o.rew;
+                    p.host_done[e] = (pl.ok || pl.noop) ? 0 : 1;
                 }
-                p.counter[e] = st.n_boxes;                             // bin3D.py:111,124
-                p.ratio[e] = ratio;
-                p.ep_ret[e] = st.ep_ret;
-                p.ep_len[e] = st.ep_len;
+                p.counter[e] = o.boxes;
+                p.ratio[e] = o.ratio;
+                p.ep_ret[e] = o.ret;
+                p.ep_len[e] = o.len;
             }
-            fin = active && !ok && !noop;
-            fin_ret = st.ep_ret;
-            fin_ratio = ratio;
-            fin_len = st.ep_len;
-            if (ok) {
-                st.cursor += 1;                                        // bin3D.py:116-117
-                st.item_cur = it_nxt;
-                st.item_next = sp_ok;
-                st.hmax = max(st.hmax, (uint32_t)top);                 // highest cell of the bin
-                r.item = it_nxt;
-                r.place = (uint32_t)lx | ((uint32_t)ly << 8) | ((uint32_t)x << 16) | ((uint32_t)y << 24);
+            fin = active && o.fin;
+            fin_ret = o.ret;
+            fin_ratio = o.ratio;
+            fin_len = o.len;
+            r.item = st.item_cur;
+            if (pl.ok) {
+                r.place = (uint32_t)pl.lx | ((uint32_t)pl.ly << 8) | ((uint32_t)x << 16) | ((uint32_t)y << 24);
                 r.flags = 1u | ((uint32_t)top << 8);
-            } else if (noop) {
-                r.item = it_cur;
-            } else {                                                   // shmem_vec_env.py:128-129
-                st.episode += 1;
-                st.seq = seq_n;
-                st.cursor = 0;
-                st.n_boxes = 0;
-                st.vol_sum = 0;
-                st.ep_ret = 0.0;
-                st.ep_len = 0;
-                st.item_cur = it_rst;
-                st.item_next = sp_f1;
-                st.item_reset = sp_f2;
-                st.hmax = 0;
-                r.item = it_rst;
+            } else if (!pl.noop) {
                 r.flags = 2u;
             }
             if (active) p.state[e] = st;
             if (active && p.cache != nullptr) row_cache_drop(p, e);
         } else if (MODE == kResetInit || MODE == kResetAdvance) {
-            bpp_env_state st;
-            if (MODE == kResetInit) {
-                st.episode = 0;
-                st.seq = (int32_t)(((uint32_t)p.base_mod + (uint32_t)e) % (uint32_t)p.P);
-            } else {
-                st = p.state[e];
-                st.episode += 1;
-                const int sq = st.seq + p.seq_stride;
-                st.seq = sq >= p.P ? sq - p.P : sq;
-            }
-            st.cursor = 0;
-            st.n_boxes = 0;
-            st.vol_sum = 0;
-            st.ep_ret = 0.0;
-            st.ep_len = 0;
-            int sn = st.seq + p.seq_stride;
-            sn = sn >= p.P ? sn - p.P : sn;
-            st.item_cur = p.pool[(size_t)st.seq * p.T + p.ring2];
-            st.item_next = p.pool[(size_t)st.seq * p.T + p.ring2 + min(1, p.T - 1 - p.ring2)];
-            st.item_reset = p.pool[(size_t)sn * p.T + p.ring2];
-            st.hmax = 0;
+            const bpp_env_state st = reset_state<MODE>(p, e);
             if (active) p.state[e] = st;
             if (active && p.cache != nullptr) row_cache_drop(p, e);
             r.item = st.item_cur;
@@ -765,8 +618,8 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             ((BinRec *)(ob + p.off_rec))[oel] = r;
             OriRec *oo = (OriRec *)(ob + p.off_ori) + oel * 2;
             const int nx = r.item & 255u, ny = (r.item >> 8) & 255u, nz = (r.item >> 16) & 255u;
-            oo[0] = make_ori(Wv, Lv, nx, ny, nz, p.H);
-            if (ROT) oo[1] = make_ori(Wv, Lv, ny, nx, nz, p.H);          // utils.py:81-84
+            oo[0] = make_ori(W, L, nx, ny, nz, p.H);
+            if (ROT) oo[1] = make_ori(W, L, ny, nx, nz, p.H);          // utils.py:81-84
         }
     }
     __syncthreads();
@@ -783,10 +636,10 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             const BinRec r = rec[el];
             if (r.flags & 1u) {
                 const int lx = r.place & 255u, ly = (r.place >> 8) & 255u, x = (r.place >> 16) & 255u, y = r.place >> 24;
-                uint8_t *hb = hm + el * A + lx * Lv + ly;
+                uint8_t *hb = hm + el * A + lx * L + ly;
                 const uint8_t top = (uint8_t)(r.flags >> 8);
                 for (int a = sl; a < x; a += G)
-                    for (int b = 0; b < y; ++b) hb[a * Lv + b] = top;
+                    for (int b = 0; b < y; ++b) hb[a * L + b] = top;
             }
         }
         wave_sync();
@@ -799,8 +652,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             const int el = div_a4(q);
             const uint32_t v = hm32[q];
             gh[q] = v;
-            go[q + el * (3 * A4)] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u),
-                                                (float)(v >> 24));
+            go[q + el * (3 * A4)] = quad_floats(v);
         }
         // planes x, y, z are constants per bin (bin3D.py:49-53): bin-uniform passes, the value comes from a
         // scalar register and every lane keeps one fixed offset
@@ -829,71 +681,36 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
     }
 
     // ---- phase 4a: prefix image of the height-level codes ------------------------------------------
-    bool built = false;
-    if constexpr (!RT) {
-        if (!BPP_ABL(p, 1) && p.epw == 1 && W * 2 <= kWave) {
-            if (nenv > 0) build_prefix_one_bin<W, L, K>(hm, P, hclamp, lane);
-            built = true;
-        }
-    }
-    if (!built && !BPP_ABL(p, 1)) {
+    if (!BPP_ABL(p, 1)) {
         Ent<K> zero;
 #pragma unroll
         for (int k = 0; k < K; ++k) zero.w[k] = 0;
-        for (int t = lane; t < nenv * (PW + Wv); t += kWave) {         // row 0 and column 0
-            const int el = div_pww(t), r = t - el * (PW + Wv);
+        for (int t = lane; t < nenv * (PW + W); t += kWave) {         // row 0 and column 0
+            const int el = div_pww(t), r = t - el * (PW + W);
             P[el * PN + (r < PW ? r : (r - PW + 1) * PW)] = zero;
         }
-        for (int t = lane; t < nenv * Wv; t += kWave) {                // running sums along each row
-            const int el = div_w(t), i = t - el * Wv;
-            const uint8_t *row = hm + el * A + i * Lv;
+        for (int t = lane; t < nenv * W; t += kWave) {                // running sums along each row
+            const int el = div_w(t), i = t - el * W;
+            const uint8_t *row = hm + el * A + i * L;
             Ent<K> *pr = P + el * PN + (i + 1) * PW + 1;
             Ent<K> s = zero;
-            if constexpr (!RT) {
-                uint32_t hv[L > 0 ? L : 1];
+            for (int j = 0; j < L; ++j) {
+                const Ent<K> c = code_of<K>(min((uint32_t)row[j], hclamp));
 #pragma unroll
-                for (int j = 0; j < L; ++j) hv[j] = row[j];
-#pragma unroll
-                for (int j = 0; j < L; ++j) {
-                    const Ent<K> c = code_of<K>(min(hv[j], hclamp));
-#pragma unroll
-                    for (int k = 0; k < K; ++k) s.w[k] += c.w[k];
-                    pr[j] = s;
-                }
-            } else {
-                for (int j = 0; j < Lv; ++j) {
-                    const Ent<K> c = code_of<K>(min((uint32_t)row[j], hclamp));
-#pragma unroll
-                    for (int k = 0; k < K; ++k) s.w[k] += c.w[k];
-                    pr[j] = s;
-                }
+                for (int k = 0; k < K; ++k) s.w[k] += c.w[k];
+                pr[j] = s;
             }
         }
         wave_sync();
-        for (int t = lane; t < nenv * Lv; t += kWave) {                // then down each column
-            const int el = div_l(t), j = t - el * Lv;
+        for (int t = lane; t < nenv * L; t += kWave) {                // then down each column
+            const int el = div_l(t), j = t - el * L;
             Ent<K> *pc = P + el * PN + PW + (j + 1);
             Ent<K> s = zero;
-            if constexpr (!RT) {
-                constexpr int CH = W % 10 == 0 ? 10 : (W % 5 == 0 ? 5 : 1);
-                for (int i0 = 0; i0 < W; i0 += CH) {
-                    Ent<K> v[CH];
+            for (int i = 0; i < W; ++i) {
+                const Ent<K> v = pc[i * PW];
 #pragma unroll
-                    for (int i = 0; i < CH; ++i) v[i] = pc[(i0 + i) * PW];
-#pragma unroll
-                    for (int i = 0; i < CH; ++i) {
-#pragma unroll
-                        for (int k = 0; k < K; ++k) s.w[k] += v[i].w[k];
-                        pc[(i0 + i) * PW] = s;
-                    }
-                }
-            } else {
-                for (int i = 0; i < Wv; ++i) {
-                    const Ent<K> v = pc[i * PW];
-#pragma unroll
-                    for (int k = 0; k < K; ++k) s.w[k] += v.w[k];
-                    pc[i * PW] = s;
-                }
+                for (int k = 0; k < K; ++k) s.w[k] += v.w[k];
+                pc[i * PW] = s;
             }
         }
         wave_sync();
@@ -928,7 +745,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             const bool big = (oa >> 25) & 1u;
             const int nj = (int)(oc >> 24) + 1, nv = ((int)((oc >> 16) & 255u) + 1) * nj;
             const int t95 = ob & 0xffffu, t85 = ob >> 16, t50 = oc & 0xffffu;
-            const int o10 = (x - 1) * Lv, o01 = y - 1;
+            const int o10 = (x - 1) * L, o01 = y - 1;
             // one candidate loop per case, so that no bin-uniform condition is re-tested per candidate
             auto run = [&](auto big_c, auto empty_c) {
                 constexpr bool BIG = decltype(big_c)::value, EMPTY = decltype(empty_c)::value;
@@ -950,7 +767,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
                         } else {
                             window_top<K>(Pe, PW, i, j, x, y, mh, ma);
                         }
-                        const uint8_t *hb = he + i * Lv + j;
+                        const uint8_t *hb = he + i * L + j;
                         const int r00 = hb[0], r10 = hb[o10], r01 = hb[o01], r11 = hb[o10 + o01];
                         const int cnt = (r00 == mh) + (r10 == mh) + (r01 == mh) + (r11 == mh);  // utils.py:23-26
                         const int thr = cnt == 4 ? t50 : (cnt == 3 ? t85 : t95);
@@ -960,7 +777,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
                             f = f && ((r00 == rm) + (r10 == rm) + (r01 == rm) + (r11 == rm) >= 3);
                         }
                     }
-                    me[rot * A + i * Lv + j] = f ? 1 : 0;
+                    me[rot * A + i * L + j] = f ? 1 : 0;
                     any |= __ballot(f);
                 }
             };
@@ -1027,8 +844,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
     {
         float4 *gm = (float4 *)(p.mask + (size_t)e0 * M);
         for (int g = lane; g < (BPP_ABL(p, 4) ? 0 : nenv * M4); g += kWave) {
-            const uint32_t v = rec[div_m4(g)].any ? ((const uint32_t *)mk)[g] : 0x01010101u;
-            gm[g] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u), (float)(v >> 24));
+            gm[g] = quad_floats(rec[div_m4(g)].any ? ((const uint32_t *)mk)[g] : 0x01010101u);
         }
     }
 }

@@ -96,20 +96,12 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
                 const int4 *gh = (const int4 *)(p.hmap_in + (size_t)(e0 + el) * A) + sl;
 #pragma unroll
                 for (int k = 0; k < KQ; ++k)
-                    if (mine && sl + G * k < A4) {
-                        const int4 v = gh[G * k];
-                        hm32[el * A4 + sl + G * k] = min((uint32_t)v.x, 255u) | (min((uint32_t)v.y, 255u) << 8) |
-                                                     (min((uint32_t)v.z, 255u) << 16) | (min((uint32_t)v.w, 255u) << 24);
-                    }
+                    if (mine && sl + G * k < A4) hm32[el * A4 + sl + G * k] = byte_quad(gh[G * k]);
             } else if (MODE == kMaskObs) {
                 const float4 *go = (const float4 *)(p.obs_in + (size_t)(e0 + el) * 4 * A) + sl;  // acktr/utils.py:41-47
 #pragma unroll
                 for (int k = 0; k < KQ; ++k)
-                    if (mine && sl + G * k < A4) {
-                        const float4 v = go[G * k];
-                        hm32[el * A4 + sl + G * k] = min((uint32_t)(int)v.x, 255u) | (min((uint32_t)(int)v.y, 255u) << 8) |
-                                                     (min((uint32_t)(int)v.z, 255u) << 16) | (min((uint32_t)(int)v.w, 255u) << 24);
-                    }
+                    if (mine && sl + G * k < A4) hm32[el * A4 + sl + G * k] = byte_quad(go[G * k]);
             } else {
 #pragma unroll
                 for (int k = 0; k < KQ; ++k)
@@ -145,14 +137,9 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
         r.flags = 0;
         if (MODE == kStep) {
             bpp_env_state st = st0;
-            const int64_t act = act0;
             // binCreator.py:15-18: current / next / first-of-next-episode items come from the state record;
             // the pool entries the NEXT step needs are fetched speculatively for both outcomes.
-            int seq_n = st.seq + p.seq_stride;
-            seq_n = seq_n >= p.P ? seq_n - p.P : seq_n;
-            int seq_nn = seq_n + p.seq_stride;
-            seq_nn = seq_nn >= p.P ? seq_nn - p.P : seq_nn;
-            const uint32_t it_cur = st.item_cur, it_nxt = st.item_next, it_rst = st.item_reset;
+            const int seq_n = next_row(p, st.seq), seq_nn = next_row(p, seq_n);
             uint32_t sp_ok, sp_f1, sp_f2;
             if constexpr (CACHE) {
                 // The control word says whether the current line answers this step's look-ahead; the three loads (from the
@@ -173,27 +160,16 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
                 const uint32_t *a_f1 = hit ? ln + (d == 0u ? 8 : 0) : p.pool + la.f1;
                 const uint32_t *a_f2 = hit ? ln + (d == 0u ? 9 : 1) : p.pool + la.f2;
                 la_ok = *a_ok, la_f1 = *a_f1, la_f2 = *a_f2;
-                sp_ok = it_nxt, sp_f1 = it_nxt, sp_f2 = it_rst;                               // (placeholders: patched behind the barrier)
+                sp_ok = st.item_next, sp_f1 = st.item_next, sp_f2 = st.item_reset;           // (placeholders: patched behind the barrier)
             } else {
                 const LookAheadAt la = look_ahead_at(p, st.seq, seq_n, seq_nn, st.cursor);
                 sp_ok = p.pool[la.ok], sp_f1 = p.pool[la.f1], sp_f2 = p.pool[la.f2];
             }
-            const int ix = it_cur & 255, iy = (it_cur >> 8) & 255, iz = (it_cur >> 16) & 255;
-            const bool noop = act == BPP_ACTION_NOOP;                  // include/bpp_abi.h: the bin is left alone
-            int64_t idx = act;                                         // bin3D.py:96-105
-            const bool flag = ROT && idx > A;
-            if (flag) idx -= A;
-            const int x = flag ? iy : ix, y = flag ? ix : iy, z = iz;  // space.py:166-172
-            bool ok = dactive && idx >= 0 && idx < (int64_t)(W + 1) * L;
-            int lx = 0, ly = 0;
-            if (ok) {
-                lx = (int)idx / L;                                     // space.py:153-156
-                ly = (int)idx - lx * L;
-                ok = (lx + x <= W) && (ly + y <= L);                   // space.py:112-115
-            }
+            Placement pl = decode_action(act0, st.item_cur, ROT, dactive, W, L, [](int n) { return n / L; });
+            const int x = pl.x, y = pl.y;
             int top = 0;
-            if (ok) {   // uniform over the bin's LPB lanes
-                const uint8_t *hb = ohm + lx * L + ly;
+            if (pl.ok) {   // uniform over the bin's LPB lanes
+                const uint8_t *hb = ohm + pl.lx * L + pl.ly;
                 int mh = 0, ma = 0;                                    // space.py:127-129
                 if (x <= 5 && y <= 5) {
                     // common item sizes: rows ql, ql + LPB, ... of the window in this lane, predicated reads
@@ -242,16 +218,15 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
 #pragma unroll
                     for (int d = 1; d < LPB; d <<= 1) merge(__shfl_xor(mh, d, kWave), __shfl_xor(ma, d, kWave));
                 }
-                const int r00 = hb[0], r10 = hb[(x - 1) * L], r01 = hb[y - 1], r11 = hb[(x - 1) * L + y - 1];
-                const int rm = max(max(r00, r10), max(r01, r11));      // space.py:117-125
-                Win w;
-                w.mh = mh;
-                w.ma = ma;
-                w.c = (r00 == mh) + (r10 == mh) + (r01 == mh) + (r11 == mh);
-                w.sc = (r00 == rm) + (r10 == rm) + (r01 == rm) + (r11 == rm);
-                ok = feasible(w, x * y, z, p.H, BPP_RULE_SPACE);       // space.py:131-144
-                top = mh + z;                                          // space.py:42-45 with lz = max_h
+                pl.ok = feasible(corner_win(hb, L, x, y, mh, ma), x * y, pl.z, p.H, BPP_RULE_SPACE);   // space.py:131-144
+                top = mh + pl.z;                                       // space.py:42-45 with lz = max_h
             }
+            // step_outcome (bpp_kernels.hip) spelled out: through that helper -- or begin_episode alone -- the compiler allocates
+            // the step kernels differently (vector registers -2 .. +2 depending on the shape, one shape gains a workgroup slot,
+            // another loses occupancy headroom).  Any change to the rules here goes into step_outcome too.
+            const uint32_t it_cur = st.item_cur, it_nxt = st.item_next, it_rst = st.item_reset;
+            const bool ok = pl.ok, noop = pl.noop;
+            const int ix = it_cur & 255, iy = (it_cur >> 8) & 255, iz = (it_cur >> 16) & 255;
             const int vol = ix * iy * iz;
             const double rew = ok ? ((double)vol / p.binvol) * 10.0 : 0.0;  // bin3D.py:44-46,108-121
             st.n_boxes += ok ? 1 : 0;
@@ -270,9 +245,9 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
                 st.cursor += 1;                                        // bin3D.py:116-117
                 st.item_cur = it_nxt;
                 st.item_next = sp_ok;
-                st.hmax = max(st.hmax, (uint32_t)top);                 // highest cell of the bin (space.py:42-45 raised the window to `top`)
+                st.hmax = max(st.hmax, (uint32_t)top);
                 r.item = it_nxt;
-                r.place = (uint32_t)lx | ((uint32_t)ly << 8) | ((uint32_t)x << 16) | ((uint32_t)y << 24);
+                r.place = (uint32_t)pl.lx | ((uint32_t)pl.ly << 8) | ((uint32_t)x << 16) | ((uint32_t)y << 24);
                 r.flags = 1u | ((uint32_t)top << 8) | (st.hmax <= (uint32_t)kLowTop ? 4u : 0u);
             } else if (noop) {
                 r.item = it_cur;
@@ -296,29 +271,9 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
             // record -- instead of speculatively before the decision was measured twice, state store right after the loads
             // and state tail stored at the end of the kernel: 28.3 -> 28.9 / 29.2 us, stream mode 52.4 -> 55.3 us per lock-step.)
             st_out = st;
-            if constexpr (CACHE) outcome = ok ? 1u : (noop ? 0u : 2u);
+            if constexpr (CACHE) outcome = pl.ok ? 1u : (pl.noop ? 0u : 2u);
         } else if (MODE == kResetInit || MODE == kResetAdvance) {
-            bpp_env_state st;
-            if (MODE == kResetInit) {
-                st.episode = 0;
-                st.seq = (int32_t)(((uint32_t)p.base_mod + (uint32_t)e) % (uint32_t)p.P);
-            } else {
-                st = p.state[e];
-                st.episode += 1;
-                const int sq = st.seq + p.seq_stride;
-                st.seq = sq >= p.P ? sq - p.P : sq;
-            }
-            st.cursor = 0;
-            st.n_boxes = 0;
-            st.vol_sum = 0;
-            st.ep_ret = 0.0;
-            st.ep_len = 0;
-            int sn = st.seq + p.seq_stride;
-            sn = sn >= p.P ? sn - p.P : sn;
-            st.item_cur = p.pool[(size_t)st.seq * p.T + p.ring2];
-            st.item_next = p.pool[(size_t)st.seq * p.T + p.ring2 + min(1, p.T - 1 - p.ring2)];
-            st.item_reset = p.pool[(size_t)sn * p.T + p.ring2];
-            st.hmax = 0;
+            const bpp_env_state st = reset_state<MODE>(p, e);
             if (lead) p.state[e] = st;
             if (lead && p.cache != nullptr) row_cache_drop(p, e);
             r.item = st.item_cur;
@@ -493,14 +448,11 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
                         if (pl == 0) {
                             const uint32_t v = hm32[el * A4 + q];
                             gh[G * k] = v;
-                            if constexpr (kNtOut)
-                                store_out4_nt(go + G * k, (float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u), (float)(v >> 24));
-                            else
-                                go[G * k] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u),
-                                                        (float)(v >> 24));
+                            if constexpr (kNtOut) store_out4_nt(go + G * k, quad_floats(v));
+                            else go[G * k] = quad_floats(v);
                         } else {
                             const float f = pl == 1 ? fx : (pl == 2 ? fy : fz);
-                            if constexpr (kNtOut) store_out4_nt(go + G * k, f, f, f, f);
+                            if constexpr (kNtOut) store_out4_nt(go + G * k, make_float4(f, f, f, f));
                             else go[G * k] = make_float4(f, f, f, f);
                         }
                     }
@@ -825,10 +777,8 @@ __global__ __launch_bounds__(kWave * kTileWaves) BPP_TILE_ATTR void BPP_TILE_NAM
             for (int k = 0; k < KM; ++k)
                 if (sl + G * k < M4) {
                     const uint32_t v = anyf ? mk32[el * M4 + sl + G * k] : 0x01010101u;
-                    if constexpr (kNtOut)
-                        store_out4_nt(gm + G * k, (float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u), (float)(v >> 24));
-                    else
-                        gm[G * k] = make_float4((float)(v & 255u), (float)((v >> 8) & 255u), (float)((v >> 16) & 255u), (float)(v >> 24));
+                    if constexpr (kNtOut) store_out4_nt(gm + G * k, quad_floats(v));
+                    else gm[G * k] = quad_floats(v);
                 }
         }
         if (it == NIT - 1) BPP_STAMP(p, 10);

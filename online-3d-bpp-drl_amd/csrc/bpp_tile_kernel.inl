@@ -157,8 +157,8 @@ typedef float bpp_v4f __attribute__((ext_vector_type(4)));
 #else
 typedef float bpp_v4f __attribute__((vector_size(16)));   // (the host emulator's compiler)
 #endif
-__device__ __forceinline__ void store_out4_nt(float4 *dst, float a, float b, float c, float d) {
-    __builtin_nontemporal_store((bpp_v4f){a, b, c, d}, (bpp_v4f *)dst);
+__device__ __forceinline__ void store_out4_nt(float4 *dst, float4 v) {
+    __builtin_nontemporal_store((bpp_v4f){v.x, v.y, v.z, v.w}, (bpp_v4f *)dst);
 }
 
 // The kernel itself, in its two forms (bpp_tile_body.inl).
