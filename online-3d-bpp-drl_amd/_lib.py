@@ -15,7 +15,8 @@ SRC = os.path.join(CSRC, "bpp_kernels.hip")
 BUILD_LIB = os.path.join(CSRC, "libbpp_hip.so")
 LIB = os.environ.get("BPP_HIP_LIB") or BUILD_LIB
 HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_abi.h")
-DEPS = [SRC, HDR, os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+BRANCH_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_branch.h")
+DEPS = [SRC, HDR, BRANCH_HDR, os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -28,6 +29,8 @@ SYMBOLS = ["bpp_abi_version", "bpp_last_error", "bpp_limits", "bpp_reset", "bpp_
            "bpp_mask_from_hmap", "bpp_sample_feasible", "bpp_episode_stats", "bpp_rollout_uniform", "bpp_masked_act", "bpp_gen_cut2", "bpp_gen_cut1", "bpp_gen_rs",
            "bpp_get_knobs", "bpp_set_knobs", "bpp_launch_info", "bpp_stream_sizes", "bpp_stream_init", "bpp_stream_refill",
            "bpp_rollout_uniform_stream", "bpp_masked_evaluate", "bpp_masked_evaluate_backward", "bpp_episode_acc_reduce", "bpp_rollout_uniform_sets", "bpp_fetch_to_host", "bpp_wait", "bpp_gather_finished", "bpp_epsilon_override", "bpp_side_create", "bpp_side_destroy", "bpp_mark", "bpp_wait_mark", "bpp_step_dropin", "bpp_masked_act_counter"]
+# include/bpp_branch.h: exported by libbpp_hip.so only (not part of bpp_abi.h, which the oracle library implements too)
+BRANCH_SYMBOLS = ["bpp_step_subset", "bpp_copy_bins"]
 
 
 class Batch(ctypes.Structure):
@@ -178,6 +181,12 @@ def lib():
         L.bpp_launch_info.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]
         L.bpp_get_knobs.argtypes = [ctypes.POINTER(Knobs)]
         L.bpp_set_knobs.argtypes = [ctypes.POINTER(Knobs)]
+        L.bpp_step_subset.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(StepOut),
+                                      ctypes.c_void_p, ctypes.c_void_p]
+        L.bpp_step_subset.restype = ctypes.c_int
+        L.bpp_copy_bins.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Stream), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                    ctypes.c_void_p]
+        L.bpp_copy_bins.restype = ctypes.c_int
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

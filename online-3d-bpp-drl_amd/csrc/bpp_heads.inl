@@ -412,13 +412,12 @@ __global__ __launch_bounds__(256) void masked_eval_bwd_kernel(const float *logit
     }
 }
 
-// Fallback for rows that are not a multiple of 4 floats or longer than 16 * 8 quads: one wave per bin.
-__global__ __launch_bounds__(256) void sample_kernel_generic(const float *mask, int64_t *actions, int E, int M,
-                                                             int64_t env_id_base, uint64_t seed, uint64_t step) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (e >= E) return;
-    const float *m = mask + (size_t)e * M;
+// One wave draws a uniform-feasible entry of mask row r, that of the bin with global id env_id_base + bin, into actions[r] (0
+// when nothing is feasible).
+template <typename Bin>
+__device__ __forceinline__ void sample_row_wave(const float *mask, int64_t *actions, int r, int M, int64_t env_id_base, Bin bin,
+                                                uint64_t seed, uint64_t step, int lane) {
+    const float *m = mask + (size_t)r * M;
     const int per = (M + kWave - 1) / kWave;
     const int b = min(lane * per, M), en = min(b + per, M);
     int cnt = 0;
@@ -431,21 +430,39 @@ __global__ __launch_bounds__(256) void sample_kernel_generic(const float *mask, 
     }
     const int total = __shfl(incl, kWave - 1, kWave);
     if (total == 0) {
-        if (lane == 0) actions[e] = 0;
+        if (lane == 0) actions[r] = 0;
         return;
     }
-    int pick = (int)__umulhi(mix32(mix32_base(seed, step), (uint32_t)(env_id_base + e)), (uint32_t)total);
+    int pick = (int)__umulhi(mix32(mix32_base(seed, step), (uint32_t)(env_id_base + bin)), (uint32_t)total);
     const int excl = incl - cnt;
     if (pick >= excl && pick < incl) {
         pick -= excl;
         for (int k = b; k < en; ++k)
             if (m[k] != 0.0f) {
                 if (pick == 0) {
-                    actions[e] = k;
+                    actions[r] = k;
                     break;
                 }
                 --pick;
             }
     }
+}
+
+// Fallback for rows that are not a multiple of 4 floats or longer than 16 * 8 quads: one wave per bin.
+__global__ __launch_bounds__(256) void sample_kernel_generic(const float *mask, int64_t *actions, int E, int M,
+                                                             int64_t env_id_base, uint64_t seed, uint64_t step) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= E) return;
+    sample_row_wave(mask, actions, e, M, env_id_base, e, seed, step, lane);
+}
+
+// The draw of a cell-scan subset step (bpp_step_subset with next_action): row i of the compact mask belongs to bin ids[i].
+__global__ __launch_bounds__(256) void sample_ids_kernel(const float *mask, int64_t *actions, const int64_t *ids, int n, int M,
+                                                         int64_t env_id_base, uint64_t seed, uint64_t step) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    sample_row_wave(mask, actions, i, M, env_id_base, ids[i], seed, step, lane);
 }
 

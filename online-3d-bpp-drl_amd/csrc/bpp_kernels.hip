@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "../../include/bpp_abi.h"
+#include "../../include/bpp_branch.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -130,6 +131,11 @@ struct Params {
     int64_t *next_action;
     uint64_t sample_seed, sample_step;
     int64_t env_id_base;
+    // subset step (the SUB kernels, bpp_step_subset): launch slot i stands for bin ids[i] and writes output row i, nsub slots;
+    // bad_ids: NULL or a counter of the slots whose id lies outside [0, E).  (Last: the fields above keep their kernel-argument offsets.)
+    const int64_t *ids;
+    int32_t *bad_ids;
+    int32_t nsub;
 };
 
 // Measured on gfx950 this round (profiles/r5e_ubench_sparse_exec_by_instruction.jsonl, tools/ubench sparse): a vector instruction of
@@ -476,6 +482,34 @@ __device__ __forceinline__ StepOutcome step_outcome(const Params &p, bpp_env_sta
     return o;
 }
 
+// ---- subset launches (bpp_step_subset): slot i of the launch stands for bin ids[i] ---------------------------------------
+// The bin of slot i: b = ids[i] when it lies in [0, E); false for a bad slot, which must not touch any bin.
+__device__ __forceinline__ bool sub_id(const Params &p, int i, int &b) {
+    const int64_t id = p.ids[i];
+    const bool ok = (uint64_t)id < (uint64_t)p.E;
+    b = ok ? (int)id : 0;
+    return ok;
+}
+// A bad slot: the outputs of a no-op of an empty bin, one count in p.bad_ids, and the record that makes the kernel emit a
+// zero observation and mask (item 0: no candidate fits; flags 2: the map is cleared; any = 1: no all-ones fallback).
+__device__ __forceinline__ void sub_noop(const Params &p, int i, BinRec &r) {
+    p.reward[i] = 0.0f;
+    p.done[i] = 0;
+    if (p.host_reward) {
+        p.host_reward[i] = 0.0f;
+        p.host_done[i] = 0;
+    }
+    p.counter[i] = 0;
+    p.ratio[i] = 0.0;
+    p.ep_ret[i] = 0.0;
+    p.ep_len[i] = 0;
+    r.item = 0;
+    r.place = 0;
+    r.flags = 2u;
+    r.any = 1u;
+    if (p.bad_ids) (void)__hip_atomic_fetch_add(p.bad_ids, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Byte tiles: four heights per dword, clamped to a byte on the way in.
 __device__ __forceinline__ uint32_t byte_quad(int4 v) {
     return min((uint32_t)v.x, 255u) | (min((uint32_t)v.y, 255u) << 8) | (min((uint32_t)v.z, 255u) << 16) | (min((uint32_t)v.w, 255u) << 24);
@@ -597,7 +631,8 @@ bpp_knobs current_knobs() {
     return g_knobs;
 }
 
-Launch configure(int E, int W, int L, int H, int rotation, int rule) {
+// tile = false: no tile kernel (the subset step runs the runtime-geometry kernels for every geometry).
+Launch configure(int E, int W, int L, int H, int rotation, int rule, bool tile = true) {
     Launch l;
     Params &p = l.p;
     memset(&p, 0, sizeof p);
@@ -624,7 +659,7 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule) {
     if (!kn.force_generic && vec && H + 2 <= kLevelsPerWord * 2) {
         l.kind = BPP_KERNEL_PREFIX_RT;
         l.K = H + 2 <= kLevelsPerWord ? 1 : 2;
-        if (!kn.legacy_fast && kn.bins_per_wave <= 0 && kn.waves_per_group <= 0)
+        if (tile && !kn.legacy_fast && kn.bins_per_wave <= 0 && kn.waves_per_group <= 0)
             for (int g = 0; g < kNumTileGeo; ++g)
                 if (kTileGeo[g].W == W && kTileGeo[g].L == L && H + 2 <= kLevelsPerWord * kTileGeo[g].K) {
                     l.kind = BPP_KERNEL_TILE;
@@ -684,9 +719,9 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule) {
     return l;
 }
 
-template <int K, bool ROT, int MODE>
+template <int K, bool ROT, int MODE, bool SUB>
 void launch_fast_rot(const Launch &l, hipStream_t s) {
-    auto kern = bpp_fast_kernel<K, ROT, MODE>;
+    auto kern = bpp_fast_kernel<K, ROT, MODE, SUB>;
     if (l.lds > 64 * 1024) {  // large workgroups: opt in to more than 64 KiB of dynamic LDS, once per kernel AND device
         static std::atomic<uint64_t> raised{0};
         int dev = 0;
@@ -700,12 +735,12 @@ void launch_fast_rot(const Launch &l, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
 }
 
-template <int K, int MODE>
+template <int K, int MODE, bool SUB>
 void launch_fast(const Launch &l, hipStream_t s) {
     if (l.p.rotation)
-        launch_fast_rot<K, true, MODE>(l, s);
+        launch_fast_rot<K, true, MODE, SUB>(l, s);
     else
-        launch_fast_rot<K, false, MODE>(l, s);
+        launch_fast_rot<K, false, MODE, SUB>(l, s);
 }
 
 template <int W, int L, int K, int MODE, int EPW, int NIT>
@@ -762,22 +797,23 @@ size_t tile_lds_block(const Launch &l) {
                       : (l.nit == 2 ? TileGeo<W, L, K, false, EPW, 2>::LDS_BLOCK : TileGeo<W, L, K, false, EPW, 1>::LDS_BLOCK);
 }
 
-template <int MODE>
+// SUB: the subset step (l configured without a tile kernel, grid over l.p.nsub slots).
+template <int MODE, bool SUB = false>
 int launch(const Launch &l, hipStream_t s) {
     if (l.lds > (l.kind == BPP_KERNEL_PREFIX_RT ? 160 : 64) * 1024) return fail(BPP_E_TOOLARGE, "LDS request per workgroup too large");
-    if (l.kind == BPP_KERNEL_TILE)
+    if (!SUB && l.kind == BPP_KERNEL_TILE)
         with_tile_geo(l.tile, [&](auto g) {
             constexpr TileGeoEntry t = kTileGeo[decltype(g)::value];
             launch_tile<t.W, t.L, t.K, MODE, t.epw>(l, s);
         });
     else if (l.kind == BPP_KERNEL_PREFIX_RT && l.K == 1)
-        launch_fast<1, MODE>(l, s);
+        launch_fast<1, MODE, SUB>(l, s);
     else if (l.kind == BPP_KERNEL_PREFIX_RT)
-        launch_fast<2, MODE>(l, s);
+        launch_fast<2, MODE, SUB>(l, s);
     else if (l.p.A % 4 == 0)
-        hipLaunchKernelGGL((bpp_kernel<true, MODE>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
+        hipLaunchKernelGGL((bpp_kernel<true, MODE, SUB>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
     else
-        hipLaunchKernelGGL((bpp_kernel<false, MODE>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
+        hipLaunchKernelGGL((bpp_kernel<false, MODE, SUB>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
 }
@@ -849,6 +885,55 @@ __global__ void eps_override_kernel(int64_t *actions, int E, int M, int64_t env_
     const uint32_t gid = (uint32_t)(env_id_base + e);
     const uint32_t h = mix32(mix32_base(seed ^ BPP_EPS_KEY_COIN, step), gid);
     if ((h >> 8) < eps_q24) actions[e] = (int64_t)__umulhi(mix32(mix32_base(seed ^ BPP_EPS_KEY_PICK, step), gid), (uint32_t)M);
+}
+
+// bpp_copy_bins (include/bpp_branch.h): one wave per pair copies what makes bin src the bin it is into bin dst -- the heightmap
+// row, the state record and, for a ring pool, the bin's ring rows (row k * E + bin, k < depth), generator record and gen_next.
+struct CopyArgs {
+    int32_t E, A, n;
+    int32_t T, depth, rec4;        // ring pool: entries per row, rows per bin, generator record in 16-byte units (0: static pool)
+    uint8_t *hmap;
+    bpp_env_state *state;
+    unsigned char *cache;          // bpp_batch.seq_cache or nullptr
+    uint32_t *ring;
+    uint4 *mt;
+    int32_t *gen_next;
+    const int64_t *src, *dst;
+};
+constexpr int kCopyWaves = 4;
+__global__ __launch_bounds__(kWave * kCopyWaves) void copy_bins_kernel(const CopyArgs c) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int i = (int)blockIdx.x * kCopyWaves + (int)(threadIdx.x >> 6);
+    if (i >= c.n) return;
+    const int64_t s64 = c.src[i], d64 = c.dst[i];
+    if ((uint64_t)s64 >= (uint64_t)c.E || (uint64_t)d64 >= (uint64_t)c.E) return;     // never outside the buffers
+    const int s = (int)s64, d = (int)d64;
+    if ((c.A & 3) == 0) {
+        const uint32_t *hs = (const uint32_t *)(c.hmap + (size_t)s * c.A);
+        uint32_t *hd = (uint32_t *)(c.hmap + (size_t)d * c.A);
+        for (int k = lane; k < c.A / 4; k += kWave) hd[k] = hs[k];
+    } else {
+        for (int k = lane; k < c.A; k += kWave) c.hmap[(size_t)d * c.A + k] = c.hmap[(size_t)s * c.A + k];
+    }
+    const bool ring = c.ring != nullptr;
+    if (lane < 12) {          // the 48-byte record; a ring row number encodes the bin: seq moves to dst's column
+        const int32_t w = ((const int32_t *)(c.state + s))[lane];
+        ((int32_t *)(c.state + d))[lane] = (ring && lane == 7) ? w + (d - s) : w;
+    }
+    if (ring) {
+        for (int k = 0; k < c.depth; ++k) {
+            const uint32_t *rs = c.ring + ((size_t)k * c.E + s) * c.T;
+            uint32_t *rd = c.ring + ((size_t)k * c.E + d) * c.T;
+            for (int t = lane; t < c.T; t += kWave) rd[t] = rs[t];
+        }
+        for (int k = lane; k < c.rec4; k += kWave) c.mt[(size_t)d * c.rec4 + k] = c.mt[(size_t)s * c.rec4 + k];
+        if (lane == 0) c.gen_next[d] = c.gen_next[s];
+    }
+    if (c.cache != nullptr && lane == 0) {   // dst's row cache lines no longer describe it
+        const RowCache rc = row_cache(c.cache, c.E);
+        rc.ctl[d] = make_uint2(0u, 0u);
+        rc.req[d] = 0ull;
+    }
 }
 
 }  // namespace
@@ -945,6 +1030,36 @@ int bpp_step(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out
     if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action)  // ... a separate launch draws from the mask it wrote
         rc = bpp_sample_feasible(out->mask, out->next_action, b->num_envs, b->W * b->L * (1 + b->rotation),
                                  b->env_id_base, out->sample_seed, out->sample_step, stream);
+    return rc;
+}
+
+int bpp_step_subset(const bpp_batch *b, const int64_t *ids, int32_t n, const int64_t *actions, const bpp_step_out *out,
+                    int32_t *bad_ids, void *stream) {
+    if (!b || !ids || !actions) return fail(BPP_E_BADARG, "bpp_step_subset: NULL pointer");
+    if (n < 0) return fail(BPP_E_BADARG, "bpp_step_subset: negative n");
+    if (((uintptr_t)ids & 7u) || ((uintptr_t)actions & 7u) || ((uintptr_t)bad_ids & 3u))
+        return fail(BPP_E_BADARG, "bpp_step_subset: ids / actions must be 8-byte aligned, bad_ids 4-byte aligned");
+    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    if (rc) return rc;
+    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule, false);
+    rc = fill_batch(l, b, out, true);
+    if (rc) return rc;
+    if (out->next_action && !out->mask) return fail(BPP_E_BADARG, "bpp_step_subset: next_action needs mask");
+    if (out->next_action && ((uintptr_t)out->next_action & 7u)) return fail(BPP_E_BADARG, "bpp_step_subset: next_action must be 8-byte aligned");
+    if (n == 0) return 0;
+    l.p.actions = actions;
+    l.p.ids = ids;
+    l.p.bad_ids = bad_ids;
+    l.p.nsub = n;
+    l.blocks = ((n + l.p.epw - 1) / l.p.epw + l.wpb - 1) / l.wpb;     // the grid covers the n slots, not the batch
+    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;     // as in bpp_step: a separate launch draws from the mask
+    rc = launch<kStep, true>(l, (hipStream_t)stream);
+    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action) {
+        hipLaunchKernelGGL(sample_ids_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, out->mask, out->next_action, ids, n,
+                           l.p.M, b->env_id_base, out->sample_seed, out->sample_step);
+        const hipError_t e = hipGetLastError();
+        rc = e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    }
     return rc;
 }
 
@@ -1611,5 +1726,47 @@ int bpp_episode_acc_reduce(double *ep_acc, int32_t E, double *acc, int32_t clear
     return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
 }
 
+
+int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, const int64_t *dst, int32_t n, void *stream) {
+    if (!b || !src || !dst || !b->hmap || !b->state) return fail(BPP_E_BADARG, "bpp_copy_bins: NULL pointer");
+    if (n < 0) return fail(BPP_E_BADARG, "bpp_copy_bins: negative n");
+    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    if (rc) return rc;
+    if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u) || ((uintptr_t)b->hmap & 3u) || !aligned16(b->state) || ((uintptr_t)b->seq_cache & 127u))
+        return fail(BPP_E_BADARG, "bpp_copy_bins: misaligned buffer");
+    CopyArgs c;
+    memset(&c, 0, sizeof c);
+    c.E = b->num_envs;
+    c.A = b->W * b->L;
+    c.n = n;
+    c.hmap = b->hmap;
+    c.state = b->state;
+    c.src = src;
+    c.dst = dst;
+    if (b->pool_mode == BPP_POOL_RING) {
+        if (!s) return fail(BPP_E_BADARG, "bpp_copy_bins: a ring pool needs its bpp_stream");
+        rc = check_stream(s);
+        if (rc) return rc;
+        if (s->num_envs != b->num_envs || (const void *)s->ring != (const void *)b->seq_pool || s->state != b->state ||
+            (int64_t)s->depth * s->num_envs != b->pool_size || s->pool_len != b->pool_len)
+            return fail(BPP_E_BADARG, "bpp_copy_bins: the bpp_stream is not the one of this batch's ring");
+        c.T = s->pool_len;
+        c.depth = s->depth;
+        c.rec4 = (s->rng == BPP_STREAM_RNG_COUNTER ? kCtrRec : kMtRec) / 4;
+        c.ring = (uint32_t *)s->ring;
+        c.mt = (uint4 *)s->mt;
+        c.gen_next = s->gen_next;
+        c.cache = (unsigned char *)b->seq_cache;
+    } else if (b->pool_mode == BPP_POOL_STATIC) {
+        if (s) return fail(BPP_E_BADARG, "bpp_copy_bins: a bpp_stream goes with BPP_POOL_RING");
+        if (b->seq_cache) return fail(BPP_E_BADARG, "bpp_batch: seq_cache goes with BPP_POOL_RING");
+    } else {
+        return fail(BPP_E_BADARG, "bpp_batch: unknown pool_mode");
+    }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(copy_bins_kernel, dim3((unsigned)((n + kCopyWaves - 1) / kCopyWaves)), dim3(kWave * kCopyWaves), 0, (hipStream_t)stream, c);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+}
 
 }  // extern "C"

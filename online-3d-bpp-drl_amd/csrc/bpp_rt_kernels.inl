@@ -3,14 +3,17 @@
 // plus the prefix-image primitives (Ent, code_of, top_of, window_top, build_prefix_one_bin) that the compile-time-geometry
 // kernels of bpp_tile_kernel.inl share.  Params, the per-bin step chain and the other helpers: bpp_kernels.hip.
 
-template <bool VEC, int MODE>
+// SUB: the subset step of bpp_fast_kernel (slot i steps bin p.ids[i], output row i).
+template <bool VEC, int MODE, bool SUB = false>
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Params p) {
+    static_assert(!SUB || MODE == kStep, "a subset launch steps");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = threadIdx.x >> 6;
     const int e0 = (xcd_block(p.xcd_remap) * (blockDim.x >> 6) + wid) * p.epw;
-    if (e0 >= p.E) return;  // no block-level barrier is ever used, a whole wave may leave
-    const int nenv = min(p.epw, p.E - e0);
+    const int NB = SUB ? p.nsub : p.E;     // bins (slots) of the launch
+    if (e0 >= NB) return;  // no block-level barrier is ever used, a whole wave may leave
+    const int nenv = min(p.epw, NB - e0);
     const int A = p.A, L = p.L, M = p.M;
     unsigned char *wb = smem + wid * p.lds_per_wave;
     uint8_t *hm = wb;                        // [epw][A] heights
@@ -20,7 +23,16 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
     constexpr int GW = VEC ? 4 : 1;          // cells handled per lane per access
 
     // ---- phase 1: stage this wave's heightmaps into LDS as bytes -------------------------------
-    if (MODE == kStep) {
+    if (MODE == kStep && SUB) {                // a gather: row by row from the slots' bins
+        for (int c = lane; c < ncell / GW; c += kWave) {
+            const int el = p.divA4.div(c);      // (A/4 quads or A cells per bin)
+            const int k = c - el * (A / GW);
+            int b;
+            const bool ok = sub_id(p, e0 + el, b);
+            if (VEC) ((uint32_t *)hm)[c] = ok ? ((const uint32_t *)p.hmap)[(size_t)b * (A / 4) + k] : 0u;
+            else hm[c] = ok ? p.hmap[(size_t)b * A + k] : 0;
+        }
+    } else if (MODE == kStep) {
         const uint8_t *gh = p.hmap + (size_t)e0 * A;
         if (VEC) {
             for (int q = lane; q < ncell / 4; q += kWave) ((uint32_t *)hm)[q] = ((const uint32_t *)gh)[q];
@@ -60,14 +72,17 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
     bool fin = false;
     double fin_ret = 0.0, fin_ratio = 0.0;
     int fin_len = 0;
+    int b = e0 + lane;                       // the lane's bin (SUB: of slot e0 + lane)
     if (lane < nenv) {
         const int e = e0 + lane;
         BinRec r;
         r.place = 0;
         r.flags = 0;
         r.any = 0;
-        if (MODE == kStep) {
-            bpp_env_state st = p.state[e];
+        if (SUB && !sub_id(p, e, b)) {
+            sub_noop(p, e, r);
+        } else if (MODE == kStep) {
+            bpp_env_state st = p.state[b];
             const int64_t act = p.actions[e];
             // BoxCreator.preview(1)[0] (binCreator.py:15-18): the current item, the one after it and the
             // first item of the next episode are cached in the state record; the entries the NEXT step
@@ -104,8 +119,8 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
             } else if (!pl.noop) {
                 r.flags = 2u;
             }
-            p.state[e] = st;
-            if (p.cache != nullptr) row_cache_drop(p, e);
+            p.state[b] = st;
+            if (p.cache != nullptr) row_cache_drop(p, b);
         } else if (MODE == kResetInit || MODE == kResetAdvance) {
             const bpp_env_state st = reset_state<MODE>(p, e);
             p.state[e] = st;
@@ -122,7 +137,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
         }
         rec[lane] = r;
     }
-    if (MODE == kStep && p.ep_acc && fin) episode_acc_add(p.ep_acc, e0 + lane, fin_ret, fin_ratio, fin_len);
+    if (MODE == kStep && p.ep_acc && fin) episode_acc_add(p.ep_acc, b, fin_ret, fin_ratio, fin_len);
     wave_sync();
 
     if (MODE == kStep || MODE == kResetInit || MODE == kResetAdvance) {
@@ -161,13 +176,17 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void bpp_kernel(const Param
                 const uint32_t k = g - pl * per_plane;
                 const uint32_t el = pl >> 2, plane = pl & 3u;
                 if (plane == 0) {
+                    int sb = 0;                                      // SUB: the slot's bin, the map goes back there
+                    const bool keep = SUB && sub_id(p, e0 + el, sb);
                     if (VEC) {
                         const uint32_t v = ((uint32_t *)hm)[el * per_plane + k];
-                        ((uint32_t *)gh)[el * per_plane + k] = v;
+                        if (!SUB) ((uint32_t *)gh)[el * per_plane + k] = v;
+                        else if (keep) ((uint32_t *)(p.hmap + (size_t)sb * A))[k] = v;
                         ((float4 *)go)[g] = quad_floats(v);
                     } else {
                         const int v = hm[el * A + k];
-                        gh[el * A + k] = (uint8_t)v;
+                        if (!SUB) gh[el * A + k] = (uint8_t)v;
+                        else if (keep) p.hmap[(size_t)sb * A + k] = (uint8_t)v;
                         go[g] = (float)v;
                     }
                 } else {
@@ -464,8 +483,11 @@ __device__ __forceinline__ OriRec make_ori(int W, int L, int x, int y, int z, in
 }
 
 // Sizes come from the launch parameters, divisions by them from their precomputed magic numbers (Params::div*).
-template <int K, bool ROT, int MODE>
+// SUB (bpp_step_subset, kStep only): the launch covers p.nsub slots, slot i steps bin p.ids[i] and writes output row i; a slot
+// whose id lies outside [0, E) touches no bin and emits the no-op of an empty bin (sub_id).
+template <int K, bool ROT, int MODE, bool SUB = false>
 __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel(const Params p) {
+    static_assert(!SUB || MODE == kStep, "a subset launch steps");
     const int W = p.W, L = p.L;
     const int A = W * L, A4 = A / 4, M = ROT ? 2 * A : A, M4 = M / 4, PW = L + 1, PN = (W + 1) * (L + 1);
     auto div_a4 = [&](int n) { return (int)p.divA4.div((uint32_t)n); };
@@ -479,7 +501,8 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
     const int wpb = blockDim.x >> 6;
     const int blk_e0 = xcd_block(p.xcd_remap) * wpb * p.epw;       // first bin of this workgroup
     const int e0 = blk_e0 + wid * p.epw;                           // first bin of this wave
-    const int nenv = max(0, min(p.epw, p.E - e0));                 // block barriers below: no early return
+    const int NB = SUB ? p.nsub : p.E;                             // bins (slots) of the launch
+    const int nenv = max(0, min(p.epw, NB - e0));                  // block barriers below: no early return
     unsigned char *wb = smem + wid * p.lds_per_wave;
     uint8_t *hm = wb;
     uint32_t *hm32 = (uint32_t *)wb;
@@ -491,17 +514,25 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
 
     if (BPP_ABL(p, 16)) return;
     // The deciding wave (wave 0) issues its per-bin loads first, so their latency overlaps the staging.
-    const int dec_nb = max(0, min(wpb * p.epw, p.E - blk_e0));
+    const int dec_nb = max(0, min(wpb * p.epw, NB - blk_e0));
     const int dec_e = blk_e0 + (lane < dec_nb ? lane : 0);
+    int dec_b = dec_e;                                             // the bin of slot dec_e
+    const bool dec_ok = !SUB || wid != 0 || sub_id(p, dec_e, dec_b);
     bpp_env_state st0;
     int64_t act0 = 0;
     if (MODE == kStep && wid == 0 && !BPP_ABL(p, 32)) {
-        st0 = p.state[dec_e];
+        st0 = p.state[dec_b];
         act0 = p.actions[dec_e];
     }
 
     // ---- phase 1: stage heightmaps as bytes ------------------------------------------------------
-    if (MODE == kStep) {
+    if (MODE == kStep && SUB) {                                    // a gather: row by row from the slots' bins
+        for (int q = lane; q < nenv * A4; q += kWave) {
+            const int el = div_a4(q);
+            int b;
+            hm32[q] = sub_id(p, e0 + el, b) ? ((const uint32_t *)p.hmap)[(size_t)b * A4 + (q - el * A4)] : 0u;
+        }
+    } else if (MODE == kStep) {
         const uint32_t *gh = (const uint32_t *)(p.hmap + (size_t)e0 * A);
         for (int q = lane; q < (BPP_ABL(p, 64) ? 0 : nenv * A4); q += kWave) hm32[q] = gh[q];
     } else if (MODE == kMaskHmap) {
@@ -526,7 +557,8 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
     double fin_ret = 0.0, fin_ratio = 0.0;
     int fin_len = 0;
     if (wid == 0 && !BPP_ABL(p, 32)) {
-        const bool active = lane < dec_nb;
+        const bool active = lane < dec_nb && dec_ok;
+        const bool bad = SUB && lane < dec_nb && !dec_ok;
         const int e = dec_e;
         const int ow = lane >> p.epw_shift, oel = lane & (p.epw - 1);  // owning wave, bin within it
         unsigned char *ob = smem + ow * p.lds_per_wave;
@@ -599,8 +631,9 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             } else if (!pl.noop) {
                 r.flags = 2u;
             }
-            if (active) p.state[e] = st;
-            if (active && p.cache != nullptr) row_cache_drop(p, e);
+            if (active) p.state[dec_b] = st;
+            if (active && p.cache != nullptr) row_cache_drop(p, dec_b);
+            if (bad) sub_noop(p, e, r);
         } else if (MODE == kResetInit || MODE == kResetAdvance) {
             const bpp_env_state st = reset_state<MODE>(p, e);
             if (active) p.state[e] = st;
@@ -614,7 +647,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
             const int32_t *it = p.items_in + (size_t)e * 3;
             r.item = pack_item(it[0], it[1], it[2]);
         }
-        if (active) {
+        if (active || bad) {
             ((BinRec *)(ob + p.off_rec))[oel] = r;
             OriRec *oo = (OriRec *)(ob + p.off_ori) + oel * 2;
             const int nx = r.item & 255u, ny = (r.item >> 8) & 255u, nz = (r.item >> 16) & 255u;
@@ -625,7 +658,7 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
     __syncthreads();
     // episode statistics (main.py:159-162): off the other waves' critical path, after the barrier
     if (MODE == kStep && wid == 0 && p.ep_acc && fin && !BPP_ABL(p, 128))
-        episode_acc_add(p.ep_acc, dec_e, fin_ret, fin_ratio, fin_len);
+        episode_acc_add(p.ep_acc, dec_b, fin_ret, fin_ratio, fin_len);
 
     if (MODE == kStep) {
         // ---- phase 2b: every wave applies its bins' placements (space.py:36-46: window := max_h + z),
@@ -651,7 +684,9 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
         for (int q = lane; q < nenv * A4; q += kWave) {
             const int el = div_a4(q);
             const uint32_t v = hm32[q];
-            gh[q] = v;
+            int b;
+            if (!SUB) gh[q] = v;
+            else if (sub_id(p, e0 + el, b)) ((uint32_t *)p.hmap)[(size_t)b * A4 + (q - el * A4)] = v;
             go[q + el * (3 * A4)] = quad_floats(v);
         }
         // planes x, y, z are constants per bin (bin3D.py:49-53): bin-uniform passes, the value comes from a
@@ -820,8 +855,10 @@ __global__ __launch_bounds__(kWave * kMaxFastWavesPerBlock) void bpp_fast_kernel
         }
         const int total = __shfl(incl, lane | (G - 1), kWave);
         const int e = e0 + el;
-        int rem = (int)__umulhi(mix32(mix32_base(p.sample_seed, p.sample_step), (uint32_t)(p.env_id_base + e)), (uint32_t)total) -
+        const int64_t gbin = SUB ? (act ? p.ids[e] : 0) : e;        // the hash takes the bin's global id
+        int rem = (int)__umulhi(mix32(mix32_base(p.sample_seed, p.sample_step), (uint32_t)(p.env_id_base + gbin)), (uint32_t)total) -
                   (incl - cnt);
+        if (SUB && act && total == 0 && sl == 0) p.next_action[e] = 0;   // a bad slot's zero mask (bpp_sample_feasible's answer)
         if (act && total > 0 && rem >= 0 && rem < cnt) {
             int found = 0;
             for (int k = 0; k < per; ++k) {
