@@ -16,7 +16,8 @@ BUILD_LIB = os.path.join(CSRC, "libbpp_hip.so")
 LIB = os.environ.get("BPP_HIP_LIB") or BUILD_LIB
 HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_abi.h")
 BRANCH_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_branch.h")
-DEPS = [SRC, HDR, BRANCH_HDR, os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+REORDER_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_reorder.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -31,6 +32,10 @@ SYMBOLS = ["bpp_abi_version", "bpp_last_error", "bpp_limits", "bpp_reset", "bpp_
            "bpp_rollout_uniform_stream", "bpp_masked_evaluate", "bpp_masked_evaluate_backward", "bpp_episode_acc_reduce", "bpp_rollout_uniform_sets", "bpp_fetch_to_host", "bpp_wait", "bpp_gather_finished", "bpp_epsilon_override", "bpp_side_create", "bpp_side_destroy", "bpp_mark", "bpp_wait_mark", "bpp_step_dropin", "bpp_masked_act_counter"]
 # include/bpp_branch.h: exported by libbpp_hip.so only (not part of bpp_abi.h, which the oracle library implements too)
 BRANCH_SYMBOLS = ["bpp_step_subset", "bpp_copy_bins"]
+# include/bpp_reorder.h: the same, for the BPP-k reorder search
+REORDER_SYMBOLS = ["bpp_reorder_sizes", "bpp_reorder_begin", "bpp_reorder_emit", "bpp_reorder_choose", "bpp_reorder_commit",
+                   "bpp_reorder_finish"]
+REORDER_MAX_K = 8
 
 
 class Batch(ctypes.Structure):
@@ -92,6 +97,29 @@ def hipcc():
         if c and (os.path.isabs(c) and os.path.exists(c) or not os.path.isabs(c)):
             return c
     return "hipcc"
+
+
+class Reorder(ctypes.Structure):
+    """struct bpp_reorder"""
+    _fields_ = [("n", ctypes.c_int32), ("k", ctypes.c_int32), ("times", ctypes.c_int32), ("max_nodes", ctypes.c_int32),
+                ("v_bound", ctypes.c_double), ("ids", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("work", ctypes.c_void_p),
+                ("overflow", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
+
+
+def bind_reorder(L, batch=None):
+    """Argument types of the REORDER_SYMBOLS on library handle L (`batch`: the ctypes class of struct bpp_batch)."""
+    B = ctypes.POINTER(batch or Batch)
+    R = ctypes.POINTER(Reorder)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_reorder_sizes.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_int64)]
+    L.bpp_reorder_begin.argtypes = [B, R, vp]
+    L.bpp_reorder_emit.argtypes = [B, R, i32, i32, vp, vp, vp]
+    L.bpp_reorder_choose.argtypes = [B, R, vp, vp, vp, vp, vp]
+    L.bpp_reorder_commit.argtypes = [B, R, vp, vp]
+    L.bpp_reorder_finish.argtypes = [B, R, vp, vp, vp, vp]
+    for name in REORDER_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
 
 
 def build(force=False, verbose=False):
@@ -187,6 +215,7 @@ def lib():
         L.bpp_copy_bins.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Stream), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                     ctypes.c_void_p]
         L.bpp_copy_bins.restype = ctypes.c_int
+        bind_reorder(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

@@ -32,6 +32,7 @@
 
 #include "../../include/bpp_abi.h"
 #include "../../include/bpp_branch.h"
+#include "../../include/bpp_reorder.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1770,3 +1771,5 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 }
 
 }  // extern "C"
+
+#include "bpp_reorder.inl"
