@@ -17,7 +17,8 @@ LIB = os.environ.get("BPP_HIP_LIB") or BUILD_LIB
 HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_abi.h")
 BRANCH_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_branch.h")
 REORDER_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_reorder.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+MULTIBIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_multibin.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -36,6 +37,9 @@ BRANCH_SYMBOLS = ["bpp_step_subset", "bpp_copy_bins"]
 REORDER_SYMBOLS = ["bpp_reorder_sizes", "bpp_reorder_begin", "bpp_reorder_emit", "bpp_reorder_choose", "bpp_reorder_commit",
                    "bpp_reorder_finish"]
 REORDER_MAX_K = 8
+# include/bpp_multibin.h: the same, for multi-bin packing
+MULTIBIN_SYMBOLS = ["bpp_multibin_sizes", "bpp_multibin_emit", "bpp_multibin_choose", "bpp_multibin_commit", "bpp_multibin_clear"]
+MULTIBIN_MAX_K = 256
 
 
 class Batch(ctypes.Structure):
@@ -118,6 +122,27 @@ def bind_reorder(L, batch=None):
     L.bpp_reorder_commit.argtypes = [B, R, vp, vp]
     L.bpp_reorder_finish.argtypes = [B, R, vp, vp, vp, vp]
     for name in REORDER_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
+class MultiBin(ctypes.Structure):
+    """struct bpp_multibin"""
+    _fields_ = [("n", ctypes.c_int32), ("w", ctypes.c_int32), ("s", ctypes.c_int32), ("K", ctypes.c_int32), ("ids", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("work", ctypes.c_void_p)]
+
+
+def bind_multibin(L, batch=None):
+    """Argument types of the MULTIBIN_SYMBOLS on library handle L (`batch`: the ctypes class of struct bpp_batch)."""
+    B = ctypes.POINTER(batch or Batch)
+    M = ctypes.POINTER(MultiBin)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_multibin_sizes.argtypes = [i32] * 6 + [ctypes.POINTER(ctypes.c_int64)]
+    L.bpp_multibin_emit.argtypes = [B, M, vp, vp]
+    L.bpp_multibin_choose.argtypes = [B, M, vp, vp, vp, vp, vp, vp]
+    L.bpp_multibin_commit.argtypes = [B, M, vp, vp]
+    L.bpp_multibin_clear.argtypes = [B, M, vp, i32, vp]
+    for name in MULTIBIN_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     return L
 
@@ -216,6 +241,7 @@ def lib():
                                     ctypes.c_void_p]
         L.bpp_copy_bins.restype = ctypes.c_int
         bind_reorder(L)
+        bind_multibin(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

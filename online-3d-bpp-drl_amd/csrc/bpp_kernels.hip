@@ -33,6 +33,7 @@
 #include "../../include/bpp_abi.h"
 #include "../../include/bpp_branch.h"
 #include "../../include/bpp_reorder.h"
+#include "../../include/bpp_multibin.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1773,3 +1774,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 }  // extern "C"
 
 #include "bpp_reorder.inl"
+#include "bpp_multibin.inl"
