@@ -18,7 +18,8 @@ HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_abi.h")
 BRANCH_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_branch.h")
 REORDER_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_reorder.h")
 MULTIBIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_multibin.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -40,6 +41,10 @@ REORDER_MAX_K = 8
 # include/bpp_multibin.h: the same, for multi-bin packing
 MULTIBIN_SYMBOLS = ["bpp_multibin_sizes", "bpp_multibin_emit", "bpp_multibin_choose", "bpp_multibin_commit", "bpp_multibin_clear"]
 MULTIBIN_MAX_K = 256
+# include/bpp_mcts.h: the same, for the batched MCTS
+MCTS_SYMBOLS = ["bpp_mcts_sizes", "bpp_mcts_seed", "bpp_mcts_clear", "bpp_mcts_begin", "bpp_mcts_select", "bpp_mcts_emit",
+                "bpp_mcts_expand", "bpp_mcts_rollout", "bpp_mcts_backup", "bpp_mcts_finish", "bpp_mcts_advance"]
+MCTS_MAX_K = 16
 
 
 class Batch(ctypes.Structure):
@@ -147,6 +152,35 @@ def bind_multibin(L, batch=None):
     return L
 
 
+class Mcts(ctypes.Structure):
+    """struct bpp_mcts"""
+    _fields_ = [("n", ctypes.c_int32), ("k", ctypes.c_int32), ("sim_times", ctypes.c_int32), ("max_depth", ctypes.c_int32),
+                ("rollout_length", ctypes.c_int32), ("cap", ctypes.c_int32), ("credit", ctypes.c_double), ("zeta", ctypes.c_double),
+                ("ids", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("state", ctypes.c_void_p), ("overflow", ctypes.c_void_p),
+                ("reserved", ctypes.c_int32)]
+
+
+def bind_mcts(L, batch=None):
+    """Argument types of the MCTS_SYMBOLS on library handle L (`batch`: the ctypes class of struct bpp_batch)."""
+    B = ctypes.POINTER(batch or Batch)
+    M = ctypes.POINTER(Mcts)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_mcts_sizes.argtypes = [i32] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+    L.bpp_mcts_seed.argtypes = [B, M, vp, vp, i32, vp]
+    L.bpp_mcts_clear.argtypes = [B, M, vp, i32, vp]
+    L.bpp_mcts_begin.argtypes = [B, M, vp]
+    L.bpp_mcts_select.argtypes = [B, M, i32, vp, vp, vp]
+    L.bpp_mcts_emit.argtypes = [B, M, i32, vp, vp, vp]
+    L.bpp_mcts_expand.argtypes = [B, M, vp, vp, vp, vp]
+    L.bpp_mcts_rollout.argtypes = [B, M, vp, vp, vp, vp]
+    L.bpp_mcts_backup.argtypes = [B, M, vp, vp]
+    L.bpp_mcts_finish.argtypes = [B, M, vp, vp, vp]
+    L.bpp_mcts_advance.argtypes = [B, M, vp, vp]
+    for name in MCTS_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
 def build(force=False, verbose=False):
     """Compile csrc/bpp_kernels.hip for gfx950 into csrc/libbpp_hip.so (in-tree; no-op when fresh)."""
     if LIB != BUILD_LIB:        # an explicitly chosen build is loaded as it is
@@ -242,6 +276,7 @@ def lib():
         L.bpp_copy_bins.restype = ctypes.c_int
         bind_reorder(L)
         bind_multibin(L)
+        bind_mcts(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L
