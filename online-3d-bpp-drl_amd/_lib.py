@@ -19,7 +19,8 @@ BRANCH_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_branch.h")
 REORDER_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_reorder.h")
 MULTIBIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_multibin.h")
 MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -45,6 +46,9 @@ MULTIBIN_MAX_K = 256
 MCTS_SYMBOLS = ["bpp_mcts_sizes", "bpp_mcts_seed", "bpp_mcts_clear", "bpp_mcts_begin", "bpp_mcts_select", "bpp_mcts_emit",
                 "bpp_mcts_expand", "bpp_mcts_rollout", "bpp_mcts_backup", "bpp_mcts_finish", "bpp_mcts_advance"]
 MCTS_MAX_K = 16
+# include/bpp_pipeline.h: the same, for the pipelined rollout driver
+PIPELINE_SYMBOLS = ["bpp_pipeline_create", "bpp_pipeline_destroy", "bpp_pipeline_plan", "bpp_rollout_uniform_sets_pipelined"]
+PIPELINE_MAX_GROUPS, PIPELINE_ALIGN, PIPELINE_MIN_GROUP = 4, 64, 8192
 
 
 class Batch(ctypes.Structure):
@@ -274,6 +278,11 @@ def lib():
         L.bpp_copy_bins.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Stream), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                     ctypes.c_void_p]
         L.bpp_copy_bins.restype = ctypes.c_int
+        L.bpp_pipeline_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]
+        L.bpp_pipeline_destroy.argtypes = [ctypes.c_void_p]
+        L.bpp_pipeline_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        L.bpp_rollout_uniform_sets_pipelined.argtypes = L.bpp_rollout_uniform_sets.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int32,
+                                                                                                    ctypes.c_void_p]
         bind_reorder(L)
         bind_multibin(L)
         bind_mcts(L)
@@ -321,6 +330,15 @@ def launch_info(E, size, rotation=False):
     check(lib().bpp_launch_info(int(E), int(size[0]), int(size[1]), int(size[2]), int(bool(rotation)), out))
     return {"kernel": int(out[0]), "kernel_name": KERNEL_NAMES.get(int(out[0]), "?"), "K": int(out[1]), "bins_per_wave": int(out[2]),
             "waves_per_group": int(out[3]), "workgroups": int(out[4]), "lds_bytes": int(out[5])}
+
+
+def pipeline_plan(E, groups):
+    """bpp_pipeline_plan: the [(first bin, bins)] ranges the pipelined rollout driver splits E bins into (pure host function)."""
+    first, count = (ctypes.c_int32 * PIPELINE_MAX_GROUPS)(), (ctypes.c_int32 * PIPELINE_MAX_GROUPS)()
+    n = lib().bpp_pipeline_plan(int(E), int(groups), first, count)
+    if n < 0:
+        check(n)
+    return [(int(first[g]), int(count[g])) for g in range(n)]
 
 
 def limits():

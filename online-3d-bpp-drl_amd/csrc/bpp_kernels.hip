@@ -35,6 +35,7 @@
 #include "../../include/bpp_reorder.h"
 #include "../../include/bpp_multibin.h"
 #include "../../include/bpp_mcts.h"
+#include "../../include/bpp_pipeline.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1468,6 +1469,187 @@ int bpp_rollout_uniform_sets(const bpp_batch *b, const bpp_step_out *outs, int32
         o.sample_step = step0 + (uint64_t)t + 1;
         rc = bpp_step(b, actions, &o, stream);
         if (rc == 0 && eps) rc = bpp_epsilon_override(actions, b->num_envs, M, b->env_id_base, seed, step0 + (uint64_t)t + 1, eps, stream);
+    }
+    return rc;
+}
+
+}  // extern "C"
+
+namespace {
+// bpp_pipeline (include/bpp_pipeline.h): the side streams and the fork / join events of the pipelined rollout driver, created and
+// owned by the CALLER like bpp_side -- no per-device state in the library.
+struct Pipeline {
+    int device, max_groups;
+    hipStream_t streams[BPP_PIPELINE_MAX_GROUPS - 1];
+    hipEvent_t fork, join[BPP_PIPELINE_MAX_GROUPS - 1];
+};
+
+template <typename T>
+T *rows_from(T *p, int32_t first, size_t row) {   // NULL stays NULL
+    return p ? p + (size_t)first * row : nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int bpp_pipeline_plan(int32_t E, int32_t groups, int32_t *first, int32_t *count) {
+    if (!first || !count) return fail(BPP_E_BADARG, "bpp_pipeline_plan: NULL pointer");
+    if (E <= 0 || groups < 1 || groups > BPP_PIPELINE_MAX_GROUPS)
+        return fail(BPP_E_BADARG, "bpp_pipeline_plan: need E > 0 and 1 <= groups <= BPP_PIPELINE_MAX_GROUPS");
+    int n = groups;
+    if (n > E / BPP_PIPELINE_MIN_GROUP) n = E / BPP_PIPELINE_MIN_GROUP;
+    if (n < 1) n = 1;
+    // every group but the last holds E / n bins rounded UP to the alignment; the last one takes the remainder, the smallest share --
+    // where rounding up leaves it below the minimum, one group fewer is made
+    for (;; --n) {
+        const int64_t per = (((int64_t)E + n - 1) / n + BPP_PIPELINE_ALIGN - 1) / BPP_PIPELINE_ALIGN * BPP_PIPELINE_ALIGN;
+        const int64_t last = (int64_t)E - per * (n - 1);
+        if (n > 1 && last < BPP_PIPELINE_MIN_GROUP) continue;
+        for (int g = 0; g < n; ++g) {
+            first[g] = (int32_t)(per * g);
+            count[g] = (int32_t)(g + 1 < n ? per : last);
+        }
+        return n;
+    }
+}
+
+int bpp_pipeline_create(void **pipe, int32_t max_groups) {
+    if (!pipe) return fail(BPP_E_BADARG, "bpp_pipeline_create: NULL pointer");
+    *pipe = nullptr;
+    if (max_groups < 1 || max_groups > BPP_PIPELINE_MAX_GROUPS)
+        return fail(BPP_E_BADARG, "bpp_pipeline_create: need 1 <= max_groups <= BPP_PIPELINE_MAX_GROUPS");
+    Pipeline *pl = new Pipeline();
+    pl->max_groups = max_groups;
+    if (hipGetDevice(&pl->device) != hipSuccess) {
+        delete pl;
+        return fail(BPP_E_BADARG, "bpp_pipeline_create: no current device");
+    }
+    const int ns = max_groups - 1;
+    hipError_t e = hipEventCreateWithFlags(&pl->fork, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        delete pl;
+        return hip_fail(e, "hipEventCreateWithFlags");
+    }
+    for (int k = 0; k < ns; ++k) {
+        const char *what = "hipStreamCreateWithPriority";
+        e = hipStreamCreateWithPriority(&pl->streams[k], hipStreamNonBlocking, 0);      // 0: the default priority
+        if (e == hipSuccess) {
+            what = "hipEventCreateWithFlags";
+            e = hipEventCreateWithFlags(&pl->join[k], hipEventDisableTiming);
+            if (e != hipSuccess) (void)hipStreamDestroy(pl->streams[k]);
+        }
+        if (e != hipSuccess) {
+            for (int j = 0; j < k; ++j) {
+                (void)hipEventDestroy(pl->join[j]);
+                (void)hipStreamDestroy(pl->streams[j]);
+            }
+            (void)hipEventDestroy(pl->fork);
+            delete pl;
+            return hip_fail(e, what);
+        }
+    }
+    *pipe = pl;
+    return 0;
+}
+
+int bpp_pipeline_destroy(void *pipe) {
+    if (!pipe) return 0;
+    Pipeline *pl = (Pipeline *)pipe;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < pl->max_groups - 1; ++k) {
+        (void)hipStreamSynchronize(pl->streams[k]);
+        (void)hipEventDestroy(pl->join[k]);
+        const hipError_t ek = hipStreamDestroy(pl->streams[k]);
+        if (e == hipSuccess) e = ek;
+    }
+    (void)hipEventDestroy(pl->fork);
+    delete pl;
+    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamDestroy");
+}
+
+int bpp_rollout_uniform_sets_pipelined(const bpp_batch *b, const bpp_step_out *outs, int32_t nsets, const float *first_mask,
+                                       int64_t *actions, uint64_t seed, uint64_t step0, int32_t nsteps, int32_t flags,
+                                       void *pipe, int32_t groups, void *stream) {
+    if (!b || !outs || !actions || nsets < 1) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: NULL pointer / no output set");
+    if (nsteps < 0) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: negative nsteps");
+    if (groups < 1 || groups > BPP_PIPELINE_MAX_GROUPS)
+        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: need 1 <= groups <= BPP_PIPELINE_MAX_GROUPS");
+    if (b->pool_mode != BPP_POOL_STATIC || b->seq_cache)
+        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: static pools only (ring rows and the row cache are indexed by local bin)");
+    for (int k = 0; k < nsets; ++k) {
+        if (!outs[k].mask) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: every output set needs a mask");
+        if (outs[k].host_reward || outs[k].host_done)
+            return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: output sets with host_reward / host_done are not split");
+    }
+    if (!(flags & BPP_ROLLOUT_CONTINUE) && !first_mask)
+        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: first_mask needed without BPP_ROLLOUT_CONTINUE");
+    int32_t first[BPP_PIPELINE_MAX_GROUPS], count[BPP_PIPELINE_MAX_GROUPS];
+    const int G = bpp_pipeline_plan(b->num_envs, groups, first, count);
+    if (G < 0) return G;
+    if (G == 1) return bpp_rollout_uniform_sets(b, outs, nsets, first_mask, actions, seed, step0, nsteps, flags, stream);
+    Pipeline *pl = (Pipeline *)pipe;
+    if (!pl) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: more than one group needs a pipe (bpp_pipeline_create)");
+    if (G > pl->max_groups) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: more groups than the pipe was created for");
+    if (nsteps == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != pl->device)
+        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: the pipe belongs to another device than the current one");
+
+    const size_t A = (size_t)b->W * b->L, M = A * (1 + b->rotation);
+    const uint32_t eps = BPP_ROLLOUT_EPS_OF(flags);
+    bpp_batch sub[BPP_PIPELINE_MAX_GROUPS];
+    void *st[BPP_PIPELINE_MAX_GROUPS];
+    std::vector<bpp_step_out> so((size_t)G * nsets);      // [g][k]: output set k seen from group g's first bin
+    for (int g = 0; g < G; ++g) {
+        const int32_t f = first[g];
+        sub[g] = *b;
+        sub[g].num_envs = count[g];
+        sub[g].env_id_base = b->env_id_base + f;
+        sub[g].hmap = rows_from(b->hmap, f, A);
+        sub[g].state = rows_from(b->state, f, 1);
+        sub[g].ep_acc = rows_from(b->ep_acc, f, 4);
+        st[g] = g == 0 ? stream : (void *)pl->streams[g - 1];
+        for (int k = 0; k < nsets; ++k) {
+            bpp_step_out &o = so[(size_t)g * nsets + k];
+            o = outs[k];
+            o.obs = rows_from(o.obs, f, 4 * A);
+            o.mask = rows_from(o.mask, f, M);
+            o.reward = rows_from(o.reward, f, 1);
+            o.done = rows_from(o.done, f, 1);
+            o.counter = rows_from(o.counter, f, 1);
+            o.ratio = rows_from(o.ratio, f, 1);
+            o.ep_ret = rows_from(o.ep_ret, f, 1);
+            o.ep_len = rows_from(o.ep_len, f, 1);
+            o.next_action = actions + f;       // every lock-step draws the next one's actions, the last one included
+            o.sample_seed = seed;
+        }
+    }
+    hipError_t e = hipEventRecord(pl->fork, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
+    for (int g = 1; g < G; ++g) {
+        e = hipStreamWaitEvent(pl->streams[g - 1], pl->fork, 0);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");     // nothing is enqueued on a side stream yet
+    }
+    int rc = 0;
+    if (!(flags & BPP_ROLLOUT_CONTINUE))
+        for (int g = 0; rc == 0 && g < G; ++g) {
+            rc = bpp_sample_feasible(first_mask + (size_t)first[g] * M, actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0, st[g]);
+            if (rc == 0 && eps) rc = bpp_epsilon_override(actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0, eps, st[g]);
+        }
+    // interleaved: lock-step t of every group, then t + 1 -- all G queues hold work from the first launch on
+    for (int t = 0; rc == 0 && t < nsteps; ++t)
+        for (int g = 0; rc == 0 && g < G; ++g) {
+            bpp_step_out &o = so[(size_t)g * nsets + t % nsets];
+            o.sample_step = step0 + (uint64_t)t + 1;
+            rc = bpp_step(&sub[g], actions + first[g], &o, st[g]);
+            if (rc == 0 && eps)
+                rc = bpp_epsilon_override(actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0 + (uint64_t)t + 1, eps, st[g]);
+        }
+    // join, also behind a failed enqueue: whatever did reach a side stream stays ordered in front of the caller's next work
+    for (int g = 1; g < G; ++g) {
+        e = hipEventRecord(pl->join[g - 1], pl->streams[g - 1]);
+        if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, pl->join[g - 1], 0);
+        if (e != hipSuccess && rc == 0) rc = hip_fail(e, "hipEventRecord / hipStreamWaitEvent");
     }
     return rc;
 }

@@ -10,6 +10,7 @@ baselines/bench/monitor.py:64-75).  All bins live on ONE GPU and are stepped by 
 Tensor-native fast path (no host sync, everything stays on the device): `step_tensors(actions)`.
 """
 import ctypes
+import os
 import time
 
 import numpy as np
@@ -25,6 +26,17 @@ STATE_FORMAT = 1      # state_dict()["format"]: 1 = 48-byte records whose last w
 STREAM_LAYOUT = 2     # state_dict()["stream_layout"]: layout of the ring rows and generator records of a streaming env.
 #                       2 = ring rows start with two look-ahead entries, item i at entry 2 + i; byte-output MT19937 records /
 #                       16-byte counter records (ABI v12+).  A checkpoint without the key (layout 1 or older) is refused.
+# rollout_uniform_sets: chains of step-kernel launches the bins are split over (include/bpp_pipeline.h), where nothing is asked for.
+# Measured (profiles/pipelined_rollout_ab.json, pipelined_rollout_groups.json): two chains win on every workload,
+# three and four lose to two.  The default is two for the 10x10 bins from 32 768 bins up and one for everything else: smaller
+# batches and other footprints were not measured often enough, and the 20x20x20 workload, 22 % faster with two chains, then
+# moves its contract bytes faster than the 8 TB/s HBM peak bench.py's roofline block divides by (L3-served reads), which that
+# block's consumers take for a measurement error -- rollout_groups=2 is there for whoever wants it.
+def default_rollout_groups(E, W, L):
+    return 2 if (W, L) == (10, 10) and E >= 32768 else 1
+
+
+_ENV_ROLLOUT_GROUPS = int(os.environ.get("BPP_ROLLOUT_GROUPS") or 0)     # read once; 0 = not set
 
 
 class StepTensors(object):
@@ -293,6 +305,10 @@ class BppVecEnv(object):
     mask_rule:      'utils' (acktr/utils.py check_box -- what the training loop consumes) or 'space'
                     (Space.check_box, i.e. PackingGame.get_possible_position).
     compute_mask:   also produce the feasibility mask of every returned observation (`location_masks`).
+    rollout_groups: chains rollout_uniform_sets splits the bins over (include/bpp_pipeline.h: each group's launches on a stream of
+                    its own, results bit-identical for any value); None = the measured default (default_rollout_groups; a batch
+                    too small to split runs as one chain whatever is asked); the environment variable BPP_ROLLOUT_GROUPS, read
+                    once per process, overrides both (1 = the single-stream driver).
     eager_infos:    step() also enqueues the compaction of the finished bins' infos behind the step kernel (one more launch,
                     ~10 us of device time at 65 536 bins), so that reading `infos.episodes()` / a finished bin's dict costs no
                     launch and no second synchronisation -- for loops that look at the finished episodes EVERY step, as
@@ -314,7 +330,8 @@ class BppVecEnv(object):
     """
 
     def __init__(self, num_envs, container_size=(10, 10, 10), enable_rotation=False, pool=None, device="cuda",
-                 env_id_base=0, env_id_total=None, mask_rule="utils", compute_mask=True, fresh_outputs=False, stream=None, eager_infos=False):
+                 env_id_base=0, env_id_total=None, mask_rule="utils", compute_mask=True, fresh_outputs=False, stream=None, eager_infos=False,
+                 rollout_groups=None):
         if not torch.cuda.is_available():
             raise RuntimeError("BppVecEnv needs a HIP device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -420,6 +437,11 @@ class BppVecEnv(object):
         self._tstart = time.time()
         self.monitor = None        # MonitorCsv (make_vec_envs with a log_dir): step_wait() appends the finished episodes' rows
         self._side = None          # bpp_side (rollout_uniform in streaming mode): created on first use
+        groups = _ENV_ROLLOUT_GROUPS or rollout_groups or default_rollout_groups(self.E, self.W, self.L)
+        if not 1 <= int(groups) <= _lib.PIPELINE_MAX_GROUPS:
+            raise ValueError("rollout_groups must be in 1 .. %d" % _lib.PIPELINE_MAX_GROUPS)
+        self.rollout_groups = len(_lib.pipeline_plan(self.E, int(groups)))   # chains rollout_uniform_sets really runs
+        self._pipe = None          # bpp_pipeline (rollout_uniform_sets with rollout_groups > 1): created on first use
         self.closed = False
         from . import masks as _masks
         _masks.register_env(self)      # the per-row mask helpers may hand back this env's own mask rows (masks.ROW_CACHE)
@@ -738,10 +760,18 @@ class BppVecEnv(object):
         first = self.location_masks
         self._on_device()
         self._serial += int(nsteps)
-        _lib.check(self.lib.bpp_rollout_uniform_sets(self._batch_ref, outs, n, first.data_ptr() if first is not None else None,
-                                                     actions.data_ptr(), int(seed), int(step0), int(nsteps),
-                                                     (_lib.ROLLOUT_CONTINUE if resume else 0) | (_lib.rollout_eps_flags(eps) if eps else 0),
-                                                     self._stream_ptr()))
+        flags = (_lib.ROLLOUT_CONTINUE if resume else 0) | (_lib.rollout_eps_flags(eps) if eps else 0)
+        if self.rollout_groups > 1:
+            if self._pipe is None:      # the groups' streams + fork / join events: this env's own (bpp_pipeline_create), released in close()
+                self._pipe = ctypes.c_void_p()
+                _lib.check(self.lib.bpp_pipeline_create(ctypes.byref(self._pipe), self.rollout_groups))
+            _lib.check(self.lib.bpp_rollout_uniform_sets_pipelined(self._batch_ref, outs, n, first.data_ptr() if first is not None else None,
+                                                                   actions.data_ptr(), int(seed), int(step0), int(nsteps), flags,
+                                                                   self._pipe, self.rollout_groups, self._stream_ptr()))
+        else:
+            _lib.check(self.lib.bpp_rollout_uniform_sets(self._batch_ref, outs, n, first.data_ptr() if first is not None else None,
+                                                         actions.data_ptr(), int(seed), int(step0), int(nsteps), flags,
+                                                         self._stream_ptr()))
         if nsteps > 0:
             self._bufs, self._out = sets[(int(nsteps) - 1) % n]
             self._res = self._bufs
@@ -819,12 +849,14 @@ class BppVecEnv(object):
 
     def _release_side(self):
         side, self._side = getattr(self, "_side", None), None
-        if side is not None and side.value:
-            try:
-                with torch.cuda.device(self.device):
-                    self.lib.bpp_side_destroy(side)
-            except Exception:  # noqa: BLE001 -- interpreter shutdown: the runtime may be gone already
-                pass
+        pipe, self._pipe = getattr(self, "_pipe", None), None
+        for handle, destroy in ((side, "bpp_side_destroy"), (pipe, "bpp_pipeline_destroy")):
+            if handle is not None and handle.value:
+                try:
+                    with torch.cuda.device(self.device):
+                        getattr(self.lib, destroy)(handle)
+                except Exception:  # noqa: BLE001 -- interpreter shutdown: the runtime may be gone already
+                    pass
 
     def __del__(self):
         self._release_side()
