@@ -4,7 +4,12 @@ mcts_test.py:14-65 drives it (fixtures: tests/golden/make_mcts_golden.py).
 CPU: the product kernels in the host SIMT emulator (tests/emu), the fixtures' flat policy between the launches; the sizes
 bound; argument checks.  `-m gpu`: BppVecEnv + MCTSearch on the device, the same policy in torch; subsets, invalid ids,
 the sync-free path, seed ranges, stream supply against pool supply, 2 048 slots against a host restatement over
-oracle/ref_port.py; the toolchain's float64 sqrt against numpy."""
+oracle/ref_port.py; the toolchain's float64 sqrt against numpy.
+
+Every claim here holds under flat_policy only: its softmax is exactly 1/c, so all priors are equal and exact and the
+trajectories match bit for bit.  Under real logits the priors agree with float64 within a float32 softmax tolerance, and
+what follows them (UCB choice, backup, play()) is exact given the priors' bits: tests/test_mcts_real_policy.py checks
+that launch by launch."""
 import ctypes
 import os
 
