@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""The training loop of the reference's main.py:148-185, tensor-native, on a device-resident rollout storage.
+
+    python examples/train_with_storage.py --envs 4096 --updates 4
+
+Per update: `--steps` lock-steps in which the policy's logits go through bpp_masked_act and `storage.step` lets the step kernel
+write observation, mask, reward and done straight into the storage (no insert, no copy of an environment output); then ONE
+native call for the returns (`storage.compute_returns`, the reference's main.py variant: no GAE, no time limits), the
+reference's five loss terms (acktr/algo/acktr_pipeline.py:45-92: value, action, entropy, invalid-probability and mask-prediction
+loss) with the log-probabilities, entropy and invalid probability from bpp_masked_evaluate, and RMSprop with gradient clipping:
+the reference's own optimiser path with acktr=False.  K-FAC is not part of this example.
+
+The network is a plain-torch stand-in shaped like the reference's CNNPro (acktr/model.py:265-323) with random weights.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn as nn
+
+import bpp_amd
+
+
+class ActorCritic(nn.Module):
+    """5 x conv3x3(64) trunk; actor, critic and mask-prediction heads of 1x1 conv + linear layers."""
+
+    def __init__(self, side, n_actions, hidden=256):
+        super().__init__()
+        layers, c = [], 4
+        for _ in range(5):
+            layers += [nn.Conv2d(c, 64, 3, padding=1), nn.ReLU()]
+            c = 64
+        self.share = nn.Sequential(*layers)
+
+        def head(channels, out):
+            return nn.Sequential(nn.Conv2d(64, channels, 1), nn.ReLU(), nn.Flatten(), nn.Linear(channels * side * side, hidden), nn.ReLU(),
+                                 nn.Linear(hidden, out))
+
+        self.actor, self.critic, self.mask = head(8, n_actions), head(4, 1), head(8, n_actions)
+        self.side = side
+
+    def forward(self, obs):
+        x = self.share(obs.reshape(-1, 4, self.side, self.side))
+        return self.actor(x), self.critic(x), torch.sigmoid(self.mask(x))
+
+
+def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True):
+    """Runs `updates` updates; returns one (value_loss, action_loss, dist_entropy, prob_loss, graph_loss) tuple of floats per update."""
+    dev = torch.device(device)
+    size = (10, 10, 10)
+    torch.manual_seed(seed)
+    env = bpp_amd.BppVecEnv(envs, size, enable_rotation=rotation, pool=bpp_amd.sequences.cut2_pool(size, 1024, seed=seed), device=dev)
+    net = ActorCritic(size[0], env.action_space.n).to(dev)
+    # acktr/algo/acktr_pipeline.py:33 with acktr=False; coefficients of the reference's defaults
+    optimizer = torch.optim.RMSprop(net.parameters(), lr, eps=1e-5, alpha=0.99)
+    value_coef, entropy_coef, invalid_coef, force, max_grad_norm = 0.5, 0.01, 2.0, 0.5 * 10, 0.5
+    storage = bpp_amd.RolloutStorage(steps, env, env.observation_space.shape, env.action_space)
+    storage.reset(env)                                   # observation and mask of the reset land in slot 0
+    counter = torch.tensor([seed, 0], dtype=torch.int64, device=dev)     # (seed, step) of the sampler, read by the kernel
+    T, N, M = steps, envs, env.action_space.n
+    history = []
+    for j in range(updates):
+        for t in range(T):                               # main.py:150-174
+            with torch.no_grad():
+                logits, value, _ = net(storage.obs[t])
+            action, logp = bpp_amd.masked_act(logits, storage.location_masks[t], counter=counter)
+            counter[1:].add_(1)
+            storage.step(env, action, value, logp)       # ONE lock-step; its outputs are row t of the storage
+        with torch.no_grad():
+            next_value = net(storage.obs[-1])[1]
+        storage.compute_returns(next_value, False, gamma, 0.95, False)         # main.py:181
+        # acktr/algo/acktr_pipeline.py:45-101
+        logits, values, pred_mask = net(storage.obs[:-1].view(T * N, -1))
+        truth = storage.location_masks[:-1].view(T * N, M)
+        action_log_probs, dist_entropy, prob_loss = bpp_amd.masked_evaluate(logits, truth, storage.actions.view(T * N, 1))
+        advantages = storage.returns[:-1] - values.view(T, N, 1)
+        value_loss = advantages.pow(2).mean()
+        action_loss = -(advantages.detach() * action_log_probs.view(T, N, 1)).mean()
+        graph_loss = nn.functional.mse_loss(pred_mask, truth)
+        optimizer.zero_grad()
+        loss = value_loss * value_coef + action_loss + prob_loss * invalid_coef - dist_entropy * entropy_coef + force * graph_loss
+        loss.backward()
+        nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
+        optimizer.step()
+        storage.after_update()
+        # the infos scan of main.py:159-162, once per update over the [T][N] slabs the lock-steps filled
+        finished = storage.done.bool()
+        n_done = int(finished.sum())
+        mean_ratio = float(storage.ratio[finished].mean()) if n_done else float("nan")
+        history.append(tuple(float(v.detach()) for v in (value_loss, action_loss, dist_entropy, prob_loss, graph_loss)))
+        if verbose:
+            print("update %d: value %.4f  action %.4f  entropy %.4f  invalid-prob %.5f  mask %.4f | %d episodes finished, "
+                  "mean space utilisation %.3f" % ((j + 1,) + history[-1] + (n_done, mean_ratio)))
+    env.close()
+    return history
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--updates", type=int, default=4)
+    ap.add_argument("--rotation", action="store_true")
+    ap.add_argument("--gamma", type=float, default=1.0)
+    args = ap.parse_args()
+    train(args.envs, args.steps, args.updates, args.rotation, args.gamma)
+
+
+if __name__ == "__main__":
+    main()

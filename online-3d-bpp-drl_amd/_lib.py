@@ -20,7 +20,8 @@ REORDER_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_reorder.h")
 MULTIBIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_multibin.h")
 MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
 PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, ROLLOUT_HDR, os.path.join(CSRC, "bpp_returns.inl"), os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -49,6 +50,8 @@ MCTS_MAX_K = 16
 # include/bpp_pipeline.h: the same, for the pipelined rollout driver
 PIPELINE_SYMBOLS = ["bpp_pipeline_create", "bpp_pipeline_destroy", "bpp_pipeline_plan", "bpp_rollout_uniform_sets_pipelined"]
 PIPELINE_MAX_GROUPS, PIPELINE_ALIGN, PIPELINE_MIN_GROUP = 4, 64, 8192
+# include/bpp_rollout.h: the same, for the returns of a device-resident rollout storage
+ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host"]
 
 
 class Batch(ctypes.Structure):
@@ -185,6 +188,16 @@ def bind_mcts(L, batch=None):
     return L
 
 
+def bind_rollout(L):
+    """Argument types of the ROLLOUT_SYMBOLS on library handle L."""
+    vp, i32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    L.bpp_compute_returns_host.argtypes = [vp] * 8 + [i32] * 4 + [f64, f64]
+    L.bpp_compute_returns.argtypes = L.bpp_compute_returns_host.argtypes + [vp]
+    for name in ROLLOUT_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
 def build(force=False, verbose=False):
     """Compile csrc/bpp_kernels.hip for gfx950 into csrc/libbpp_hip.so (in-tree; no-op when fresh)."""
     if LIB != BUILD_LIB:        # an explicitly chosen build is loaded as it is
@@ -286,6 +299,7 @@ def lib():
         bind_reorder(L)
         bind_multibin(L)
         bind_mcts(L)
+        bind_rollout(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

@@ -36,6 +36,7 @@
 #include "../../include/bpp_multibin.h"
 #include "../../include/bpp_mcts.h"
 #include "../../include/bpp_pipeline.h"
+#include "../../include/bpp_rollout.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1959,3 +1960,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_reorder.inl"
 #include "bpp_multibin.inl"
 #include "bpp_mcts.inl"
+#include "bpp_returns.inl"

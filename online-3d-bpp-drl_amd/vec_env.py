@@ -647,10 +647,24 @@ class BppVecEnv(object):
         return self._res.mask if self._res is not None else None
 
     # ------------------------------------------------------------------ VecEnv interface
-    def reset(self):
-        """All bins start a fresh episode (next sequence of their stride); returns obs [E,4A] float32."""
+    def _caller_set(self, out):
+        """out= of reset / step_tensors: a caller-owned output set (StepTensors, bpp_step_out), e.g. a slot of a RolloutStorage.
+        It becomes the env's current result (location_masks, the first mask of rollout_uniform_sets); the env's own set is
+        left alone and is what the next call without out= writes."""
+        if self.fresh_outputs:
+            raise RuntimeError("out= hands the env a caller-owned output set; fresh_outputs=True promises a new set of the env's "
+                               "own every step -- build the env with fresh_outputs=False")
+        res, so = out
+        if not isinstance(so, _lib.StepOut) or res.obs is None or res.obs.device != self.device or \
+                tuple(res.obs.shape) != (self.E, self.obs_len) or (res.mask is not None and tuple(res.mask.shape) != (self.E, self.M)):
+            raise ValueError("out must be (StepTensors, bpp_step_out) with [E,4A] / [E,M] rows on the env's device")
+        return res, so
+
+    def reset(self, out=None):
+        """All bins start a fresh episode (next sequence of their stride); returns obs [E,4A] float32.
+        out: a caller-owned output set the reset writes into instead of the env's own (_caller_set)."""
         self._on_device()
-        bufs, out = self._buffers()
+        bufs, out = self._buffers() if out is None else self._caller_set(out)
         self._res = bufs
         mode = _lib.RESET_INIT if self._first_reset else _lib.RESET_ADVANCE
         if self._stream is not None and not self._first_reset:
@@ -662,13 +676,15 @@ class BppVecEnv(object):
         self._tstart = time.time()
         return bufs["obs"]
 
-    def step_tensors(self, actions, sample=None, _host=None, _dropin=None):
+    def step_tensors(self, actions, sample=None, _host=None, _dropin=None, out=None):
         """Enqueue one lock-step; returns device tensors, never synchronises.  actions: int64 [E] or [E,1].
         sample=(seed, step, out): additionally draw, inside the step kernel, the uniform-feasible action
         for the NEW observation into int64 tensor `out` [E] (== sample_feasible(seed, step) on the new mask;
         `out` may be the action tensor itself).  (_host: page-locked numpy byte buffer the kernel mirrors reward and
         done into; _dropin = (fin_host pointer or None, completion-word pointer or None, value): bpp_step_dropin instead of
-        bpp_step -- step_async's business.)"""
+        bpp_step -- step_async's business.)
+        out: a caller-owned output set (StepTensors, bpp_step_out) this lock-step writes into instead of the env's own
+        (RolloutStorage.step; _caller_set) -- None changes nothing."""
         if self._first_reset:
             raise RuntimeError("call reset() before step()")
         a = actions
@@ -680,10 +696,16 @@ class BppVecEnv(object):
         if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
             a = a.to(device=self.device, dtype=torch.int64).contiguous()
         self._on_device()
-        if self.fresh_outputs or self._bufs is None:
-            self._bufs, self._out = self._alloc()
-            self._res = self._bufs
-        out = self._out          # this output set's own bpp_step_out: the per-call fields are set in place (no struct copy)
+        if out is not None:
+            if _host is not None or _dropin is not None:
+                raise RuntimeError("out= cannot be combined with the host mirror of step_async (its reward / done copy and the "
+                                   "eager gather are laid out for the env's own output set); use step_tensors")
+            self._res, out = self._caller_set(out)
+        else:
+            if self.fresh_outputs or self._bufs is None:
+                self._bufs, self._out = self._alloc()
+            self._res = self._bufs   # (also after a lock-step that went into a caller's set)
+            out = self._out          # this output set's own bpp_step_out: the per-call fields are set in place (no struct copy)
         if sample is not None:
             seed, step, nxt = sample
             if nxt.device != self.device or nxt.dtype != torch.int64 or nxt.numel() != self.E or not nxt.is_contiguous():
@@ -1122,10 +1144,10 @@ class BppVecEnv(object):
         if self._stream is not None:   # streaming supply: the ring, every bin's generator and its progress
             sd.update(stream_ring=self.pool.clone(), stream_mt=self._mt.clone(), stream_gen_next=self.gen_next.clone(),
                       stream_since_refill=self._since_refill, stream_spec=self._stream_identity(), stream_layout=STREAM_LAYOUT)
-        if self._bufs is not None:
-            sd["obs"] = self._bufs["obs"].clone()
-            if self._bufs["mask"] is not None:
-                sd["mask"] = self._bufs["mask"].clone()
+        if self._res is not None:       # (the env's own output set, or the caller's set the last reset / lock-step wrote)
+            sd["obs"] = self._res["obs"].clone()
+            if self._res["mask"] is not None:
+                sd["mask"] = self._res["mask"].clone()
         return sd
 
     def _stream_identity(self):
