@@ -54,6 +54,13 @@ int bpp_compute_returns_host(const float *rewards, float *value_preds, const flo
                              const float *bad_masks, float *returns, float *advantages, int32_t T, int32_t N, int32_t use_gae,
                              int32_t use_proper_time_limits, double gamma, double gae_lambda);
 
+
+/* Which form bpp_compute_returns takes for these arguments (documentation and tests; touches no device, same argument checks):
+ * out = {bins per lane: 4 = 16-byte accesses, 1 = one bin per lane; lanes per workgroup; workgroups}. */
+int bpp_compute_returns_info(const float *rewards, float *value_preds, const float *next_value, const uint8_t *done, float *masks,
+                             const float *bad_masks, float *returns, float *advantages, int32_t T, int32_t N, int32_t use_gae,
+                             int32_t use_proper_time_limits, double gamma, double gae_lambda, int32_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

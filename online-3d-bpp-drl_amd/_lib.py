@@ -51,7 +51,7 @@ MCTS_MAX_K = 16
 PIPELINE_SYMBOLS = ["bpp_pipeline_create", "bpp_pipeline_destroy", "bpp_pipeline_plan", "bpp_rollout_uniform_sets_pipelined"]
 PIPELINE_MAX_GROUPS, PIPELINE_ALIGN, PIPELINE_MIN_GROUP = 4, 64, 8192
 # include/bpp_rollout.h: the same, for the returns of a device-resident rollout storage
-ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host"]
+ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host", "bpp_compute_returns_info"]
 
 
 class Batch(ctypes.Structure):
@@ -193,6 +193,7 @@ def bind_rollout(L):
     vp, i32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
     L.bpp_compute_returns_host.argtypes = [vp] * 8 + [i32] * 4 + [f64, f64]
     L.bpp_compute_returns.argtypes = L.bpp_compute_returns_host.argtypes + [vp]
+    L.bpp_compute_returns_info.argtypes = L.bpp_compute_returns_host.argtypes + [ctypes.POINTER(i32)]
     for name in ROLLOUT_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     return L

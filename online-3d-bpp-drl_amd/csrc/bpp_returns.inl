@@ -162,6 +162,19 @@ ReturnsArgs returns_args(const float *rewards, float *value_preds, const float *
     return a;
 }
 
+// The form a call takes: 4 bins per lane (16-byte accesses) when every row of every array starts 16-byte aligned -- exactly when the
+// array does and N is a multiple of 4 (done rows: 4-byte) --, else one bin per lane.  NULL pointers are aligned.
+int returns_bins_per_lane(const ReturnsArgs &a) {
+    const uintptr_t f32 = (uintptr_t)a.rewards | (uintptr_t)a.value_preds | (uintptr_t)a.next_value | (uintptr_t)a.masks |
+                          (uintptr_t)a.bad_masks | (uintptr_t)a.returns | (uintptr_t)a.advantages;
+    return (a.N % 4 == 0 && (f32 & 15u) == 0 && ((uintptr_t)a.done & 3u) == 0) ? 4 : 1;
+}
+
+unsigned returns_workgroups(const ReturnsArgs &a, int V) {
+    const unsigned lanes = V == 4 ? (unsigned)(a.N / 4) : (unsigned)a.N, per = V == 4 ? kReturnsVecLanes : kReturnsLanes;
+    return (lanes + per - 1) / per;
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,19 +186,29 @@ int bpp_compute_returns(const float *rewards, float *value_preds, const float *n
                                        use_proper_time_limits, gamma, gae_lambda);
     const int rc = returns_check(a, "bpp_compute_returns");
     if (rc) return rc;
-    // every row of every array starts 16-byte aligned exactly when the array does and N is a multiple of 4 (done rows: 4-byte)
-    const uintptr_t f32 = (uintptr_t)rewards | (uintptr_t)value_preds | (uintptr_t)next_value | (uintptr_t)masks | (uintptr_t)bad_masks |
-                          (uintptr_t)returns | (uintptr_t)advantages;
-    if (N % 4 == 0 && (f32 & 15u) == 0 && ((uintptr_t)done & 3u) == 0) {
-        const unsigned lanes = (unsigned)(N / 4);
-        hipLaunchKernelGGL(returns_kernel<4>, dim3((lanes + kReturnsVecLanes - 1) / kReturnsVecLanes), dim3(kReturnsVecLanes), 0,
-                           (hipStream_t)stream, a);
+    if (returns_bins_per_lane(a) == 4) {
+        hipLaunchKernelGGL(returns_kernel<4>, dim3(returns_workgroups(a, 4)), dim3(kReturnsVecLanes), 0, (hipStream_t)stream, a);
     } else {
-        hipLaunchKernelGGL(returns_kernel<1>, dim3(((unsigned)N + kReturnsLanes - 1) / kReturnsLanes), dim3(kReturnsLanes), 0,
-                           (hipStream_t)stream, a);
+        hipLaunchKernelGGL(returns_kernel<1>, dim3(returns_workgroups(a, 1)), dim3(kReturnsLanes), 0, (hipStream_t)stream, a);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+}
+
+int bpp_compute_returns_info(const float *rewards, float *value_preds, const float *next_value, const uint8_t *done, float *masks,
+                             const float *bad_masks, float *returns, float *advantages, int32_t T, int32_t N, int32_t use_gae,
+                             int32_t use_proper_time_limits, double gamma, double gae_lambda, int32_t out[3]) {
+    const ReturnsArgs a = returns_args(rewards, value_preds, next_value, done, masks, bad_masks, returns, advantages, T, N, use_gae,
+                                       use_proper_time_limits, gamma, gae_lambda);
+    const int rc = returns_check(a, "bpp_compute_returns_info");
+    if (rc) return rc;
+    if (!out) {
+        snprintf(g_err, sizeof g_err, "bpp_compute_returns_info: NULL out");
+        return BPP_E_BADARG;
+    }
+    const int V = returns_bins_per_lane(a);
+    out[0] = V, out[1] = V == 4 ? kReturnsVecLanes : kReturnsLanes, out[2] = (int32_t)returns_workgroups(a, V);
+    return 0;
 }
 
 int bpp_compute_returns_host(const float *rewards, float *value_preds, const float *next_value, const uint8_t *done, float *masks,

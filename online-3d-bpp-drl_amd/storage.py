@@ -123,7 +123,9 @@ class RolloutStorage(object):
 
     def output_sets(self):
         """Slots 1 .. T as the `sets` of BppVecEnv.rollout_uniform_sets: with these T sets lock-step t of the driver lands in
-        slot t + 1.  The rollout they fill starts at row 0 and takes its masks from the done bytes."""
+        slot t + 1.  The rollout they fill starts at row 0 and takes its masks from the done bytes.  The slots stay the
+        storage's: after the driver's call slot T is the env's current result (its location_masks), but never the env's own
+        output set -- a later env.reset() or env.step_tensors() without out= writes the env's buffers, not the slabs."""
         sets = [self._slot(j) for j in range(1, self.num_steps + 1)]
         self._from_done = [True] * self.num_steps
         self.step_index = 0
@@ -166,7 +168,7 @@ class RolloutStorage(object):
         if any(self._from_done) and not all(self._from_done):      # a rollout filled both ways: finish the masks, then read them
             for t, d in enumerate(self._from_done):
                 if d:
-                    s["masks"][t + 1].copy_(1.0 - s["done"][t + 1].to(torch.float32))
+                    s["masks"][t + 1].copy_((s["done"][t + 1] == 0).to(torch.float32))     # any nonzero byte is done, as in the kernel
                     self._from_done[t] = False
         done = self.done.data_ptr() if all(self._from_done) else None
         adv = torch.empty((T, N), dtype=torch.float32, device=dev) if advantages else None

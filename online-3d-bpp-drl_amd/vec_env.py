@@ -45,11 +45,12 @@ class StepTensors(object):
     device allocation with a layout {name: (byte offset, dtype, shape)}: the views are then made on first use, so a
     step that nobody inspects beyond `obs` costs one allocation and one view."""
     FIELDS = ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len", "_small")
-    __slots__ = FIELDS + ("_offs", "_stage", "_hot", "_flat", "_layout")
+    __slots__ = FIELDS + ("_offs", "_stage", "_hot", "_flat", "_layout", "_owner")
 
     def __init__(self, _flat=None, _layout=None, **kw):
         self._flat, self._layout = _flat, _layout
         self._offs, self._stage, self._hot = kw.pop("_offs", None), kw.pop("_stage", None), kw.pop("_hot", None)
+        self._owner = kw.pop("_owner", None)     # the ownership mark of the env whose _alloc() made this set (None: a caller's set)
         if _flat is None:
             for k in self.FIELDS:
                 setattr(self, k, kw.get(k))
@@ -427,6 +428,7 @@ class BppVecEnv(object):
             self.refill()
         self._bufs = None
         self._out = None
+        self._set_owner = object()     # marks the output sets _alloc() makes (StepTensors._owner): no reference back to the env
         self._res = None
         self._first_reset = True
         self._out_pool = []        # fresh_outputs: output sets that may be handed out again once unreferenced
@@ -509,7 +511,7 @@ class BppVecEnv(object):
                 self._out_pool.append((flat, out))
         if use_count is not None:
             flat = flat.detach()        # the result's own handle on the storage: the pool's stays the only one when it is gone
-        res = StepTensors(_flat=flat, _layout=regions, _offs=offs, _stage=self._staging, _hot=hot)
+        res = StepTensors(_flat=flat, _layout=regions, _offs=offs, _stage=self._staging, _hot=hot, _owner=self._set_owner)
         return res, out
 
     def _storage_use_count(self):
@@ -760,13 +762,23 @@ class BppVecEnv(object):
         """`n` complete sets of output buffers for rollout_uniform_sets (lock-step t writes set t mod n)."""
         return [self._alloc() for _ in range(int(n))]
 
+    def _is_own_set(self, res):
+        """Did _alloc() of this env make the output set `res` (one flat allocation in the env's layout, staged through the env's
+        own buffers)?  Only such a set may become the env's own: step_async, the host mirrors and the eager gather address
+        it by that layout."""
+        return res._owner is self._set_owner
+
     def rollout_uniform_sets(self, seed, step0, nsteps, actions, sets=None, resume=False, eps=0.0):
         """bpp_rollout_uniform_sets: like rollout_uniform, but lock-step t writes its outputs into sets[t mod n]
         (output_sets(n); default: the env's own single set) and the LAST lock-step also draws the next action, so that
         a following call with resume=True enqueues nothing but its `nsteps` step-kernel launches.  Finite pools only.
         eps > 0: SURVEY 8d's failure-path variant -- every draw is followed by bpp_epsilon_override (with probability eps
         the action becomes a uniform draw over ALL entries; one more tiny launch per lock-step).
-        Returns the StepTensors of the last lock-step."""
+        Returns the StepTensors of the last lock-step, which is the env's current result (location_masks, the first mask of
+        a following call).  Sets the env allocated itself (output_sets(n), the default) rotate: the last one written becomes the
+        env's own set.  Caller-owned sets -- RolloutStorage.output_sets(), anything else built around a bpp_step_out -- are
+        treated like out= of step_tensors (_caller_set): the env's own set is left alone and is what the next reset() /
+        step_tensors() without out= writes, so nothing the env does later lands in the caller's buffers."""
         if self._first_reset:
             raise RuntimeError("call reset() before rollout_uniform_sets()")
         if self._stream is not None:
@@ -776,7 +788,10 @@ class BppVecEnv(object):
         if actions.device != self.device or actions.dtype != torch.int64 or actions.numel() != self.E or not actions.is_contiguous():
             raise ValueError("actions must be a contiguous int64 [E] tensor on the env's device")
         if sets is None:
-            sets = [(self._bufs, self._out)]
+            sets = [self._buffers()]
+        for st in sets:                 # a caller's set of another geometry would be written out of bounds
+            if not self._is_own_set(st[0]):
+                self._caller_set(st)
         n = len(sets)
         outs = (_lib.StepOut * n)(*[self._plain(o) for _, o in sets])
         first = self.location_masks
@@ -795,8 +810,10 @@ class BppVecEnv(object):
                                                          actions.data_ptr(), int(seed), int(step0), int(nsteps), flags,
                                                          self._stream_ptr()))
         if nsteps > 0:
-            self._bufs, self._out = sets[(int(nsteps) - 1) % n]
-            self._res = self._bufs
+            last = sets[(int(nsteps) - 1) % n]
+            if self._is_own_set(last[0]):
+                self._bufs, self._out = last
+            self._res = last[0]
         return self._res
 
     def _stage_offsets(self):

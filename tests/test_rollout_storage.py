@@ -1,7 +1,9 @@
 """CPU checks of the native returns (include/bpp_rollout.h) and of bpp_amd.RolloutStorage on the CPU: the host entry point and
 the emulated device kernel against returns recorded from the reference's RolloutStorage.compute_returns
-(tests/golden/returns_golden.npz) and against the live reference, bit for bit; the done path against the masks path; argument
-validation; exports; and the reference's own ACKTR update on a CPU storage."""
+(tests/golden/returns_golden.npz; tests/golden/returns_edges.npz: chunk, lane and workgroup edges, subnormal numbers, inf and
+NaN) and against the live reference, bit for bit; the done path against the masks path; which form a call takes; argument
+validation; exports; the reference's own ACKTR update on a CPU storage; and a CPU storage fed by the emulated step kernel
+against the reference's storage across updates (tests/golden/storage_updates_*.npz)."""
 import ctypes
 import os
 import re
@@ -22,6 +24,7 @@ import returns_cases as rc  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BADARG = -1
 CASES = rc.load_cases() if os.path.exists(rc.GOLDEN) else []
+EDGE_CASES = rc.load_edge_cases() if os.path.exists(rc.EDGES) else []
 
 
 @pytest.fixture(scope="module")
@@ -37,7 +40,7 @@ def emu_lib(emu):
 
 def check_against_recording(out, d, T, use_gae, want_returns, want_vlast, what):
     assert out["rc"] == 0, what
-    assert np.array_equal(rc.bits(out["returns"]), rc.bits(want_returns)), what      # every row: written ones AND returns[T] under GAE
+    assert rc.same_bits(out["returns"], want_returns), what      # every row: written ones AND returns[T] under GAE (NaN: rc.same_bits)
     if use_gae:
         assert np.array_equal(rc.bits(out["returns"][T]), rc.bits(d["returns0"][T])), what   # ... which the reference leaves alone
     assert np.array_equal(rc.bits(out["value_preds"][T]), rc.bits(want_vlast)), what
@@ -100,13 +103,115 @@ def test_emulated_kernel_on_misaligned_arrays_takes_the_scalar_path(emu_lib, lib
         assert r == 0 and np.array_equal(rc.bits(ret), rc.bits(want["returns"]))
 
 
+def edge_id(c):
+    return "e%d_%s_T%d_N%d_g%s_l%s_gae%d_proper%d" % (c[0], c[10], c[2], c[3], c[4], c[5], c[6], c[7])
+
+
+def test_the_edge_fixture_holds_what_it_claims():
+    """tests/golden/make_returns_edges.py asserted this of the reference's results when it recorded them; here of the file."""
+    assert len(EDGE_CASES) == 248
+    seen = {(f, T, N, g, lam, u, p) for _, _, T, N, g, lam, u, p, _, _, f in EDGE_CASES}
+    pairs = rc.edge_pairs()
+    g, lam = pairs[-1]
+    assert np.float32(g * lam) != np.float32(np.float32(g) * np.float32(lam)) and len(pairs) == 5
+    shapes = {(T, N) for f, T, N, _, _, _, _ in seen if f == "unit"}
+    assert all((T, 260) in shapes for T in rc.EDGE_T) and all((13, N) in shapes for N in rc.EDGE_N) and set(rc.EDGE_LONG) <= shapes
+    for f, T, N, _, _, _, _ in list(seen):                       # all four variants wherever a shape and a pair occur
+        for u, p in rc.VARIANTS:
+            assert any(k[:3] == (f, T, N) and k[5:] == (u, p) for k in seen), (f, T, N, u, p)
+    for pair in pairs:                                          # every pair at T = 13, N = 260, and on some other shape
+        assert ("unit", 13, 260) + pair + (1, 1) in seen and len({k[1:3] for k in seen if k[3:5] == pair}) > 1, pair
+    nan = {f: [0, 0] for f in rc.FAMILIES}
+    for c, d, T, N, g, lam, u, p, want, vlast, f in EDGE_CASES:
+        r = want[:T]
+        sub = (r != 0.0) & (np.abs(r) < rc.FLT_MIN)
+        assert all(np.isfinite(d[k]).all() for k in rc.INPUTS), c
+        assert set(np.unique(d["masks"]).tolist()) <= {0.0, 1.0} and set(np.unique(d["bad_masks"]).tolist()) <= {0.0, 1.0}
+        if f == "denormal":
+            assert sub.any() and np.isfinite(r).all(), c
+        elif f == "huge":
+            assert np.isinf(r).any() and np.isnan(r).any(), c
+        else:
+            assert np.isfinite(r).all(), c
+        nan[f][0] += int(np.isnan(r).sum())
+        nan[f][1] += r.size
+    # NaN positions are compared as a class (rc.same_bits): a minority where they occur, none anywhere else
+    assert nan["unit"][0] == 0 and nan["denormal"][0] == 0 and 0 < 2 * nan["huge"][0] < nan["huge"][1]
+    assert {f for *_, f in EDGE_CASES} == set(rc.FAMILIES)
+
+
+@pytest.mark.parametrize("case", EDGE_CASES, ids=edge_id)
+def test_host_entry_point_matches_the_recorded_edges(lib, case):
+    c, d, T, N, gamma, lam, use_gae, proper, want, vlast, family = case
+    for use_done in (False, True):
+        out = rc.run(lib, d, T, N, gamma, lam, use_gae, proper, use_done=use_done, advantages=True)
+        check_against_recording(out, d, T, use_gae, want, vlast, "done path" if use_done else "masks path")
+        assert np.array_equal(rc.bits(out["masks"]), rc.bits(d["masks"]))
+        with np.errstate(invalid="ignore", over="ignore"):
+            assert rc.same_bits(out["advantages"], out["returns"][:T] - d["value_preds"][:T])
+
+
+@pytest.mark.parametrize("case", EDGE_CASES, ids=edge_id)
+def test_emulated_device_kernel_matches_the_recorded_edges(emu_lib, case):
+    """Both forms of the kernel on the host emulator, masks path and done path: N % 4 == 0 takes four bins per lane (asserted
+    through bpp_compute_returns_info), so T = 9, 13, 17, 33 and 1 000 run a full chunk of eight rows and then a partial one there."""
+    c, d, T, N, gamma, lam, use_gae, proper, want, vlast, family = case
+    for use_done in (False, True):
+        out = rc.run(emu_lib, d, T, N, gamma, lam, use_gae, proper, use_done=use_done, advantages=True, kernel=True)
+        assert out["form"] == (4 if N % 4 == 0 else 1)
+        check_against_recording(out, d, T, use_gae, want, vlast, "done path" if use_done else "masks path")
+        assert np.array_equal(rc.bits(out["masks"]), rc.bits(d["masks"]))
+        with np.errstate(invalid="ignore", over="ignore"):
+            assert rc.same_bits(out["advantages"], out["returns"][:T] - d["value_preds"][:T])
+
+
+MOVABLE = ("rewards", "value_preds", "next_value", "masks", "bad_masks", "returns0", "advantages", "done")
+
+
+@pytest.mark.parametrize("moved", MOVABLE)
+def test_one_misplaced_array_selects_one_bin_per_lane(lib, emu_lib, moved):
+    """N % 4 == 0: any one float array 4 bytes off a 16-byte boundary, or `done` 1, 2 or 3 bytes off a 4-byte boundary, selects the
+    one-bin-per-lane form (bpp_compute_returns_info), and the emulated kernel gives the bits of the aligned call."""
+    T, N = 13, 260
+    d = rc.family_inputs("unit", T, N, seed=77)
+    done = rc.done_of(d["masks"])
+    want = rc.run(lib, d, T, N, 0.99, 0.95, 1, 1, use_done=True, advantages=True)
+    info = (ctypes.c_int32 * 3)()
+    for shift in ((1, 2, 3, 5) if moved == "done" else (4, 8, 12)):
+        for use_done in (False, True):
+            if moved == "done" and not use_done:
+                continue
+            a = {k: rc.placed(v, shift if k == moved else 0) for k, v in d.items()}
+            a["done"] = rc.placed(done, shift if moved == "done" else 0)
+            a["advantages"] = rc.placed(np.full((T, N), -7.0, np.float32), shift if moved == "advantages" else 0)
+            if use_done:
+                a["masks"][1:] = -7.0
+            args = [a["rewards"].ctypes.data, a["value_preds"].ctypes.data, a["next_value"].ctypes.data, a["done"].ctypes.data if use_done else None,
+                    a["masks"].ctypes.data, a["bad_masks"].ctypes.data, a["returns0"].ctypes.data, a["advantages"].ctypes.data, T, N, 1, 1, 0.99, 0.95]
+            for handle in (lib, emu_lib):
+                assert handle.bpp_compute_returns_info(*args, info) == 0 and list(info) == [1, 256, 2], (shift, use_done)
+            assert emu_lib.bpp_compute_returns(*args, None) == 0
+            for k, w in (("returns0", "returns"), ("value_preds", "value_preds"), ("masks", "masks"), ("advantages", "advantages")):
+                assert np.array_equal(rc.bits(a[k]), rc.bits(want[w])), (k, shift, use_done)
+    a = {k: rc.placed(v, 0) for k, v in d.items()}
+    args = [a["rewards"].ctypes.data, a["value_preds"].ctypes.data, a["next_value"].ctypes.data, rc.placed(done, 4).ctypes.data,
+            a["masks"].ctypes.data, a["bad_masks"].ctypes.data, a["returns0"].ctypes.data, None, T, N, 1, 1, 0.99, 0.95]
+    assert lib.bpp_compute_returns_info(*args, info) == 0 and list(info) == [4, 64, 2]         # 65 lanes: one in the second workgroup
+    assert lib.bpp_compute_returns_info(*args[:9], 259, *args[10:], info) == 0 and list(info) == [1, 256, 2]
+    assert lib.bpp_compute_returns_info(*args, None) == BADARG
+
+
 @pytest.mark.skipif(not ref_shims.available(), reason="reference tree not present")
 @pytest.mark.parametrize("T,N", [(7, 1001), (3, 35), (40, 130)])
 def test_host_entry_point_matches_the_live_reference(lib, T, N):
     ref_shims.install()
     from acktr.storage import RolloutStorage
-    for k, (gamma, lam) in enumerate(((0.99, 0.95), (1.0, 1.0), (0.5, 0.3))):
-        d = rc.random_inputs(T, N, seed=100 * T + k)
+    draws = [(rc.random_inputs(T, N, seed=100 * T + k), pair) for k, pair in enumerate(((0.99, 0.95), (1.0, 1.0), (0.5, 0.3)))]
+    # the value families and the (gamma, lambda) pairs of the edge fixture, drawn afresh
+    draws += [(rc.family_inputs(f, T, N, seed=300 * T + k), pair) for k, (f, pair) in
+              enumerate([("denormal", (0.99, 0.95)), ("huge", (0.99, 0.95)), ("huge", (1.0, 1.0)), ("unit", (0.0, 0.95)), ("unit", (0.99, 0.0)),
+                         ("denormal", rc.split_product_pair()), ("unit", rc.split_product_pair())])]
+    for d, (gamma, lam) in draws:
         for use_gae, proper in rc.VARIANTS:
             st = RolloutStorage(T, N, (1,), bpp_amd.Discrete(1), 1, can_give_up=False, enable_rotation=False, pallet_size=1)
             for name in ("rewards", "value_preds", "masks", "bad_masks"):
@@ -116,7 +221,7 @@ def test_host_entry_point_matches_the_live_reference(lib, T, N):
             out = rc.run(lib, d, T, N, gamma, lam, use_gae, proper, advantages=True)
             check_against_recording(out, d, T, use_gae, st.returns.numpy()[:, :, 0], st.value_preds.numpy()[-1, :, 0], (T, N, gamma, use_gae, proper))
             adv = (st.returns[:-1] - st.value_preds[:-1]).numpy()[:, :, 0]
-            assert np.array_equal(rc.bits(out["advantages"]), rc.bits(adv))
+            assert rc.same_bits(out["advantages"], adv)
 
 
 @pytest.mark.parametrize("use_gae,proper", rc.VARIANTS)
@@ -238,3 +343,102 @@ def test_cpu_storage_goes_through_the_reference_update(emu):
         mine.after_update()
         for name in ("obs", "masks", "bad_masks", "location_masks", "recurrent_hidden_states"):
             assert torch.equal(getattr(ref, name)[0], getattr(mine, name)[0]), name
+
+
+STORAGE_SLABS = ("obs", "location_masks", "rewards", "value_preds", "returns", "masks", "bad_masks", "actions", "action_log_probs")
+
+
+def snapshot(st, names=STORAGE_SLABS):
+    return {k: getattr(st, k).detach().cpu().numpy().copy() for k in names}
+
+
+@pytest.mark.parametrize("name", rc.STORAGE_CASES)
+def test_the_storage_fixture_holds_what_it_claims(name):
+    g, s = rc.load_storage_case(name)
+    T, U, N = int(s["T"]), int(s["U"]), g["actions"].shape[1]
+    assert U >= 3 and T == 5 and s["returns"].shape == (U, T + 1, N) == s["masks"].shape == s["value_preds"].shape
+    assert s["main"].tolist() == [0.0, 1.0, 0.95, 0.0] and s["gae"].tolist() == [1.0, 0.99, 0.95, 1.0]
+    for u in range(U):
+        done = g["done"][u * T:(u + 1) * T]
+        assert done.any() and not done.all()                                   # episodes end inside every update
+        assert np.array_equal(s["masks"][u][1:], np.where(done != 0, 0.0, 1.0).astype(np.float32))
+        assert np.array_equal(s["masks"][u][0], s["masks"][u - 1][T] if u else np.ones(N, np.float32))      # after_update
+        assert np.array_equal(rc.bits(s["value_preds"][u][T]), rc.bits(s["next_value"][u]))
+        assert np.array_equal(rc.bits(s["returns_main"][u][T]), rc.bits(s["next_value"][u]))
+        assert not np.array_equal(s["returns"][u][:T], s["returns_main"][u][:T]) and np.isfinite(s["returns"][u]).all()
+    assert (s["masks"][1:, 0] == 0.0).any()                                    # ... and a carried-over row differs from ones
+
+
+@pytest.mark.parametrize("name", rc.STORAGE_CASES)
+def test_cpu_storage_fed_by_the_emulated_step_kernel_equals_the_reference_storage_across_updates(emu, name):
+    """The GPU replay of tests/test_gpu_rollout_storage.py without a GPU: the emulated step kernel plays the recorded actions, a CPU
+    storage takes every lock-step through insert() and the host entry point computes the returns."""
+    g, s = rc.load_storage_case(name)
+    T, U, N = int(s["T"]), int(s["U"]), g["actions"].shape[1]
+    size, rot = tuple(int(v) for v in g["size"]), bool(g["rotation"])
+    env = emu.EmuEnv(g["pool"], size, rot, N, mask_rule=0)
+    st = bpp_amd.RolloutStorage(T, N, (g["obs"].shape[2],), bpp_amd.Discrete(g["mask"].shape[2]), 1)
+    obs, mask = env.reset()
+    st.obs[0].copy_(torch.from_numpy(obs))
+    st.location_masks[0].copy_(torch.from_numpy(mask))
+
+    def col(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).unsqueeze(-1)
+
+    for u in range(U):
+        for t in range(T):
+            assert st.step == t
+            a = g["actions"][u * T + t]
+            o = env.step(a)
+            assert set(np.unique(o["done"]).tolist()) <= {0, 1}
+            st.insert(torch.from_numpy(o["obs"]), torch.zeros(N, 1), col(a), col(s["log_probs"][u, t]), col(s["values"][u, t]), col(o["reward"]),
+                      1.0 - col(o["done"]).to(torch.float32), torch.ones(N, 1), torch.from_numpy(o["mask"]))
+        assert st.step == 0
+        nv = col(s["next_value"][u])
+        assert st.compute_returns(nv, bool(s["main"][0]), s["main"][1], s["main"][2], bool(s["main"][3])) is None
+        main = st.returns.numpy().copy()
+        st.compute_returns(nv, bool(s["gae"][0]), s["gae"][1], s["gae"][2], bool(s["gae"][3]))
+        rc.check_storage_update(dict(snapshot(st), returns_main=main), g, s, u, small_rows=())
+        st.after_update()
+
+
+def filled_cpu_storage(T, N, seed, from_done):
+    d = rc.random_inputs(T, N, seed, bad_ones=True)
+    st = bpp_amd.RolloutStorage(T, N, (4,), bpp_amd.Discrete(4), 1)
+    for k in ("rewards", "value_preds", "masks", "bad_masks"):
+        getattr(st, k).copy_(torch.from_numpy(d[k]).unsqueeze(-1))
+    st.done.copy_(torch.from_numpy(rc.done_of(d["masks"])))                      # bytes 1 and 255 for "done"
+    st._from_done = list(from_done)
+    return st, d
+
+
+@pytest.mark.parametrize("variant", [(False, 0.99, 0.95, False), (True, 0.99, 0.95, True)], ids=["main", "gae_proper"])
+def test_a_rollout_filled_both_ways_reads_any_nonzero_done_byte_as_done(lib, variant):
+    """compute_returns on rows filled partly by lock-steps (done bytes) and partly by insert() (masks): the masks of the former are
+    rebuilt from the bytes, any nonzero byte being 'done' as in the kernel -- hand-written bytes, 255 among them."""
+    T, N = 7, 37
+    for from_done in ([t % 2 == 0 for t in range(T)], [True] * T, [False] * T):
+        st, d = filled_cpu_storage(T, N, 4, from_done)
+        assert (st.done == 255).any() and (st.done == 1).any()
+        for t in range(T):
+            if from_done[t]:
+                st.masks[t + 1].fill_(-7.0)                                      # not valid yet on these rows: must not be read
+        nv = torch.from_numpy(d["next_value"]).unsqueeze(-1)
+        st.compute_returns(nv, *variant)
+        want = rc.run(lib, d, T, N, variant[1], variant[2], int(variant[0]), int(variant[3]))
+        assert np.array_equal(rc.bits(st.masks.numpy()[:, :, 0]), rc.bits(d["masks"]))
+        rows = slice(0, T) if variant[0] else slice(0, T + 1)
+        assert np.array_equal(rc.bits(st.returns.numpy()[rows, :, 0]), rc.bits(want["returns"][rows])), from_done
+        # a second call in a row changes nothing (GAE: value_preds[T] already holds next_value)
+        before = snapshot(st, ("returns", "value_preds", "masks", "rewards"))
+        st.compute_returns(nv, *variant)
+        for k, v in before.items():
+            assert np.array_equal(rc.bits(getattr(st, k).numpy()), rc.bits(v)), k
+
+
+def test_next_value_of_the_wrong_size_is_refused():
+    st, d = filled_cpu_storage(3, 8, 1, [False] * 3)
+    for n in (9, 7, 16):
+        with pytest.raises(ValueError, match="one value per bin"):
+            st.compute_returns(torch.zeros(n, 1), False, 0.99, 0.95, False)
+    st.compute_returns(torch.zeros(8), False, 0.99, 0.95, False)
