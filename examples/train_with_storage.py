@@ -46,8 +46,10 @@ class ActorCritic(nn.Module):
         return self.actor(x), self.critic(x), torch.sigmoid(self.mask(x))
 
 
-def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True):
-    """Runs `updates` updates; returns one (value_loss, action_loss, dist_entropy, prob_loss, graph_loss) tuple of floats per update."""
+def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True, fused_loss=False):
+    """Runs `updates` updates; returns one (value_loss, action_loss, dist_entropy, prob_loss, graph_loss) tuple of floats per update.
+    fused_loss: the five terms and the gradients at the network's outputs from ONE native call (storage.a2c_loss) instead of
+    bpp_masked_evaluate + torch expressions + their autograd backward."""
     dev = torch.device(device)
     size = (10, 10, 10)
     torch.manual_seed(seed)
@@ -71,6 +73,10 @@ def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, see
         with torch.no_grad():
             next_value = net(storage.obs[-1])[1]
         storage.compute_returns(next_value, False, gamma, 0.95, False)         # main.py:181
+        if fused_loss:
+            history.append(fused_update(net, optimizer, storage, (value_coef, entropy_coef, invalid_coef, force), max_grad_norm))
+            report(j, history, storage, verbose)
+            continue
         # acktr/algo/acktr_pipeline.py:45-101
         logits, values, pred_mask = net(storage.obs[:-1].view(T * N, -1))
         truth = storage.location_masks[:-1].view(T * N, M)
@@ -97,6 +103,28 @@ def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, see
     return history
 
 
+def fused_update(net, optimizer, storage, coefs, max_grad_norm):
+    """One update through storage.a2c_loss; returns the five terms as floats."""
+    T, N = storage.num_steps, storage.num_envs
+    logits, values, pred_mask = net(storage.obs[:-1].view(T * N, -1))
+    out = storage.a2c_loss(logits, values, pred_mask, value_loss_coef=coefs[0], entropy_coef=coefs[1], invalid_coef=coefs[2], mask_coef=coefs[3])
+    optimizer.zero_grad()
+    out.backward()
+    nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
+    optimizer.step()
+    storage.after_update()
+    return tuple(out.terms[:5].tolist())
+
+
+def report(j, history, storage, verbose):
+    if verbose:
+        finished = storage.done.bool()
+        n_done = int(finished.sum())
+        mean_ratio = float(storage.ratio[finished].mean()) if n_done else float("nan")
+        print("update %d: value %.4f  action %.4f  entropy %.4f  invalid-prob %.5f  mask %.4f | %d episodes finished, "
+              "mean space utilisation %.3f" % ((j + 1,) + history[-1] + (n_done, mean_ratio)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -104,8 +132,9 @@ def main():
     ap.add_argument("--updates", type=int, default=4)
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--gamma", type=float, default=1.0)
+    ap.add_argument("--fused-loss", action="store_true", help="loss terms and output gradients from one native call (bpp_amd.a2c_loss)")
     args = ap.parse_args()
-    train(args.envs, args.steps, args.updates, args.rotation, args.gamma)
+    train(args.envs, args.steps, args.updates, args.rotation, args.gamma, fused_loss=args.fused_loss)
 
 
 if __name__ == "__main__":

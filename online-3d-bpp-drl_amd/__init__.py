@@ -13,8 +13,9 @@ from .reorder import ReorderSearch  # noqa: F401
 from .spaces import Box, Discrete  # noqa: F401
 from .stats import EpisodeStats, shard_range  # noqa: F401
 from .storage import RolloutStorage  # noqa: F401
+from .update import A2CLoss, a2c_loss  # noqa: F401
 from .vec_env import BppVecEnv, LazyInfos, StepTensors  # noqa: F401
 
 __all__ = ["BppVecEnv", "LazyInfos", "StepTensors", "Box", "Discrete", "batched_mask_from_obs",
            "batched_mask_from_hmap", "batched_window_masks", "get_possible_position", "get_rotation_mask", "build", "sequences", "EpisodeStats", "shard_range", "make_vec_envs", "make_pool", "masked_act", "masked_evaluate", "ReorderSearch",
-           "MultiBinPacker", "MCTSearch", "RolloutStorage"]
+           "MultiBinPacker", "MCTSearch", "RolloutStorage", "A2CLoss", "a2c_loss"]

@@ -21,7 +21,8 @@ MULTIBIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_multibin.h")
 MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
 PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
 ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, ROLLOUT_HDR, os.path.join(CSRC, "bpp_returns.inl"), os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
+DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, ROLLOUT_HDR, UPDATE_HDR, os.path.join(CSRC, "bpp_returns.inl"), os.path.join(CSRC, "bpp_update.inl"), os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1
@@ -52,6 +53,9 @@ PIPELINE_SYMBOLS = ["bpp_pipeline_create", "bpp_pipeline_destroy", "bpp_pipeline
 PIPELINE_MAX_GROUPS, PIPELINE_ALIGN, PIPELINE_MIN_GROUP = 4, 64, 8192
 # include/bpp_rollout.h: the same, for the returns of a device-resident rollout storage
 ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host", "bpp_compute_returns_info"]
+# include/bpp_update.h: the same, for the fused loss of the A2C update
+UPDATE_SYMBOLS = ["bpp_a2c_loss", "bpp_a2c_loss_workspace", "bpp_a2c_loss_info"]
+A2C_TERMS = ("value_loss", "action_loss", "dist_entropy", "prob_loss", "graph_loss", "loss")
 
 
 class Batch(ctypes.Structure):
@@ -199,6 +203,18 @@ def bind_rollout(L):
     return L
 
 
+def bind_update(L):
+    """Argument types of the UPDATE_SYMBOLS on library handle L."""
+    vp, i32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    L.bpp_a2c_loss.argtypes = [vp] * 6 + [f64] * 4 + [vp] * 6 + [i32, i32, vp]
+    L.bpp_a2c_loss.restype = ctypes.c_int
+    L.bpp_a2c_loss_workspace.argtypes = [i32, i32]
+    L.bpp_a2c_loss_workspace.restype = ctypes.c_size_t
+    L.bpp_a2c_loss_info.argtypes = [i32, i32, ctypes.POINTER(i32)]
+    L.bpp_a2c_loss_info.restype = ctypes.c_int
+    return L
+
+
 def build(force=False, verbose=False):
     """Compile csrc/bpp_kernels.hip for gfx950 into csrc/libbpp_hip.so (in-tree; no-op when fresh)."""
     if LIB != BUILD_LIB:        # an explicitly chosen build is loaded as it is
@@ -301,6 +317,7 @@ def lib():
         bind_multibin(L)
         bind_mcts(L)
         bind_rollout(L)
+        bind_update(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

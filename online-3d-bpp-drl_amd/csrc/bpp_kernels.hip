@@ -37,6 +37,7 @@
 #include "../../include/bpp_mcts.h"
 #include "../../include/bpp_pipeline.h"
 #include "../../include/bpp_rollout.h"
+#include "../../include/bpp_update.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1961,3 +1962,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_multibin.inl"
 #include "bpp_mcts.inl"
 #include "bpp_returns.inl"
+#include "bpp_update.inl"

@@ -1,0 +1,330 @@
+// bpp_update.inl -- the loss of the A2C update and its gradients in one pass (include/bpp_update.h), included at the
+// end of bpp_kernels.hip: the five terms of acktr/algo/acktr_pipeline.py:45-92 and d loss / d (logits, values, pred_mask).
+//
+// One wave per row, four rows at a time per 256-lane workgroup, as the evaluate kernels of bpp_heads.inl -- whose expressions
+// these are, in the same operation order: entry k of a row lives in lane k % 64, a lane adds its entries in ascending k, row sums
+// go through wave_sum_f.  What differs is how often memory is visited: for M <= 512 a lane keeps its <= 8 entries of logits,
+// location mask and predicted mask in registers, together with the values the evaluate kernels compute two to four times (the
+// two exponentials, the probability and its logarithm), so each input array is read once per row and each gradient array is
+// written once.  Longer rows walk memory like masked_eval_*_kernel do.  Same bits either way (float32, -ffp-contract=off).
+//
+// The sums of the five per-row terms are taken in double, without atomics, in an order fixed by E alone: a workgroup owns
+// `4 * iters` consecutive rows and publishes one partial, at most kA2cWidth partials exist, one final workgroup adds them.
+
+namespace {
+
+constexpr int kA2cWidth = 1024;     // partials of the row kernel at most = lanes of the final workgroup
+constexpr int kA2cMaxRegs = 8;      // entries of a row a lane holds in registers: M <= 64 * 8
+
+struct A2cArgs {
+    const float *logits, *mask, *values, *returns, *pred;
+    const int64_t *action;
+    float *g_logits, *g_values, *g_pred, *rows;
+    double *partial;
+    int E, M, iters;
+    float cE, g_ent, g_bad, c_v, c_p;
+};
+
+// d loss / d p_k of masked_eval_bwd_kernel (its `hk`), given lg = logf(clamp(p)): the entropy term, and the log-probability
+// term on the entry that is the action taken
+__device__ __forceinline__ float a2c_hk(bool taken, float p, float lg, float gl, float ge) {
+    const bool inside = p > kProbEps && p < 1.0f - kProbEps;
+    const float pc = fminf(fmaxf(p, kProbEps), 1.0f - kProbEps);
+    float h = -ge * (lg + (inside ? p / pc : 0.0f));
+    if (taken) h += inside ? gl / pc : 0.0f;
+    return h;
+}
+
+__device__ __forceinline__ float a2c_logp(const float *x, const float *m, int M, int64_t a, float mq, float sq, float tot) {
+    const float pa = (a >= 0 && a < M) ? (expf(x[a] - (1.0f - m[a]) * 14.0f - mq) / sq + 1e-5f) / tot : kProbEps;
+    return logf(fminf(fmaxf(pa, kProbEps), 1.0f - kProbEps));
+}
+
+// Row e with NJ entries per lane in registers (M <= 64 * NJ).  out = {adv * adv, -(adv * logp), ent, bad, sq}, in every lane.
+template <int NJ>
+__device__ __forceinline__ void a2c_row(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
+    const int M = a.M;
+    const size_t off = e * (size_t)M;
+    const float *x = a.logits + off, *m = a.mask + off;
+    float *g = a.g_logits + off;
+    float xv[NJ], om[NJ];       // logit; 1 - mask
+    float s = 0.0f;
+    if (a.pred) {               // every load of the row is issued before any arithmetic
+        float mv[NJ], pv[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + kWave * j;
+            const bool ok = k < M;
+            xv[j] = ok ? x[k] : 0.0f;
+            mv[j] = ok ? m[k] : 0.0f;
+            pv[j] = ok ? a.pred[off + k] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + kWave * j;
+            if (k < M) {
+                const float d = pv[j] - mv[j];
+                s += d * d;
+                a.g_pred[off + k] = a.c_p * d;
+            }
+            om[j] = 1.0f - mv[j];
+        }
+        s = wave_sum_f(s);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + kWave * j;
+            const bool ok = k < M;
+            xv[j] = ok ? x[k] : 0.0f;
+            om[j] = 1.0f - (ok ? m[k] : 0.0f);
+        }
+    }
+    const float adv = a.returns[e] - a.values[e];
+    const int64_t act = a.action[e];
+    const float gl = -(adv * a.cE), ge = a.g_ent, gb = a.g_bad;
+    // masked_row_stats
+    float q[NJ], av[NJ];        // masked logit -> its exponential -> q; exponential of the plain softmax -> av
+    float mq = -INFINITY, ma = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (lane + kWave * j < M) {
+            q[j] = xv[j] - om[j] * 14.0f;
+            mq = fmaxf(mq, q[j]);
+            ma = fmaxf(ma, xv[j]);
+        }
+    mq = wave_max_f(mq);
+    ma = wave_max_f(ma);
+    float sq = 0.0f, sa = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (lane + kWave * j < M) {
+            q[j] = expf(q[j] - mq);
+            av[j] = expf(xv[j] - ma);
+            sq += q[j];
+            sa += av[j];
+        }
+    sq = wave_sum_f(sq);
+    sa = wave_sum_f(sa);
+    float tot = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (lane + kWave * j < M) {
+            q[j] = q[j] / sq;
+            tot += q[j] + 1e-5f;
+        }
+    tot = wave_sum_f(tot);
+    // masked_eval_fwd_kernel's entropy and bad mass; masked_eval_bwd_kernel's c
+    float hv[NJ];               // h_k
+    float h = 0.0f, b = 0.0f, c = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = lane + kWave * j;
+        if (k < M) {
+            const float p = (q[j] + 1e-5f) / tot;
+            const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
+            h -= p * lg;
+            av[j] = av[j] / sa;
+            b += av[j] * om[j];
+            hv[j] = a2c_hk(k == act, p, lg, gl, ge);
+            c += p * hv[j];
+        }
+    }
+    h = wave_sum_f(h);
+    b = wave_sum_f(b);
+    c = wave_sum_f(c);
+    float v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (lane + kWave * j < M) v += q[j] * (hv[j] - c) / tot;
+    v = wave_sum_f(v);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = lane + kWave * j;
+        if (k < M) {
+            const float u = (hv[j] - c) / tot;
+            g[k] = q[j] * (u - v) + gb * av[j] * (om[j] - b);
+        }
+    }
+    const float logp = a2c_logp(x, m, M, act, mq, sq, tot);
+    if (lane == 0) a.g_values[e] = a.c_v * adv;
+    out[0] = adv * adv, out[1] = -(adv * logp), out[2] = h, out[3] = b, out[4] = s;
+}
+
+// The same for a row of any length: the loops of masked_eval_fwd_kernel and masked_eval_bwd_kernel over memory.
+__device__ __forceinline__ void a2c_row_looped(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
+    const int M = a.M;
+    const size_t off = e * (size_t)M;
+    const float *x = a.logits + off, *m = a.mask + off;
+    float *g = a.g_logits + off;
+    float s = 0.0f;
+    if (a.pred) {
+        for (int k = lane; k < M; k += kWave) {
+            const float d = a.pred[off + k] - m[k];
+            s += d * d;
+            a.g_pred[off + k] = a.c_p * d;
+        }
+        s = wave_sum_f(s);
+    }
+    const float adv = a.returns[e] - a.values[e];
+    const int64_t act = a.action[e];
+    const float gl = -(adv * a.cE), ge = a.g_ent, gb = a.g_bad;
+    const RowStats r = masked_row_stats(x, m, M, lane);
+    float h = 0.0f, b = 0.0f, c = 0.0f;
+    for (int k = lane; k < M; k += kWave) {
+        const float p = (expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq + 1e-5f) / r.tot;
+        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
+        h -= p * lg;
+        b += expf(x[k] - r.ma) / r.sa * (1.0f - m[k]);
+        c += p * a2c_hk(k == act, p, lg, gl, ge);
+    }
+    h = wave_sum_f(h);
+    b = wave_sum_f(b);
+    c = wave_sum_f(c);
+    float v = 0.0f;
+    for (int k = lane; k < M; k += kWave) {
+        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
+        const float p = (q + 1e-5f) / r.tot;
+        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
+        v += q * (a2c_hk(k == act, p, lg, gl, ge) - c) / r.tot;
+    }
+    v = wave_sum_f(v);
+    for (int k = lane; k < M; k += kWave) {
+        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
+        const float p = (q + 1e-5f) / r.tot;
+        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
+        const float u = (a2c_hk(k == act, p, lg, gl, ge) - c) / r.tot;
+        const float avk = expf(x[k] - r.ma) / r.sa;
+        g[k] = q * (u - v) + gb * avk * ((1.0f - m[k]) - b);
+    }
+    const float logp = a2c_logp(x, m, M, act, r.mq, r.sq, r.tot);
+    if (lane == 0) a.g_values[e] = a.c_v * adv;
+    out[0] = adv * adv, out[1] = -(adv * logp), out[2] = h, out[3] = b, out[4] = s;
+}
+
+// NJ = 0: the looped form
+template <int NJ>
+__global__ __launch_bounds__(256) void a2c_loss_kernel(A2cArgs a) {
+    static __shared__ double part[4][5];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const size_t e0 = (size_t)blockIdx.x * 4u * (size_t)a.iters;
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < a.iters; ++i) {
+        const size_t e = e0 + 4u * (size_t)i + (size_t)wave;
+        if (e >= (size_t)a.E) break;       // a whole wave: its later rows lie further out still
+        float r[5];
+        if constexpr (NJ > 0) a2c_row<NJ>(a, e, lane, r);
+        else a2c_row_looped(a, e, lane, r);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) acc[j] = acc[j] + (double)r[j];
+        if (lane == 0 && a.rows) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) a.rows[e * 5 + j] = r[j];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) part[wave][j] = acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int j = threadIdx.x;
+        a.partial[(size_t)blockIdx.x * 5 + j] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+    }
+}
+
+// One workgroup: the G partials -> the six terms.
+__global__ __launch_bounds__(kA2cWidth) void a2c_terms_kernel(const double *partial, int G, int E, int M, double vc, double ec,
+                                                              double ic, double mc, float *terms) {
+    static __shared__ double part[5][kA2cWidth];
+    const int t = threadIdx.x;
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int gi = t; gi < G; gi += kA2cWidth) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) s[j] = s[j] + partial[(size_t)gi * 5 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) part[j][t] = s[j];
+    __syncthreads();
+    for (int d = kA2cWidth / 2; d > 0; d >>= 1) {
+        if (t < d) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) part[j][t] = part[j][t] + part[j][t + d];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double n = (double)E, nm = (double)E * (double)M;
+        const double value_loss = part[0][0] / n, action_loss = part[1][0] / n, dist_entropy = part[2][0] / n;
+        const double prob_loss = part[3][0] / nm, graph_loss = part[4][0] / nm;
+        terms[0] = (float)value_loss, terms[1] = (float)action_loss, terms[2] = (float)dist_entropy;
+        terms[3] = (float)prob_loss, terms[4] = (float)graph_loss;
+        terms[5] = (float)(vc * value_loss + action_loss + ic * prob_loss - ec * dist_entropy + mc * graph_loss);
+    }
+}
+
+// rows per workgroup = 4 * iters and workgroups, from E alone
+void a2c_shape(int E, int &iters, int &groups) {
+    const long long quads = ((long long)E + 3) / 4;
+    iters = (int)((quads + kA2cWidth - 1) / kA2cWidth);
+    groups = (int)((quads + iters - 1) / iters);
+}
+
+int a2c_regs(int M) { return M <= 64 ? 1 : M <= 128 ? 2 : M <= 256 ? 4 : M <= kWave * kA2cMaxRegs ? 8 : 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t bpp_a2c_loss_workspace(int32_t E, int32_t M) {
+    if (E < 1 || M < 1) return 0;
+    int iters, groups;
+    a2c_shape(E, iters, groups);
+    return (size_t)groups * 5 * sizeof(double);
+}
+
+int bpp_a2c_loss_info(int32_t E, int32_t M, int32_t out[4]) {
+    if (E < 1 || M < 1) return fail(BPP_E_BADARG, "bpp_a2c_loss_info: E and M must be >= 1");
+    if (!out) return fail(BPP_E_BADARG, "bpp_a2c_loss_info: NULL out");
+    int iters, groups;
+    a2c_shape(E, iters, groups);
+    out[0] = 4 * iters, out[1] = groups, out[2] = a2c_regs(M) > 0, out[3] = kA2cWidth;
+    return 0;
+}
+
+int bpp_a2c_loss(const float *logits, const float *location_masks, const int64_t *action, const float *values, const float *returns,
+                 const float *pred_mask, double value_loss_coef, double entropy_coef, double invalid_coef, double mask_coef,
+                 float *grad_logits, float *grad_values, float *grad_pred_mask, float *rows, float *terms, void *workspace, int32_t E,
+                 int32_t M, void *stream) {
+    if (E < 1 || M < 1) return fail(BPP_E_BADARG, "bpp_a2c_loss: E and M must be >= 1");
+    if (!logits || !location_masks || !action || !values || !returns || !grad_logits || !grad_values || !terms || !workspace)
+        return fail(BPP_E_BADARG, "bpp_a2c_loss: NULL pointer");
+    if (pred_mask && !grad_pred_mask) return fail(BPP_E_BADARG, "bpp_a2c_loss: pred_mask without grad_pred_mask");
+    A2cArgs a;
+    a.logits = logits, a.mask = location_masks, a.values = values, a.returns = returns, a.pred = pred_mask, a.action = action;
+    a.g_logits = grad_logits, a.g_values = grad_values, a.g_pred = grad_pred_mask, a.rows = rows, a.partial = (double *)workspace;
+    a.E = E, a.M = M;
+    int groups;
+    a2c_shape(E, a.iters, groups);
+    const double n = (double)E, nm = (double)E * (double)M;
+    a.cE = (float)(1.0 / n);
+    a.g_ent = (float)(-entropy_coef / n);
+    a.g_bad = (float)(invalid_coef / nm);
+    a.c_v = (float)(-2.0 * value_loss_coef / n);
+    a.c_p = (float)(2.0 * mask_coef / nm);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (a2c_regs(M)) {
+        case 1: hipLaunchKernelGGL(a2c_loss_kernel<1>, dim3(groups), dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(a2c_loss_kernel<2>, dim3(groups), dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL(a2c_loss_kernel<4>, dim3(groups), dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(a2c_loss_kernel<8>, dim3(groups), dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL(a2c_loss_kernel<0>, dim3(groups), dim3(256), 0, st, a); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    hipLaunchKernelGGL(a2c_terms_kernel, dim3(1), dim3(kA2cWidth), 0, st, (const double *)workspace, groups, E, M, value_loss_coef,
+                       entropy_coef, invalid_coef, mask_coef, terms);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+}
+
+}  // extern "C"

@@ -187,6 +187,15 @@ class RolloutStorage(object):
             raise RuntimeError("RolloutStorage.compute_returns runs on a HIP device or on the CPU, not on %s" % dev)
         return adv.unsqueeze(-1) if adv is not None else None
 
+    def a2c_loss(self, logits, values, pred_mask, **coefs):
+        """The loss of the reference's update on this rollout and its gradients in one native call (update.a2c_loss): logits
+        [T*N, M], values [T*N, 1] or [T, N, 1] and pred_mask [T*N, M] or None are the network's outputs on obs[:-1];
+        location_masks[:-1], actions and returns[:-1] are handed over as views of the slabs, nothing is copied."""
+        from .update import a2c_loss
+        s, T, N = self._slabs, self.num_steps, self.num_envs
+        return a2c_loss(logits, values, pred_mask, s["location_masks"][:-1].view(T * N, -1), s["actions"].view(T * N),
+                        s["returns"][:-1].view(T * N), **coefs)
+
 
 class _Step(int):
     """`storage.step`: the reference's integer attribute -- and callable, `storage.step(env, actions, value, action_log_prob)`
