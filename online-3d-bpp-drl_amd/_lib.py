@@ -4,6 +4,7 @@ There is deliberately NO fallback: if the HIP library cannot be built/loaded, or
 RuntimeError is raised.  The CPU oracle under oracle/ is never imported from here.
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -22,7 +23,9 @@ MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
 PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
 ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
 UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
-DEPS = [SRC, HDR, BRANCH_HDR, REORDER_HDR, MULTIBIN_HDR, MCTS_HDR, PIPELINE_HDR, ROLLOUT_HDR, UPDATE_HDR, os.path.join(CSRC, "bpp_returns.inl"), os.path.join(CSRC, "bpp_update.inl"), os.path.join(CSRC, "bpp_reorder.inl"), os.path.join(CSRC, "bpp_multibin.inl"), os.path.join(CSRC, "bpp_mcts.inl"), os.path.join(CSRC, "bpp_tile_kernel.inl"), os.path.join(CSRC, "bpp_tile_body.inl"), os.path.join(CSRC, "bpp_stream_gen.inl"), os.path.join(CSRC, "bpp_heads.inl"), os.path.join(CSRC, "bpp_rt_kernels.inl"), os.path.join(CSRC, "bpp_stats.inl"), os.path.join(os.path.dirname(HERE), "include", "bpp_gen.inl")]
+# everything a rebuild depends on, by glob: a new .inl or header counts from the moment it exists
+DEPS = sorted(f for d, pats in ((CSRC, ("*.hip", "*.inl")), (os.path.dirname(HDR), ("*.h", "*.inl")))
+              for pat in pats for f in glob.glob(os.path.join(d, pat)))
 
 ABI_VERSION = 16
 STREAM_RNG_MT19937, STREAM_RNG_COUNTER = 0, 1

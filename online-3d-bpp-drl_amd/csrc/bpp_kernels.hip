@@ -1958,6 +1958,7 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 
 }  // extern "C"
 
+#include "bpp_search_common.inl"
 #include "bpp_reorder.inl"
 #include "bpp_multibin.inl"
 #include "bpp_mcts.inl"

@@ -10,7 +10,6 @@
 // State layout (bpp_mcts_sizes): MBin [E] (192 bytes), then MT words [E][kMtStride], then MRec pools [E][2][cap].
 namespace {
 
-constexpr int kMctsWaves = 4;
 constexpr int kMctsMaxK = BPP_MCTS_MAX_K;
 constexpr int kMtStride = 640;      // 624 words, padded to a multiple of 64 bytes
 
@@ -68,23 +67,11 @@ struct MctsArgs {
 
 __device__ __forceinline__ MRec *mcts_half(const MctsArgs &a, int e, int half) { return a.pool + ((size_t)e * 2 + half) * a.cap; }
 
-// (bin, scratch bin) of slot i; false when either lies outside [0, E).
-__device__ __forceinline__ bool mcts_slot(const MctsArgs &a, int i, int &e, int &sid) {
-    const int64_t id = a.ids[i], sc = a.scratch[i];
-    if ((uint64_t)id >= (uint64_t)a.E || (uint64_t)sc >= (uint64_t)a.E) return false;
-    e = (int)id;
-    sid = (int)sc;
-    return true;
-}
-
-__device__ __forceinline__ double vol_reward(uint32_t vol, double binvol) {   // bin3D.get_box_ratio() * 10, float64
-    return vol ? ((double)vol / binvol) * 10.0 : 0.0;
-}
-__device__ __forceinline__ uint32_t item_vol(uint32_t it) { return (it & 255u) * ((it >> 8) & 255u) * ((it >> 16) & 255u); }
-
 __device__ __forceinline__ void mcts_sync() { twist_sync<true>(); }
 
 // ---- numpy's legacy RandomState on the bin's MT19937 (include/bpp_gen.inl: bpp_npmt_*), wave-wide ----------------------
+// (The same rounds as stream_wave_twist's, bpp_stream_gen.inl.  They are not shared: built from one function, the stream
+// kernels' instructions came out in another order, profiles/search_common_resource_usage.txt.)
 __device__ __forceinline__ void mt_twist_wave(uint32_t *mt, int lane) {
     mcts_sync();
     for (int k0 = 0; k0 < 624; k0 += kWave) {     // in place, 64 words at a time: mt[k + 1] is still old, mt[k - 227] new
@@ -156,16 +143,8 @@ __device__ __forceinline__ int choice_scan(const T *p, int cnt, double u) {
 
 // model_loader.evaluate(obs, False)'s pvec: exp(x - max) / sum in float32 (IEEE division), into LDS pv[0..A).
 __device__ __forceinline__ void mcts_softmax(const MctsArgs &a, const float *lg, float *pv, int lane) {
-    float mx = -INFINITY;
-    for (int c = lane; c < a.A; c += kWave) mx = fmaxf(mx, lg[c]);
-    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, kWave));
-    float sum = 0.0f;
-    for (int c = lane; c < a.A; c += kWave) {
-        const float v = expf(lg[c] - mx);
-        pv[c] = v;
-        sum += v;
-    }
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, kWave);
+    float mx, sum;
+    row_softmax_stats(lg, a.A, lane, mx, sum, [&](int c, float v) { pv[c] = v; });
     for (int c = lane; c < a.A; c += kWave) pv[c] = pv[c] / sum;
     wave_sync();
 }
@@ -176,7 +155,7 @@ __device__ __forceinline__ void mcts_commit(const MctsArgs &a, MScal &s, MBin *b
     s.stepped = 0;
     if (s.mode == kDescend) {                                    // monteCarlo.py:64-75
         MRec &c = P[bp->path[s.depth + 1]];
-        c.vol = done ? 0u : item_vol(s.item);
+        c.vol = done ? 0u : item_volume(s.item);
         s.depth += 1;
         if (done) {
             if (!c.term) c.term = 1, c.p = 0.0;
@@ -188,7 +167,7 @@ __device__ __forceinline__ void mcts_commit(const MctsArgs &a, MScal &s, MBin *b
             s.value = 0.0;
             s.mode = kBackup;
         } else if (s.ri + 1 < s.rb) {
-            bp->rvol[s.ri] = item_vol(s.item);
+            bp->rvol[s.ri] = item_volume(s.item);
             s.ri += 1;
         } else {
             s.mode = kBackup;                                    // the last step only decides `done`
@@ -270,36 +249,18 @@ __device__ __forceinline__ void mcts_row(const MctsArgs &a, int sid, int i, floa
     const uint8_t *hm = a.hmap + (size_t)sid * a.A;
     float *row = obs + (size_t)i * 4 * a.A;
     for (int c0 = lane * 4; c0 < a.A; c0 += 4 * kWave) {
-        if ((a.A & 3) == 0) {
-            *(float4 *)(row + c0) = make_float4((float)hm[c0], (float)hm[c0 + 1], (float)hm[c0 + 2], (float)hm[c0 + 3]);
-            *(float4 *)(row + a.A + c0) = make_float4(fx, fx, fx, fx);
-            *(float4 *)(row + 2 * a.A + c0) = make_float4(fy, fy, fy, fy);
-            *(float4 *)(row + 3 * a.A + c0) = make_float4(fz, fz, fz, fz);
-        } else {
-            for (int q = 0; q < 4 && c0 + q < a.A; ++q) {
-                row[c0 + q] = (float)hm[c0 + q];
-                row[a.A + c0 + q] = fx;
-                row[2 * a.A + c0 + q] = fy;
-                row[3 * a.A + c0 + q] = fz;
-            }
-        }
+        float h[4];
+        for (int q = 0; q < 4; ++q) h[q] = c0 + q < a.A ? (float)hm[c0 + q] : 0.0f;
+        store_obs_quad(row, a.A, c0, h, fx, fy, fz);
     }
 }
-
-#define MCTS_SLOT_PROLOGUE                                                                  \
-    const int lane = threadIdx.x & (kWave - 1);                                             \
-    const int wv = (int)(threadIdx.x >> 6);                                                 \
-    const int i = (int)blockIdx.x * kMctsWaves + wv;                                        \
-    if (i >= a.n) return;                                                                   \
-    int e = 0, sid = 0;                                                                     \
-    const bool ok = mcts_slot(a, i, e, sid);
 
 // bpp_mcts_begin: one thread per slot.
 __global__ void mcts_begin_kernel(const MctsArgs a) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= a.n) return;
     int e, sid;
-    if (!mcts_slot(a, i, e, sid)) return;
+    if (!slot_bins(a, i, e, sid)) return;
     MBin *bp = a.bins + e;
     MScal s = bp->s;
     if (!s.tree) {                                               // MCTree.__init__: root = PutNode(None, 1.0)
@@ -314,11 +275,11 @@ __global__ void mcts_begin_kernel(const MctsArgs a) {
 }
 
 // bpp_mcts_select: level `level` of the descent.
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_select_kernel(const MctsArgs a, int level, const uint8_t *step_done,
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_select_kernel(const MctsArgs a, int level, const uint8_t *step_done,
                                                                           int64_t *actions) {
-    static __shared__ double s_vals[kMctsWaves][kMaxArea];
-    static __shared__ uint16_t s_ties[kMctsWaves][kMaxArea];
-    MCTS_SLOT_PROLOGUE
+    static __shared__ double s_vals[kSearchWaves][kMaxArea];
+    static __shared__ uint16_t s_ties[kSearchWaves][kMaxArea];
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) {
         if (lane == 0) actions[i] = BPP_ACTION_NOOP;
         return;
@@ -354,9 +315,9 @@ __global__ __launch_bounds__(kWave * kMctsWaves) void mcts_select_kernel(const M
 }
 
 // bpp_mcts_emit: commit, then the row of every slot whose leaf is expanded (rlevel 0) or whose rollout goes on.
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_emit_kernel(const MctsArgs a, int rlevel, const uint8_t *step_done,
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_emit_kernel(const MctsArgs a, int rlevel, const uint8_t *step_done,
                                                                         float *obs) {
-    MCTS_SLOT_PROLOGUE
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) return;
     MBin *bp = a.bins + e;
     MScal s = bp->s;
@@ -376,10 +337,10 @@ __global__ __launch_bounds__(kWave * kMctsWaves) void mcts_emit_kernel(const Mct
 }
 
 // bpp_mcts_expand: PutNode.expand (node.py:92-137) of the slots whose row was emitted at rollout level 0.
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_expand_kernel(const MctsArgs a, const float *value, const float *logits,
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_expand_kernel(const MctsArgs a, const float *value, const float *logits,
                                                                           int64_t *actions) {
-    static __shared__ float s_pv[kMctsWaves][kMaxArea];
-    MCTS_SLOT_PROLOGUE
+    static __shared__ float s_pv[kSearchWaves][kMaxArea];
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) {
         if (lane == 0) actions[i] = BPP_ACTION_NOOP;
         return;
@@ -482,10 +443,10 @@ __global__ __launch_bounds__(kWave * kMctsWaves) void mcts_expand_kernel(const M
 }
 
 // bpp_mcts_rollout: one more evaluate and np.random.choice of roll_out (node.py:151-160).
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_rollout_kernel(const MctsArgs a, const float *value, const float *logits,
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_rollout_kernel(const MctsArgs a, const float *value, const float *logits,
                                                                            int64_t *actions) {
-    static __shared__ float s_pv[kMctsWaves][kMaxArea];
-    MCTS_SLOT_PROLOGUE
+    static __shared__ float s_pv[kSearchWaves][kMaxArea];
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) {
         if (lane == 0) actions[i] = BPP_ACTION_NOOP;
         return;
@@ -517,7 +478,7 @@ __global__ void mcts_backup_kernel(const MctsArgs a, const uint8_t *step_done) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= a.n) return;
     int e, sid;
-    if (!mcts_slot(a, i, e, sid)) return;
+    if (!slot_bins(a, i, e, sid)) return;
     MBin *bp = a.bins + e;
     MScal s = bp->s;
     MRec *P = mcts_half(a, e, s.half);
@@ -525,11 +486,11 @@ __global__ void mcts_backup_kernel(const MctsArgs a, const uint8_t *step_done) {
     if (s.mode == kBackup) {
         double v = s.value;
         if (s.rb > 0)                                            // node.py:168-170
-            for (int j = s.ri - 1; j >= 0; --j) v = vol_reward(bp->rvol[j], a.binvol) + v;
+            for (int j = s.ri - 1; j >= 0; --j) v = volume_reward(bp->rvol[j], a.binvol) + v;
         if (s.leaf) P[P[bp->path[s.depth]].block].w = v;         // self.value = value
         for (int d = s.depth; d >= 0; --d) {
             MRec &r = P[bp->path[d]];
-            v = vol_reward(r.vol, a.binvol) + v;
+            v = volume_reward(r.vol, a.binvol) + v;
             r.n += 1;
             r.w += v;
         }
@@ -541,9 +502,9 @@ __global__ void mcts_backup_kernel(const MctsArgs a, const uint8_t *step_done) {
 }
 
 // bpp_mcts_finish: MCTree.play(zeta) and sample_action (monteCarlo.py:92-125).
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_finish_kernel(const MctsArgs a, int64_t *action, int32_t *visits) {
-    static __shared__ double s_p[kMctsWaves][kMaxArea];
-    MCTS_SLOT_PROLOGUE
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_finish_kernel(const MctsArgs a, int64_t *action, int32_t *visits) {
+    static __shared__ double s_p[kSearchWaves][kMaxArea];
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) {
         if (lane == 0) action[i] = BPP_ACTION_NOOP, visits[i] = 0;
         return;
@@ -579,7 +540,7 @@ __global__ __launch_bounds__(kWave * kMctsWaves) void mcts_finish_kernel(const M
             p[j] = x;
             mx = fmax(mx, x);
         }
-        for (int m = 32; m >= 1; m >>= 1) mx = fmax(mx, __shfl_xor(mx, m, kWave));
+        mx = wave_max(mx);
         for (int j = lane; j < cnt; j += kWave) p[j] = exp(p[j] - mx);
         wave_sync();
         int pos = s.mtpos;
@@ -602,8 +563,8 @@ __global__ __launch_bounds__(kWave * kMctsWaves) void mcts_finish_kernel(const M
 
 // bpp_mcts_advance: MCTree.succeed (monteCarlo.py:127-139) -- the chosen child's subtree is copied, breadth first, into the
 // other pool half, the child at record 0 with p = 1 -- or a dropped tree where the episode ended.
-__global__ __launch_bounds__(kWave * kMctsWaves) void mcts_advance_kernel(const MctsArgs a, const uint8_t *done) {
-    MCTS_SLOT_PROLOGUE
+__global__ __launch_bounds__(kWave * kSearchWaves) void mcts_advance_kernel(const MctsArgs a, const uint8_t *done) {
+    SEARCH_SLOT_BINS_PROLOGUE(a)
     if (!ok) return;
     MBin *bp = a.bins + e;
     MScal s = bp->s;
@@ -670,7 +631,7 @@ __global__ void mcts_seed_kernel(const MctsArgs a, const int64_t *ids, const uin
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= count) return;
     const int64_t id = ids[j];
-    if ((uint64_t)id >= (uint64_t)a.E) return;
+    if (!bin_in_range(id, a.E)) return;
     uint32_t *mt = a.mt + (size_t)id * kMtStride;
     uint32_t v = seeds[j];
     mt[0] = v;
@@ -686,11 +647,9 @@ __global__ void mcts_clear_kernel(const MctsArgs a, const int64_t *ids, int coun
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= count) return;
     const int64_t id = ids ? ids[j] : (int64_t)j;
-    if ((uint64_t)id >= (uint64_t)a.E) return;
+    if (!bin_in_range(id, a.E)) return;
     a.bins[id].s.tree = 0;
 }
-
-#undef MCTS_SLOT_PROLOGUE
 
 int64_t mcts_cap(int k, int S, int max_depth, int A) { return 1 + (int64_t)(max_depth + 1) * S * (A + 1); }
 
@@ -715,30 +674,22 @@ MctsLayout mcts_layout(int64_t E, int64_t cap) {
 }
 
 // Everything an MCTS call checks before device work; fills the kernel arguments.
-int mcts_args(const bpp_batch *b, const bpp_mcts *m, const char *who, MctsArgs &a) {
-    static thread_local char msg[160];
-    auto bad = [&](const char *what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(BPP_E_BADARG, msg);
-    };
-    if (!b || !m) return bad("NULL pointer");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+int mcts_args(const bpp_batch *b, const bpp_mcts *m, const ArgCheck &ck, MctsArgs &a) {
+    const int rc = check_search_batch(b, m, ck, "MCTS supports bins without rotation only", false);
     if (rc) return rc;
-    if (b->rotation) return bad("MCTS supports bins without rotation only");
-    if (!b->hmap || !b->state) return bad("NULL batch buffer");
-    if (m->k < 2 || m->k > kMctsMaxK) return bad("k must be in 2 .. 16");
-    if (m->n < 0) return bad("negative n");
-    if (m->sim_times < 1) return bad("sim_times must be positive");
-    if (m->max_depth < 0 || m->max_depth > m->k - 1) return bad("max_depth must be in 0 .. k - 1");
-    if (m->rollout_length < -1) return bad("rollout_length must be -1, 0 or positive");
-    if (!(m->credit >= 0.0 && m->credit <= 1.0)) return bad("credit must be in [0, 1]");
-    if (!(m->zeta > 0.0)) return bad("zeta must be positive");
+    if (m->k < 2 || m->k > kMctsMaxK) return ck.bad("k must be in 2 .. 16");
+    if (m->n < 0) return ck.bad("negative n");
+    if (m->sim_times < 1) return ck.bad("sim_times must be positive");
+    if (m->max_depth < 0 || m->max_depth > m->k - 1) return ck.bad("max_depth must be in 0 .. k - 1");
+    if (m->rollout_length < -1) return ck.bad("rollout_length must be -1, 0 or positive");
+    if (!(m->credit >= 0.0 && m->credit <= 1.0)) return ck.bad("credit must be in [0, 1]");
+    if (!(m->zeta > 0.0)) return ck.bad("zeta must be positive");
     const int A = b->W * b->L;
-    if (m->cap != mcts_cap(m->k, m->sim_times, m->max_depth, A)) return bad("cap must be the one bpp_mcts_sizes gives");
-    if (!m->state || !m->overflow) return bad("NULL state / overflow");
-    if (m->n > 0 && (!m->ids || !m->scratch)) return bad("NULL ids / scratch");
+    if (m->cap != mcts_cap(m->k, m->sim_times, m->max_depth, A)) return ck.bad("cap must be the one bpp_mcts_sizes gives");
+    if (!m->state || !m->overflow) return ck.bad("NULL state / overflow");
+    if (m->n > 0 && (!m->ids || !m->scratch)) return ck.bad("NULL ids / scratch");
     if (((uintptr_t)m->ids & 7u) || ((uintptr_t)m->scratch & 7u) || ((uintptr_t)m->state & 15u) || ((uintptr_t)m->overflow & 3u))
-        return bad("ids / scratch must be 8-byte aligned, state 16-byte aligned, overflow 4-byte aligned");
+        return ck.bad("ids / scratch must be 8-byte aligned, state 16-byte aligned, overflow 4-byte aligned");
     const MctsLayout l = mcts_layout(b->num_envs, m->cap);
     a.n = m->n, a.k = m->k, a.S = m->sim_times, a.max_depth = m->max_depth, a.rollout = m->rollout_length, a.cap = m->cap;
     a.A = A, a.W = b->W, a.L = b->L, a.H = b->H, a.E = b->num_envs;
@@ -754,28 +705,21 @@ int mcts_args(const bpp_batch *b, const bpp_mcts *m, const char *who, MctsArgs &
     return 0;
 }
 
-int mcts_launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-inline dim3 mcts_grid(int n) { return dim3((unsigned)((n + kMctsWaves - 1) / kMctsWaves)); }
-inline dim3 mcts_grid1(int n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 
 extern "C" {
 
 int bpp_mcts_sizes(int32_t E, int32_t k, int32_t sim_times, int32_t max_depth, int32_t rollout_length, int32_t W, int32_t L,
                    int64_t out[4]) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_mcts_sizes: NULL pointer");
-    if (E < 0 || W <= 0 || L <= 0 || W * L > kMaxArea) return fail(BPP_E_BADARG, "bpp_mcts_sizes: bad E or geometry");
-    if (k < 2 || k > kMctsMaxK) return fail(BPP_E_BADARG, "bpp_mcts_sizes: k must be in 2 .. 16");
-    if (sim_times < 1) return fail(BPP_E_BADARG, "bpp_mcts_sizes: sim_times must be positive");
-    if (max_depth < 0 || max_depth > k - 1) return fail(BPP_E_BADARG, "bpp_mcts_sizes: max_depth must be in 0 .. k - 1");
-    if (rollout_length < -1) return fail(BPP_E_BADARG, "bpp_mcts_sizes: rollout_length must be -1, 0 or positive");
+    const ArgCheck ck{"bpp_mcts_sizes"};
+    if (!out) return ck.bad("NULL pointer");
+    if (E < 0 || W <= 0 || L <= 0 || W * L > kMaxArea) return ck.bad("bad E or geometry");
+    if (k < 2 || k > kMctsMaxK) return ck.bad("k must be in 2 .. 16");
+    if (sim_times < 1) return ck.bad("sim_times must be positive");
+    if (max_depth < 0 || max_depth > k - 1) return ck.bad("max_depth must be in 0 .. k - 1");
+    if (rollout_length < -1) return ck.bad("rollout_length must be -1, 0 or positive");
     const int64_t cap = mcts_cap(k, sim_times, max_depth, W * L);
-    if (cap > (int64_t)1 << 30) return fail(BPP_E_BADARG, "bpp_mcts_sizes: pool too large");
+    if (cap > (int64_t)1 << 30) return ck.bad("pool too large");
     const MctsLayout l = mcts_layout(E, cap);
     out[0] = l.total;
     out[1] = cap;
@@ -786,81 +730,62 @@ int bpp_mcts_sizes(int32_t E, int32_t k, int32_t sim_times, int32_t max_depth, i
 
 int bpp_mcts_seed(const bpp_batch *b, const bpp_mcts *m, const int64_t *ids, const uint32_t *seeds, int32_t count, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_seed", a);
-    if (rc) return rc;
-    if (count < 0) return fail(BPP_E_BADARG, "bpp_mcts_seed: negative count");
-    if (count > 0 && (!ids || !seeds)) return fail(BPP_E_BADARG, "bpp_mcts_seed: NULL pointer");
-    if (((uintptr_t)ids & 7u) || ((uintptr_t)seeds & 3u)) return fail(BPP_E_BADARG, "bpp_mcts_seed: misaligned buffer");
-    if (count == 0) return 0;
-    hipLaunchKernelGGL(mcts_seed_kernel, mcts_grid1(count), dim3(256), 0, (hipStream_t)stream, a, ids, seeds, count);
-    return mcts_launched();
+    const ArgCheck ck{"bpp_mcts_seed"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (count < 0) return ck.bad("negative count");
+    if (count > 0 && (!ids || !seeds)) return ck.bad("NULL pointer");
+    if (((uintptr_t)ids & 7u) || ((uintptr_t)seeds & 3u)) return ck.bad("misaligned buffer");
+    return launch_items(mcts_seed_kernel, count, stream, a, ids, seeds, count);
 }
 
 int bpp_mcts_clear(const bpp_batch *b, const bpp_mcts *m, const int64_t *ids, int32_t count, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_clear", a);
-    if (rc) return rc;
-    if (count < 0) return fail(BPP_E_BADARG, "bpp_mcts_clear: negative count");
-    if ((uintptr_t)ids & 7u) return fail(BPP_E_BADARG, "bpp_mcts_clear: misaligned ids");
+    const ArgCheck ck{"bpp_mcts_clear"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (count < 0) return ck.bad("negative count");
+    if ((uintptr_t)ids & 7u) return ck.bad("misaligned ids");
     if (!ids) count = a.E;
-    if (count == 0) return 0;
-    hipLaunchKernelGGL(mcts_clear_kernel, mcts_grid1(count), dim3(256), 0, (hipStream_t)stream, a, ids, count);
-    return mcts_launched();
+    return launch_items(mcts_clear_kernel, count, stream, a, ids, count);
 }
 
 int bpp_mcts_begin(const bpp_batch *b, const bpp_mcts *m, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_begin", a);
-    if (rc || a.n == 0) return rc;
-    hipLaunchKernelGGL(mcts_begin_kernel, mcts_grid1(a.n), dim3(256), 0, (hipStream_t)stream, a);
-    return mcts_launched();
+    if (const int rc = mcts_args(b, m, ArgCheck{"bpp_mcts_begin"}, a)) return rc;
+    return launch_items(mcts_begin_kernel, a.n, stream, a);
 }
 
 int bpp_mcts_select(const bpp_batch *b, const bpp_mcts *m, int32_t level, const uint8_t *step_done, int64_t *actions,
                     void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_select", a);
-    if (rc) return rc;
-    if (level < 0 || level >= a.max_depth) return fail(BPP_E_BADARG, "bpp_mcts_select: level must be in 0 .. max_depth - 1");
-    if (level > 0 && a.n > 0 && !step_done) return fail(BPP_E_BADARG, "bpp_mcts_select: NULL step_done after level 0");
-    if (a.n > 0 && !actions) return fail(BPP_E_BADARG, "bpp_mcts_select: NULL actions");
-    if ((uintptr_t)actions & 7u) return fail(BPP_E_BADARG, "bpp_mcts_select: misaligned actions");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(mcts_select_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, level, step_done,
-                       actions);
-    return mcts_launched();
+    const ArgCheck ck{"bpp_mcts_select"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (level < 0 || level >= a.max_depth) return ck.bad("level must be in 0 .. max_depth - 1");
+    if (level > 0 && a.n > 0 && !step_done) return ck.bad("NULL step_done after level 0");
+    if (a.n > 0 && !actions) return ck.bad("NULL actions");
+    if ((uintptr_t)actions & 7u) return ck.bad("misaligned actions");
+    return launch_slots(mcts_select_kernel, a.n, stream, a, level, step_done, actions);
 }
 
 int bpp_mcts_emit(const bpp_batch *b, const bpp_mcts *m, int32_t rollout_level, const uint8_t *step_done, float *obs, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_emit", a);
-    if (rc) return rc;
+    const ArgCheck ck{"bpp_mcts_emit"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
     const int levels = mcts_rollout_levels(a.k, a.max_depth, a.rollout);
-    if (rollout_level < 0 || (rollout_level > 0 && rollout_level >= levels))
-        return fail(BPP_E_BADARG, "bpp_mcts_emit: rollout_level must be in 0 .. rollout_levels - 1");
-    if (a.n > 0 && !obs) return fail(BPP_E_BADARG, "bpp_mcts_emit: NULL obs");
-    if ((uintptr_t)obs & 15u) return fail(BPP_E_BADARG, "bpp_mcts_emit: obs must be 16-byte aligned");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(mcts_emit_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, rollout_level,
-                       step_done, obs);
-    return mcts_launched();
+    if (rollout_level < 0 || (rollout_level > 0 && rollout_level >= levels)) return ck.bad("rollout_level must be in 0 .. rollout_levels - 1");
+    if (a.n > 0 && !obs) return ck.bad("NULL obs");
+    if ((uintptr_t)obs & 15u) return ck.bad("obs must be 16-byte aligned");
+    return launch_slots(mcts_emit_kernel, a.n, stream, a, rollout_level, step_done, obs);
 }
 
+// bpp_mcts_expand and bpp_mcts_rollout take the same arguments under the same checks.
 static int mcts_eval_call(const bpp_batch *b, const bpp_mcts *m, const float *value, const float *logits, int64_t *actions,
                           void *stream, bool expand) {
     MctsArgs a;
-    const char *who = expand ? "bpp_mcts_expand" : "bpp_mcts_rollout";
-    int rc = mcts_args(b, m, who, a);
-    if (rc) return rc;
-    if (a.n > 0 && (!value || !logits || !actions)) return fail(BPP_E_BADARG, expand ? "bpp_mcts_expand: NULL pointer" : "bpp_mcts_rollout: NULL pointer");
-    if (((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)actions & 7u))
-        return fail(BPP_E_BADARG, expand ? "bpp_mcts_expand: misaligned buffer" : "bpp_mcts_rollout: misaligned buffer");
-    if (a.n == 0) return 0;
-    if (expand)
-        hipLaunchKernelGGL(mcts_expand_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, value, logits, actions);
-    else
-        hipLaunchKernelGGL(mcts_rollout_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, value, logits, actions);
-    return mcts_launched();
+    const ArgCheck ck{expand ? "bpp_mcts_expand" : "bpp_mcts_rollout"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && (!value || !logits || !actions)) return ck.bad("NULL pointer");
+    if (((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)actions & 7u)) return ck.bad("misaligned buffer");
+    return launch_slots(expand ? mcts_expand_kernel : mcts_rollout_kernel, a.n, stream, a, value, logits, actions);
 }
 
 int bpp_mcts_expand(const bpp_batch *b, const bpp_mcts *m, const float *value, const float *logits, int64_t *actions, void *stream) {
@@ -873,31 +798,25 @@ int bpp_mcts_rollout(const bpp_batch *b, const bpp_mcts *m, const float *value, 
 
 int bpp_mcts_backup(const bpp_batch *b, const bpp_mcts *m, const uint8_t *step_done, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_backup", a);
-    if (rc || a.n == 0) return rc;
-    hipLaunchKernelGGL(mcts_backup_kernel, mcts_grid1(a.n), dim3(256), 0, (hipStream_t)stream, a, step_done);
-    return mcts_launched();
+    if (const int rc = mcts_args(b, m, ArgCheck{"bpp_mcts_backup"}, a)) return rc;
+    return launch_items(mcts_backup_kernel, a.n, stream, a, step_done);
 }
 
 int bpp_mcts_finish(const bpp_batch *b, const bpp_mcts *m, int64_t *action, int32_t *root_visits, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_finish", a);
-    if (rc) return rc;
-    if (a.n > 0 && (!action || !root_visits)) return fail(BPP_E_BADARG, "bpp_mcts_finish: NULL pointer");
-    if (((uintptr_t)action & 7u) || ((uintptr_t)root_visits & 3u)) return fail(BPP_E_BADARG, "bpp_mcts_finish: misaligned buffer");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(mcts_finish_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, action, root_visits);
-    return mcts_launched();
+    const ArgCheck ck{"bpp_mcts_finish"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && (!action || !root_visits)) return ck.bad("NULL pointer");
+    if (((uintptr_t)action & 7u) || ((uintptr_t)root_visits & 3u)) return ck.bad("misaligned buffer");
+    return launch_slots(mcts_finish_kernel, a.n, stream, a, action, root_visits);
 }
 
 int bpp_mcts_advance(const bpp_batch *b, const bpp_mcts *m, const uint8_t *done, void *stream) {
     MctsArgs a;
-    int rc = mcts_args(b, m, "bpp_mcts_advance", a);
-    if (rc) return rc;
-    if (a.n > 0 && !done) return fail(BPP_E_BADARG, "bpp_mcts_advance: NULL done");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(mcts_advance_kernel, mcts_grid(a.n), dim3(kWave * kMctsWaves), 0, (hipStream_t)stream, a, done);
-    return mcts_launched();
+    const ArgCheck ck{"bpp_mcts_advance"};
+    if (const int rc = mcts_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && !done) return ck.bad("NULL done");
+    return launch_slots(mcts_advance_kernel, a.n, stream, a, done);
 }
 
 }  // extern "C"

@@ -8,7 +8,6 @@
 // reduced with shuffles, then lane 0 adds the window to the float64 advantage scan.  commit and clear are per slot.
 namespace {
 
-constexpr int kMBWaves = 4;
 constexpr int kMBMaxK = BPP_MULTIBIN_MAX_K;
 
 // A pallet's record of one window (multi_bin.py's past_rewards[label][-1], evaluations[label][-1]).
@@ -39,14 +38,12 @@ struct MBArgs {
     const bpp_env_state *bins;
 };
 
-__global__ __launch_bounds__(kWave * kMBWaves) void multibin_emit_kernel(const MBArgs a, float *obs) {
-    static __shared__ __attribute__((aligned(16))) uint8_t hs[kMBWaves][kMaxArea];
-    const int lane = threadIdx.x & (kWave - 1), wv = (int)(threadIdx.x >> 6);
-    const int i = (int)blockIdx.x * kMBWaves + wv;
-    if (i >= a.n) return;
+__global__ __launch_bounds__(kWave * kSearchWaves) void multibin_emit_kernel(const MBArgs a, float *obs) {
+    static __shared__ __attribute__((aligned(16))) uint8_t hs[kSearchWaves][kMaxArea];
+    SEARCH_SLOT_PROLOGUE(a)
     const int64_t id = a.ids[i];
     MBSlot *sl = a.slots + i;
-    if ((uint64_t)id >= (uint64_t)a.E) {
+    if (!bin_in_range(id, a.E)) {
         if (lane == 0) *sl = MBSlot{0, 0, 0u, -2};
         return;
     }
@@ -81,6 +78,8 @@ __global__ __launch_bounds__(kWave * kMBWaves) void multibin_emit_kernel(const M
                 mbits |= 1u << (8 * j);
         }
         float *row = obs + ((size_t)i * a.K + k) * 4 * w2;
+        // store_obs_quad's stores, written out: through the shared function this kernel's code came out 17 instructions longer
+        // and a decision of 65 536 pallets 1.7 % slower (profiles/search_common_ab.json)
         if (vec) {
             *(float4 *)(row + c0) = make_float4(hv[0], hv[1], hv[2], hv[3]);
             *(float4 *)(row + w2 + c0) = make_float4(fx, fx, fx, fx);
@@ -99,11 +98,9 @@ __global__ __launch_bounds__(kWave * kMBWaves) void multibin_emit_kernel(const M
     if (lane == 0) *sl = MBSlot{1, e, it, -2};
 }
 
-__global__ __launch_bounds__(kWave * kMBWaves) void multibin_choose_kernel(const MBArgs a, const float *value, const float *logits,
+__global__ __launch_bounds__(kWave * kSearchWaves) void multibin_choose_kernel(const MBArgs a, const float *value, const float *logits,
                                                                             int64_t *action, double *adv, int32_t *window) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int i = (int)blockIdx.x * kMBWaves + (int)(threadIdx.x >> 6);
-    if (i >= a.n) return;
+    SEARCH_SLOT_PROLOGUE(a)
     MBSlot *sl = a.slots + i;
     const MBSlot s = *sl;
     if (!s.ok) {
@@ -117,13 +114,10 @@ __global__ __launch_bounds__(kWave * kMBWaves) void multibin_choose_kernel(const
     for (int k = 0; k < a.K; ++k) {
         const float *lg = logits + ((size_t)i * a.K + k) * w2;
         const uint8_t *mk = a.masks + ((size_t)i * a.K + k) * a.mstride;
-        float mx = -INFINITY;
-        for (int c = lane; c < w2; c += kWave) mx = fmaxf(mx, lg[c]);
-        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, kWave));
-        float sum = 0.0f;
+        float mx, sum;
         int cnt = 0;
-        for (int c = lane; c < w2; c += kWave) sum += expf(lg[c] - mx), cnt += mk[c];
-        for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, kWave), cnt += __shfl_xor(cnt, m, kWave);
+        row_softmax_stats(lg, w2, lane, mx, sum, [&](int c, float) { cnt += mk[c]; });
+        cnt = wave_sum(cnt);
         if (cnt == 0 || cnt == w2) continue;                    // the mask (with its fallback) sums to w^2: skipped
         float best = -1.0f;
         int bi = 0;
@@ -131,11 +125,7 @@ __global__ __launch_bounds__(kWave * kMBWaves) void multibin_choose_kernel(const
             const float p = mk[c] ? expf(lg[c] - mx) / sum : 0.0f;     // poss * mask
             if (p > best) best = p, bi = c;
         }
-        for (int m = 32; m >= 1; m >>= 1) {                      // np.argmax: the first maximum
-            const float ob = __shfl_xor(best, m, kWave);
-            const int oi = __shfl_xor(bi, m, kWave);
-            if (ob > best || (ob == best && oi < bi)) best = ob, bi = oi;
-        }
+        wave_argmax(best, bi, false);                            // np.argmax: the first maximum
         if (lane == 0) {
             const MBWin r = rec[k];
             const double v = (double)value[(size_t)i * a.K + k];
@@ -170,7 +160,7 @@ __global__ void multibin_commit_kernel(const MBArgs a, const uint8_t *step_done)
     if (step_done[i]) {                                          // the episode ended: test() starts new dicts
         for (int k = 0; k < a.K; ++k) rec[k] = MBWin{0.0, 0.0, 0};
     } else {
-        const double r = item_reward(s.item, a.binvol);
+        const double r = volume_reward(item_volume(s.item), a.binvol);
         if (s.window >= 0) {
             rec[s.window].reward = r;
             rec[s.window].has = 1;
@@ -186,7 +176,7 @@ __global__ void multibin_clear_kernel(const MBArgs a, const int64_t *ids, int n)
     if (t >= n * a.K) return;
     const int j = t / a.K, k = t - j * a.K;
     const int64_t id = ids ? ids[j] : (int64_t)j;
-    if ((uint64_t)id >= (uint64_t)a.E) return;
+    if (!bin_in_range(id, a.E)) return;
     a.state[(size_t)id * a.K + k] = MBWin{0.0, 0.0, 0};
 }
 
@@ -196,20 +186,15 @@ struct MBLayout {
 };
 
 // Geometry of the windows and the buffers; 0 or an error (messages name `who`).
-int multibin_layout(int W, int L, int w, int s, int64_t n, int64_t E, const char *who, MBLayout &l) {
-    static thread_local char msg[160];
-    auto bad = [&](const char *what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(BPP_E_BADARG, msg);
-    };
-    if (W <= 0 || L <= 0 || W * L > kMaxArea) return bad("pallet W * L must be in 1 .. 1024");
-    if (w < 1 || w > W || w > L) return bad("window side w must be in 1 .. min(W, L)");
-    if (w * w > kMaxArea) return bad("window area w * w must be at most 1024");
-    if (s < 1) return bad("stride s must be at least 1");
-    if (n < 0 || E < 0) return bad("negative n or E");
+int multibin_layout(int W, int L, int w, int s, int64_t n, int64_t E, const ArgCheck &ck, MBLayout &l) {
+    if (W <= 0 || L <= 0 || W * L > kMaxArea) return ck.bad("pallet W * L must be in 1 .. 1024");
+    if (w < 1 || w > W || w > L) return ck.bad("window side w must be in 1 .. min(W, L)");
+    if (w * w > kMaxArea) return ck.bad("window area w * w must be at most 1024");
+    if (s < 1) return ck.bad("stride s must be at least 1");
+    if (n < 0 || E < 0) return ck.bad("negative n or E");
     const int Kx = (W - w) / s + 1, Ky = (L - w) / s + 1;
     l.K = (int64_t)Kx * Ky;
-    if (l.K > kMBMaxK) return bad("more windows than BPP_MULTIBIN_MAX_K (256)");
+    if (l.K > kMBMaxK) return ck.bad("more windows than BPP_MULTIBIN_MAX_K (256)");
     l.Ky = Ky;
     l.mstride = (w * w + 15) / 16 * 16;
     l.state = E * l.K * (int64_t)sizeof(MBWin);
@@ -219,25 +204,17 @@ int multibin_layout(int W, int L, int w, int s, int64_t n, int64_t E, const char
 }
 
 // Everything a multi-bin call checks before device work; fills the kernel arguments.
-int multibin_args(const bpp_batch *b, const bpp_multibin *m, const char *who, MBArgs &a) {
-    static thread_local char msg[160];
-    auto bad = [&](const char *what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(BPP_E_BADARG, msg);
-    };
-    if (!b || !m) return bad("NULL pointer");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+int multibin_args(const bpp_batch *b, const bpp_multibin *m, const ArgCheck &ck, MBArgs &a) {
+    int rc = check_search_batch(b, m, ck, "multi-bin packing supports pallets without rotation only", false);
     if (rc) return rc;
-    if (b->rotation) return bad("multi-bin packing supports pallets without rotation only");
-    if (!b->hmap || !b->state) return bad("NULL batch buffer");
     MBLayout l;
-    rc = multibin_layout(b->W, b->L, m->w, m->s, m->n, b->num_envs, who, l);
+    rc = multibin_layout(b->W, b->L, m->w, m->s, m->n, b->num_envs, ck, l);
     if (rc) return rc;
-    if (m->K != l.K) return bad("K does not match the geometry (use bpp_multibin_sizes)");
-    if (m->n > 0 && (!m->ids || !m->work)) return bad("NULL pointer");
-    if (!m->state) return bad("NULL state");
+    if (m->K != l.K) return ck.bad("K does not match the geometry (use bpp_multibin_sizes)");
+    if (m->n > 0 && (!m->ids || !m->work)) return ck.bad("NULL pointer");
+    if (!m->state) return ck.bad("NULL state");
     if (((uintptr_t)m->ids & 7u) || ((uintptr_t)m->state & 7u) || ((uintptr_t)m->work & 15u))
-        return bad("ids / state must be 8-byte aligned, work 16-byte aligned");
+        return ck.bad("ids / state must be 8-byte aligned, work 16-byte aligned");
     a.n = m->n, a.K = (int32_t)l.K, a.Ky = l.Ky, a.w = m->w, a.w2 = m->w * m->w, a.s = m->s, a.mstride = l.mstride;
     a.W = b->W, a.L = b->L, a.H = b->H, a.A = b->W * b->L, a.E = b->num_envs;
     a.bin_num = (double)(b->W * b->L) / (double)(m->w * m->w);   // (plain.shape[0] * plain.shape[1]) / (w * w)
@@ -251,16 +228,15 @@ int multibin_args(const bpp_batch *b, const bpp_multibin *m, const char *who, MB
     return 0;
 }
 
-inline dim3 multibin_grid(int n) { return dim3((unsigned)((n + kMBWaves - 1) / kMBWaves)); }
-
 }  // namespace
 
 extern "C" {
 
 int bpp_multibin_sizes(int32_t W, int32_t L, int32_t w, int32_t s, int32_t n, int32_t E, int64_t out[3]) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_multibin_sizes: NULL pointer");
+    const ArgCheck ck{"bpp_multibin_sizes"};
+    if (!out) return ck.bad("NULL pointer");
     MBLayout l;
-    int rc = multibin_layout(W, L, w, s, n, E, "bpp_multibin_sizes", l);
+    const int rc = multibin_layout(W, L, w, s, n, E, ck, l);
     if (rc) return rc;
     out[0] = l.K;
     out[1] = l.state;
@@ -270,51 +246,41 @@ int bpp_multibin_sizes(int32_t W, int32_t L, int32_t w, int32_t s, int32_t n, in
 
 int bpp_multibin_emit(const bpp_batch *b, const bpp_multibin *m, float *obs, void *stream) {
     MBArgs a;
-    int rc = multibin_args(b, m, "bpp_multibin_emit", a);
-    if (rc) return rc;
-    if (a.n > 0 && !obs) return fail(BPP_E_BADARG, "bpp_multibin_emit: NULL obs");
-    if ((uintptr_t)obs & 15u) return fail(BPP_E_BADARG, "bpp_multibin_emit: obs must be 16-byte aligned");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(multibin_emit_kernel, multibin_grid(a.n), dim3(kWave * kMBWaves), 0, (hipStream_t)stream, a, obs);
-    return reorder_launched();
+    const ArgCheck ck{"bpp_multibin_emit"};
+    if (const int rc = multibin_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && !obs) return ck.bad("NULL obs");
+    if ((uintptr_t)obs & 15u) return ck.bad("obs must be 16-byte aligned");
+    return launch_slots(multibin_emit_kernel, a.n, stream, a, obs);
 }
 
 int bpp_multibin_choose(const bpp_batch *b, const bpp_multibin *m, const float *value, const float *logits, int64_t *action,
                         double *adv, int32_t *window, void *stream) {
     MBArgs a;
-    int rc = multibin_args(b, m, "bpp_multibin_choose", a);
-    if (rc) return rc;
-    if (a.n > 0 && (!value || !logits || !action || !adv || !window)) return fail(BPP_E_BADARG, "bpp_multibin_choose: NULL pointer");
+    const ArgCheck ck{"bpp_multibin_choose"};
+    if (const int rc = multibin_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && (!value || !logits || !action || !adv || !window)) return ck.bad("NULL pointer");
     if (((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)action & 7u) || ((uintptr_t)adv & 7u) ||
         ((uintptr_t)window & 3u))
-        return fail(BPP_E_BADARG, "bpp_multibin_choose: misaligned buffer");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(multibin_choose_kernel, multibin_grid(a.n), dim3(kWave * kMBWaves), 0, (hipStream_t)stream, a, value, logits,
-                       action, adv, window);
-    return reorder_launched();
+        return ck.bad("misaligned buffer");
+    return launch_slots(multibin_choose_kernel, a.n, stream, a, value, logits, action, adv, window);
 }
 
 int bpp_multibin_commit(const bpp_batch *b, const bpp_multibin *m, const uint8_t *step_done, void *stream) {
     MBArgs a;
-    int rc = multibin_args(b, m, "bpp_multibin_commit", a);
-    if (rc) return rc;
-    if (a.n > 0 && !step_done) return fail(BPP_E_BADARG, "bpp_multibin_commit: NULL step_done");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(multibin_commit_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, step_done);
-    return reorder_launched();
+    const ArgCheck ck{"bpp_multibin_commit"};
+    if (const int rc = multibin_args(b, m, ck, a)) return rc;
+    if (a.n > 0 && !step_done) return ck.bad("NULL step_done");
+    return launch_items(multibin_commit_kernel, a.n, stream, a, step_done);
 }
 
 int bpp_multibin_clear(const bpp_batch *b, const bpp_multibin *m, const int64_t *ids, int32_t n, void *stream) {
     MBArgs a;
-    int rc = multibin_args(b, m, "bpp_multibin_clear", a);
-    if (rc) return rc;
+    const ArgCheck ck{"bpp_multibin_clear"};
+    if (const int rc = multibin_args(b, m, ck, a)) return rc;
     if (!ids) n = a.E;
-    if (n < 0) return fail(BPP_E_BADARG, "bpp_multibin_clear: negative n");
-    if ((uintptr_t)ids & 7u) return fail(BPP_E_BADARG, "bpp_multibin_clear: ids must be 8-byte aligned");
-    const int64_t t = (int64_t)n * a.K;
-    if (t == 0) return 0;
-    hipLaunchKernelGGL(multibin_clear_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, ids, n);
-    return reorder_launched();
+    if (n < 0) return ck.bad("negative n");
+    if ((uintptr_t)ids & 7u) return ck.bad("ids must be 8-byte aligned");
+    return launch_items(multibin_clear_kernel, (int64_t)n * a.K, stream, a, ids, n);
 }
 
 }  // extern "C"

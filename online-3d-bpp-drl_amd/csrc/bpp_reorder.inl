@@ -8,7 +8,6 @@
 // start of a launch and written back by lane 0 at its end.
 namespace {
 
-constexpr int kReorderWaves = 4;
 constexpr int kReorderMaxK = BPP_REORDER_MAX_K;
 
 // A tree node (reorder.py:7-56).  max_v = factorial(height) is recomputed from height.
@@ -65,11 +64,6 @@ __device__ __forceinline__ int32_t factorial_i(int h) {
     int32_t f = 1;
     for (int j = 2; j <= h; ++j) f *= j;
     return f;
-}
-
-__device__ __forceinline__ double item_reward(uint32_t it, double binvol) {   // bin3D.get_box_ratio * 10, float64
-    const int vol = (int)(it & 255u) * (int)((it >> 8) & 255u) * (int)((it >> 16) & 255u);
-    return ((double)vol / binvol) * 10.0;
 }
 
 // Node.get_q_value: the first node upwards that holds a value decides.
@@ -155,7 +149,7 @@ __device__ __forceinline__ int commit_search(const ReorderArgs &a, RSlot &s, RNo
         return 0;
     }
     s.res &= ~(1u << idx);                                       // reorder.py:230-242
-    s.cur_value = s.cur_value + item_reward(item, a.binvol);
+    s.cur_value = s.cur_value + volume_reward(item_volume(item), a.binvol);
     if (s.action < 0 && idx == 0) s.action = s.pos;
     s.cur_node = node;
     return 1;
@@ -172,7 +166,7 @@ __device__ __forceinline__ void reorder_commit(const ReorderArgs &a, RSlot &s, i
             const bool done = step_done[i] != 0;
             if (done) s.live = 0;
             else if (s.blevel == a.k - 1) s.nor_exp = s.nor_exp + s.val, s.live = 0;
-            else s.nor_exp = s.nor_exp + item_reward(slot_item(a, i, s.blevel), a.binvol);
+            else s.nor_exp = s.nor_exp + volume_reward(item_volume(slot_item(a, i, s.blevel)), a.binvol);
         }
     } else if (s.pend == 2) {
         int go = 0;
@@ -229,11 +223,9 @@ __device__ __forceinline__ int select_child(const ReorderArgs &a, RSlot &s, RNod
 }
 
 // bpp_reorder_emit: commit the previous level (step_done), then emit level `level` of iteration `iter` (-1: baseline).
-__global__ __launch_bounds__(kWave * kReorderWaves) void reorder_emit_kernel(const ReorderArgs a, int iter, int level,
+__global__ __launch_bounds__(kWave * kSearchWaves) void reorder_emit_kernel(const ReorderArgs a, int iter, int level,
                                                                               const uint8_t *step_done, float *obs) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int i = (int)blockIdx.x * kReorderWaves + (int)(threadIdx.x >> 6);
-    if (i >= a.n) return;
+    SEARCH_SLOT_PROLOGUE(a)
     RSlot s = a.slots[i];
     __builtin_amdgcn_wave_barrier();
     if (step_done) reorder_commit(a, s, i, lane, step_done);
@@ -267,7 +259,7 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_emit_kernel(con
     }
     // the observation row: plane 0 mixed with the masks of the items after idx (get_mixed_obs), planes 1-3 the item
     const int64_t sid64 = a.scratch[i];
-    if ((uint64_t)sid64 >= (uint64_t)a.E) return;               // (never live: s.ok)
+    if (!bin_in_range(sid64, a.E)) return;                       // (never live: s.ok)
     const int sid = (int)sid64;
     const uint32_t it = slot_item(a, i, idx);
     const float fx = (float)(it & 255u), fy = (float)((it >> 8) & 255u), fz = (float)((it >> 16) & 255u);
@@ -289,21 +281,9 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_emit_kernel(con
             h[q] = (float)v;
             sum += v;
         }
-        if ((a.A & 3) == 0) {
-            *(float4 *)(row + c0) = make_float4(h[0], h[1], h[2], h[3]);
-            *(float4 *)(row + a.A + c0) = make_float4(fx, fx, fx, fx);
-            *(float4 *)(row + 2 * a.A + c0) = make_float4(fy, fy, fy, fy);
-            *(float4 *)(row + 3 * a.A + c0) = make_float4(fz, fz, fz, fz);
-        } else {
-            for (int q = 0; q < 4 && c0 + q < a.A; ++q) {
-                row[c0 + q] = h[q];
-                row[a.A + c0 + q] = fx;
-                row[2 * a.A + c0 + q] = fy;
-                row[3 * a.A + c0 + q] = fz;
-            }
-        }
+        store_obs_quad(row, a.A, c0, h, fx, fy, fz);
     }
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, kWave);
+    sum = wave_sum(sum);
     if (lane == 0) {
         a.state[sid].item_cur = it;                              // cur_env.box_creator.box_list = [cur_box, ...]
         s.idx = idx;
@@ -315,12 +295,10 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_emit_kernel(con
 }
 
 // bpp_reorder_choose: model_loader.evaluate(use_mask=True) and the position rule of the row's phase.
-__global__ __launch_bounds__(kWave * kReorderWaves) void reorder_choose_kernel(const ReorderArgs a, const float *value,
+__global__ __launch_bounds__(kWave * kSearchWaves) void reorder_choose_kernel(const ReorderArgs a, const float *value,
                                                                                 const float *logits, const float *pred,
                                                                                 int64_t *actions) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int i = (int)blockIdx.x * kReorderWaves + (int)(threadIdx.x >> 6);
-    if (i >= a.n) return;
+    SEARCH_SLOT_PROLOGUE(a)
     RSlot *sp = a.slots + i;
     const int pend = sp->pend;
     if (pend == 0) {
@@ -329,12 +307,8 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_choose_kernel(c
     }
     const float *lg = logits + (size_t)i * a.A;
     const float *pr = pred ? pred + (size_t)i * a.A : nullptr;
-    float mx = -INFINITY;
-    for (int c = lane; c < a.A; c += kWave) mx = fmaxf(mx, lg[c]);
-    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, kWave));
-    float sum = 0.0f;
-    for (int c = lane; c < a.A; c += kWave) sum += expf(lg[c] - mx);
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, kWave);
+    float mx, sum;
+    row_softmax_stats(lg, a.A, lane, mx, sum);
     // the maximum of softmax * binary(pred): baseline np.argmax (first), search argsort[-1] (last)
     const bool last = pend == 2;
     float best = -1.0f;
@@ -344,11 +318,7 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_choose_kernel(c
         if (pr && !(pr[c] >= 0.5f)) p = 0.0f;
         if (p > best || (last && p == best)) best = p, bi = c;
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ob = __shfl_xor(best, m, kWave);
-        const int oi = __shfl_xor(bi, m, kWave);
-        if (ob > best || (ob == best && (last ? oi > bi : oi < bi))) best = ob, bi = oi;
-    }
+    wave_argmax(best, bi, last);
     if (lane == 0) {
         const double v = (double)value[i];
         sp->val = v;
@@ -358,18 +328,16 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_choose_kernel(c
     }
 }
 
-__global__ __launch_bounds__(kWave * kReorderWaves) void reorder_begin_kernel(const ReorderArgs a) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int i = (int)blockIdx.x * kReorderWaves + (int)(threadIdx.x >> 6);
-    if (i >= a.n) return;
+__global__ __launch_bounds__(kWave * kSearchWaves) void reorder_begin_kernel(const ReorderArgs a) {
+    SEARCH_SLOT_PROLOGUE(a)
     uint8_t *masks = a.masks + (size_t)i * a.k * a.mstride;
     for (int j = 0; j < a.k; ++j)
         for (int c = lane * 4; c < a.A; c += 4 * kWave) *(uint32_t *)(masks + (size_t)j * a.mstride + c) = 0x01010101u;
     if (lane != 0) return;
     RSlot s;
-    const int64_t id = a.ids[i], sid = a.scratch[i];
-    const bool ok = (uint64_t)id < (uint64_t)a.E && (uint64_t)sid < (uint64_t)a.E;
-    const bpp_env_state st = a.state[ok ? id : 0];
+    int id = 0, sid = 0;
+    const bool ok = slot_bins(a, i, id, sid);
+    const bpp_env_state st = a.state[id];
     for (int j = 0; j < kReorderMaxK; ++j)                       // BoxCreator.preview(k): the terminator repeats past the end
         s.items[j] = j < a.k ? a.pool[(size_t)st.seq * a.T + min(st.cursor + j, a.T - 1)] & 0xFFFFFFu : 0u;
     s.nor_exp = 0.0, s.cur_value = 0.0, s.val = 0.0;
@@ -384,10 +352,8 @@ __global__ __launch_bounds__(kWave * kReorderWaves) void reorder_begin_kernel(co
     init_node(a.nodes[(size_t)i * a.max_nodes], -1, -1, a.k - 1);   // Node(None, None, box_num - 1)
 }
 
-__global__ __launch_bounds__(kWave * kReorderWaves) void reorder_commit_kernel(const ReorderArgs a, const uint8_t *step_done) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int i = (int)blockIdx.x * kReorderWaves + (int)(threadIdx.x >> 6);
-    if (i >= a.n) return;
+__global__ __launch_bounds__(kWave * kSearchWaves) void reorder_commit_kernel(const ReorderArgs a, const uint8_t *step_done) {
+    SEARCH_SLOT_PROLOGUE(a)
     RSlot s = a.slots[i];
     __builtin_amdgcn_wave_barrier();
     reorder_commit(a, s, i, lane, step_done);
@@ -451,25 +417,16 @@ ReorderLayout reorder_layout(int64_t n, int k, int A, int64_t max_nodes) {
 }
 
 // Everything a reorder call checks before device work; fills the kernel arguments.
-int reorder_args(const bpp_batch *b, const bpp_reorder *r, const char *who, ReorderArgs &a) {
-    static thread_local char msg[160];
-    auto bad = [&](const char *what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(BPP_E_BADARG, msg);
-    };
-    if (!b || !r) return bad("NULL pointer");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+int reorder_args(const bpp_batch *b, const bpp_reorder *r, const ArgCheck &ck, ReorderArgs &a) {
+    const int rc = check_search_batch(b, r, ck, "the reorder search supports bins without rotation only", true);
     if (rc) return rc;
-    if (b->rotation) return bad("the reorder search supports bins without rotation only");
-    if (b->pool_mode != BPP_POOL_STATIC) return bad("the reorder search needs a static item pool (BPP_POOL_STATIC)");
-    if (!b->seq_pool || !b->hmap || !b->state) return bad("NULL batch buffer");
-    if (r->k < 1 || r->k > kReorderMaxK) return bad("k must be in 1 .. 8");
-    if (r->n < 0) return bad("negative n");
-    if (r->times < 1 || r->times != reorder_iterations(r->k, r->times)) return bad("times must be in 1 .. (k-1)!");
-    if (r->max_nodes < 1) return bad("max_nodes must be positive");
-    if (r->n > 0 && (!r->ids || !r->scratch || !r->work || !r->overflow)) return bad("NULL pointer");
+    if (r->k < 1 || r->k > kReorderMaxK) return ck.bad("k must be in 1 .. 8");
+    if (r->n < 0) return ck.bad("negative n");
+    if (r->times < 1 || r->times != reorder_iterations(r->k, r->times)) return ck.bad("times must be in 1 .. (k-1)!");
+    if (r->max_nodes < 1) return ck.bad("max_nodes must be positive");
+    if (r->n > 0 && (!r->ids || !r->scratch || !r->work || !r->overflow)) return ck.bad("NULL pointer");
     if (((uintptr_t)r->ids & 7u) || ((uintptr_t)r->scratch & 7u) || ((uintptr_t)r->work & 15u) || ((uintptr_t)r->overflow & 3u))
-        return bad("ids / scratch must be 8-byte aligned, work 16-byte aligned, overflow 4-byte aligned");
+        return ck.bad("ids / scratch must be 8-byte aligned, work 16-byte aligned, overflow 4-byte aligned");
     const int A = b->W * b->L;
     const ReorderLayout l = reorder_layout(r->n, r->k, A, r->max_nodes);
     a.n = r->n, a.k = r->k, a.A = A, a.W = b->W, a.L = b->L, a.H = b->H, a.max_nodes = r->max_nodes, a.mstride = l.mstride;
@@ -487,22 +444,16 @@ int reorder_args(const bpp_batch *b, const bpp_reorder *r, const char *who, Reor
     return 0;
 }
 
-int reorder_launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-inline dim3 reorder_grid(int n) { return dim3((unsigned)((n + kReorderWaves - 1) / kReorderWaves)); }
-
 }  // namespace
 
 extern "C" {
 
 int bpp_reorder_sizes(int32_t n, int32_t k, int32_t times, int32_t W, int32_t L, int64_t out[3]) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_reorder_sizes: NULL pointer");
-    if (n < 0 || W <= 0 || L <= 0 || W * L > kMaxArea) return fail(BPP_E_BADARG, "bpp_reorder_sizes: bad n or geometry");
-    if (k < 1 || k > kReorderMaxK) return fail(BPP_E_BADARG, "bpp_reorder_sizes: k must be in 1 .. 8");
-    if (times < 1) return fail(BPP_E_BADARG, "bpp_reorder_sizes: times must be positive");
+    const ArgCheck ck{"bpp_reorder_sizes"};
+    if (!out) return ck.bad("NULL pointer");
+    if (n < 0 || W <= 0 || L <= 0 || W * L > kMaxArea) return ck.bad("bad n or geometry");
+    if (k < 1 || k > kReorderMaxK) return ck.bad("k must be in 1 .. 8");
+    if (times < 1) return ck.bad("times must be positive");
     const int64_t iters = reorder_iterations(k, times);
     const int64_t nodes = reorder_nodes(k, iters);
     out[0] = reorder_layout(n, k, W * L, nodes).total;
@@ -513,61 +464,48 @@ int bpp_reorder_sizes(int32_t n, int32_t k, int32_t times, int32_t W, int32_t L,
 
 int bpp_reorder_begin(const bpp_batch *b, const bpp_reorder *r, void *stream) {
     ReorderArgs a;
-    int rc = reorder_args(b, r, "bpp_reorder_begin", a);
-    if (rc || a.n == 0) return rc;
-    hipLaunchKernelGGL(reorder_begin_kernel, reorder_grid(a.n), dim3(kWave * kReorderWaves), 0, (hipStream_t)stream, a);
-    return reorder_launched();
+    if (const int rc = reorder_args(b, r, ArgCheck{"bpp_reorder_begin"}, a)) return rc;
+    return launch_slots(reorder_begin_kernel, a.n, stream, a);
 }
 
 int bpp_reorder_emit(const bpp_batch *b, const bpp_reorder *r, int32_t iter, int32_t level, const uint8_t *step_done,
                      float *obs, void *stream) {
     ReorderArgs a;
-    int rc = reorder_args(b, r, "bpp_reorder_emit", a);
-    if (rc) return rc;
-    if (iter < -1 || iter >= r->times || level < 0 || level >= r->k) return fail(BPP_E_BADARG, "bpp_reorder_emit: iter / level out of range");
-    if (a.n > 0 && !obs) return fail(BPP_E_BADARG, "bpp_reorder_emit: NULL obs");
-    if ((uintptr_t)obs & 15u) return fail(BPP_E_BADARG, "bpp_reorder_emit: obs must be 16-byte aligned");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(reorder_emit_kernel, reorder_grid(a.n), dim3(kWave * kReorderWaves), 0, (hipStream_t)stream, a, iter, level,
-                       step_done, obs);
-    return reorder_launched();
+    const ArgCheck ck{"bpp_reorder_emit"};
+    if (const int rc = reorder_args(b, r, ck, a)) return rc;
+    if (iter < -1 || iter >= r->times || level < 0 || level >= r->k) return ck.bad("iter / level out of range");
+    if (a.n > 0 && !obs) return ck.bad("NULL obs");
+    if ((uintptr_t)obs & 15u) return ck.bad("obs must be 16-byte aligned");
+    return launch_slots(reorder_emit_kernel, a.n, stream, a, iter, level, step_done, obs);
 }
 
 int bpp_reorder_choose(const bpp_batch *b, const bpp_reorder *r, const float *value, const float *logits, const float *pred,
                        int64_t *actions, void *stream) {
     ReorderArgs a;
-    int rc = reorder_args(b, r, "bpp_reorder_choose", a);
-    if (rc) return rc;
-    if (a.n > 0 && (!value || !logits || !actions)) return fail(BPP_E_BADARG, "bpp_reorder_choose: NULL pointer");
+    const ArgCheck ck{"bpp_reorder_choose"};
+    if (const int rc = reorder_args(b, r, ck, a)) return rc;
+    if (a.n > 0 && (!value || !logits || !actions)) return ck.bad("NULL pointer");
     if (((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)pred & 3u) || ((uintptr_t)actions & 7u))
-        return fail(BPP_E_BADARG, "bpp_reorder_choose: misaligned buffer");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(reorder_choose_kernel, reorder_grid(a.n), dim3(kWave * kReorderWaves), 0, (hipStream_t)stream, a, value, logits,
-                       pred, actions);
-    return reorder_launched();
+        return ck.bad("misaligned buffer");
+    return launch_slots(reorder_choose_kernel, a.n, stream, a, value, logits, pred, actions);
 }
 
 int bpp_reorder_commit(const bpp_batch *b, const bpp_reorder *r, const uint8_t *step_done, void *stream) {
     ReorderArgs a;
-    int rc = reorder_args(b, r, "bpp_reorder_commit", a);
-    if (rc) return rc;
-    if (a.n > 0 && !step_done) return fail(BPP_E_BADARG, "bpp_reorder_commit: NULL step_done");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(reorder_commit_kernel, reorder_grid(a.n), dim3(kWave * kReorderWaves), 0, (hipStream_t)stream, a, step_done);
-    return reorder_launched();
+    const ArgCheck ck{"bpp_reorder_commit"};
+    if (const int rc = reorder_args(b, r, ck, a)) return rc;
+    if (a.n > 0 && !step_done) return ck.bad("NULL step_done");
+    return launch_slots(reorder_commit_kernel, a.n, stream, a, step_done);
 }
 
 int bpp_reorder_finish(const bpp_batch *b, const bpp_reorder *r, int64_t *action, double *value, uint8_t *is_default,
                        void *stream) {
     ReorderArgs a;
-    int rc = reorder_args(b, r, "bpp_reorder_finish", a);
-    if (rc) return rc;
-    if (a.n > 0 && (!action || !value || !is_default)) return fail(BPP_E_BADARG, "bpp_reorder_finish: NULL pointer");
-    if (((uintptr_t)action & 7u) || ((uintptr_t)value & 7u)) return fail(BPP_E_BADARG, "bpp_reorder_finish: misaligned buffer");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(reorder_finish_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, action, value,
-                       is_default);
-    return reorder_launched();
+    const ArgCheck ck{"bpp_reorder_finish"};
+    if (const int rc = reorder_args(b, r, ck, a)) return rc;
+    if (a.n > 0 && (!action || !value || !is_default)) return ck.bad("NULL pointer");
+    if (((uintptr_t)action & 7u) || ((uintptr_t)value & 7u)) return ck.bad("misaligned buffer");
+    return launch_items(reorder_finish_kernel, a.n, stream, a, action, value, is_default);
 }
 
 }  // extern "C"

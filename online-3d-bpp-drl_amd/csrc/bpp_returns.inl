@@ -191,8 +191,7 @@ int bpp_compute_returns(const float *rewards, float *value_preds, const float *n
     } else {
         hipLaunchKernelGGL(returns_kernel<1>, dim3(returns_workgroups(a, 1)), dim3(kReturnsLanes), 0, (hipStream_t)stream, a);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
 int bpp_compute_returns_info(const float *rewards, float *value_preds, const float *next_value, const uint8_t *done, float *masks,

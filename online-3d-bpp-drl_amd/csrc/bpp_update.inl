@@ -319,12 +319,11 @@ int bpp_a2c_loss(const float *logits, const float *location_masks, const int64_t
         case 8: hipLaunchKernelGGL(a2c_loss_kernel<8>, dim3(groups), dim3(256), 0, st, a); break;
         default: hipLaunchKernelGGL(a2c_loss_kernel<0>, dim3(groups), dim3(256), 0, st, a); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    const int rc = launched();
+    if (rc) return rc;
     hipLaunchKernelGGL(a2c_terms_kernel, dim3(1), dim3(kA2cWidth), 0, st, (const double *)workspace, groups, E, M, value_loss_coef,
                        entropy_coef, invalid_coef, mask_coef, terms);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@ reference environment step).  Imported by tests/, __graft_entry__.smoke() and be
 `cpu_baseline` leg, never by the product package.  numpy in, numpy out; no torch.
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -12,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "bpp_oracle.c")
 LIB = os.path.join(HERE, "libbpp_oracle.so")
 HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_abi.h")
+# the restatement includes headers and bpp_gen.inl: every *.h / *.inl of include/ counts, by glob
+DEPS = [SRC] + sorted(f for pat in ("*.h", "*.inl") for f in glob.glob(os.path.join(os.path.dirname(HDR), pat)))
 
 RULE_UTILS, RULE_SPACE = 0, 1
 RESET_INIT, RESET_ADVANCE = 0, 1
@@ -67,8 +70,7 @@ def launch_info(E, size, rotation=False):
 
 def build(force=False):
     """gcc the restatement into oracle/libbpp_oracle.so (no-op when up to date)."""
-    if (not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= os.path.getmtime(SRC)
-            and os.path.getmtime(LIB) >= os.path.getmtime(HDR)):
+    if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
         return LIB
     subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", LIB, SRC, "-lm"])
     return LIB

@@ -4,6 +4,7 @@ emulator (tests/emu/emu_runtime.cpp, tests/emu/hip/hip_runtime.h).  Same C ABI a
 pointers, so the numpy front-end written for the oracle library drives it unchanged: this module is a second
 instance of oracle/oracle.py bound to the emulated library.  Used by the CPU test suite to check kernel
 LOGIC against the oracle without a GPU; it is never imported by the product and measures nothing."""
+import glob
 import importlib.util
 import os
 import subprocess
@@ -11,11 +12,10 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SRC = os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_kernels.hip")
-DEPS = [SRC, os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_tile_kernel.inl"), os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_tile_body.inl"),
-        os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_stream_gen.inl"), os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_heads.inl"), os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_rt_kernels.inl"),
-        os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_stats.inl"), os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_returns.inl"),
-        os.path.join(ROOT, "include", "bpp_rollout.h"), os.path.join(HERE, "emu_runtime.cpp"), os.path.join(HERE, "hip", "hip_runtime.h"),
-        os.path.join(ROOT, "include", "bpp_abi.h"), os.path.join(ROOT, "include", "bpp_gen.inl")]
+# the product's own list (every *.hip / *.inl of csrc/, every *.h / *.inl of include/, by glob) plus the emulator
+DEPS = sorted(f for d, pats in ((os.path.dirname(SRC), ("*.hip", "*.inl")), (os.path.join(ROOT, "include"), ("*.h", "*.inl")))
+              for pat in pats for f in glob.glob(os.path.join(d, pat)))
+DEPS += [os.path.join(HERE, "emu_runtime.cpp"), os.path.join(HERE, "hip", "hip_runtime.h")]
 LIB = os.path.join(HERE, "libbpp_emu.so" if not os.environ.get("BPP_EMU_DEFINES") else
                    "libbpp_emu.so." + "".join(c if c.isalnum() else "_" for c in os.environ["BPP_EMU_DEFINES"]))
 

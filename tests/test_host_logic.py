@@ -152,3 +152,28 @@ def test_step_tensors_over_one_flat_allocation_makes_views_lazily():
     # built from ready tensors (tests, emulator front-end): plain attributes
     t = StepTensors(obs=torch.ones(2, 4), done=torch.zeros(2, dtype=torch.uint8))
     assert t.mask is None and float(t.obs.sum()) == 8.0 and t._flat is None
+
+
+def test_rebuild_lists_hold_every_file_the_kernel_source_includes():
+    """Every file csrc/bpp_kernels.hip reaches through #include "..." (recursively) is a rebuild dependency of the product
+    library and of the emulated one: a list that misses one leaves a stale library in place after an edit of that file."""
+    import os
+    import re
+    import sys
+    from bpp_amd import _lib
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+    import emu_binding
+
+    reached, todo = set(), [os.path.realpath(_lib.SRC)]
+    while todo:
+        f = todo.pop()
+        if f in reached:
+            continue
+        reached.add(f)
+        with open(f) as fh:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
+                todo.append(os.path.realpath(os.path.join(os.path.dirname(f), inc)))
+    assert len(reached) > 20                     # the walk found the .inl files and the headers, not only the source
+    for name, deps in (("_lib.DEPS", _lib.DEPS), ("emu_binding.DEPS", emu_binding.DEPS)):
+        missing = sorted(reached - {os.path.realpath(d) for d in deps})
+        assert not missing, "%s misses %s" % (name, missing)
