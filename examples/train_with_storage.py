@@ -2,13 +2,16 @@
 """The training loop of the reference's main.py:148-185, tensor-native, on a device-resident rollout storage.
 
     python examples/train_with_storage.py --envs 4096 --updates 4
+    python examples/train_with_storage.py --envs 4096 --updates 4 --acktr
 
 Per update: `--steps` lock-steps in which the policy's logits go through bpp_masked_act and `storage.step` lets the step kernel
 write observation, mask, reward and done straight into the storage (no insert, no copy of an environment output); then ONE
 native call for the returns (`storage.compute_returns`, the reference's main.py variant: no GAE, no time limits), the
 reference's five loss terms (acktr/algo/acktr_pipeline.py:45-92: value, action, entropy, invalid-probability and mask-prediction
 loss) with the log-probabilities, entropy and invalid probability from bpp_masked_evaluate, and RMSprop with gradient clipping:
-the reference's own optimiser path with acktr=False.  K-FAC is not part of this example.
+the reference's own optimiser path with acktr=False.  With --acktr the optimiser is bpp_amd.KFACOptimizer and the update adds the
+sampled-Fisher pass of acktr_pipeline.py:68-84, as main.py does by default (`--algorithm acktr`): the Kronecker factors come from
+bpp_kfac_factor, which never writes an im2col patch.
 
 The network is a plain-torch stand-in shaped like the reference's CNNPro (acktr/model.py:265-323) with random weights.
 """
@@ -46,17 +49,21 @@ class ActorCritic(nn.Module):
         return self.actor(x), self.critic(x), torch.sigmoid(self.mask(x))
 
 
-def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True, fused_loss=False):
+def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True, fused_loss=False,
+          acktr=False):
     """Runs `updates` updates; returns one (value_loss, action_loss, dist_entropy, prob_loss, graph_loss) tuple of floats per update.
     fused_loss: the five terms and the gradients at the network's outputs from ONE native call (storage.a2c_loss) instead of
-    bpp_masked_evaluate + torch expressions + their autograd backward."""
+    bpp_masked_evaluate + torch expressions + their autograd backward.  acktr: K-FAC (bpp_amd.KFACOptimizer) with the Fisher pass
+    of acktr_pipeline.py:68-84 instead of RMSprop with gradient clipping."""
+    if acktr and fused_loss:
+        raise ValueError("the Fisher pass needs the log-probabilities in the autograd graph: --acktr goes without --fused-loss")
     dev = torch.device(device)
     size = (10, 10, 10)
     torch.manual_seed(seed)
     env = bpp_amd.BppVecEnv(envs, size, enable_rotation=rotation, pool=bpp_amd.sequences.cut2_pool(size, 1024, seed=seed), device=dev)
     net = ActorCritic(size[0], env.action_space.n).to(dev)
     # acktr/algo/acktr_pipeline.py:33 with acktr=False; coefficients of the reference's defaults
-    optimizer = torch.optim.RMSprop(net.parameters(), lr, eps=1e-5, alpha=0.99)
+    optimizer = bpp_amd.KFACOptimizer(net) if acktr else torch.optim.RMSprop(net.parameters(), lr, eps=1e-5, alpha=0.99)
     value_coef, entropy_coef, invalid_coef, force, max_grad_norm = 0.5, 0.01, 2.0, 0.5 * 10, 0.5
     storage = bpp_amd.RolloutStorage(steps, env, env.observation_space.shape, env.action_space)
     storage.reset(env)                                   # observation and mask of the reset land in slot 0
@@ -85,10 +92,20 @@ def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, see
         value_loss = advantages.pow(2).mean()
         action_loss = -(advantages.detach() * action_log_probs.view(T, N, 1)).mean()
         graph_loss = nn.functional.mse_loss(pred_mask, truth)
+        if acktr and optimizer.steps % optimizer.Ts == 0:                      # sampled Fisher, acktr_pipeline.py:68-84
+            net.zero_grad()
+            pg_fisher_loss = -action_log_probs.mean()
+            sample_values = values + torch.randn(values.size(), device=dev)
+            vf_fisher_loss = -(values - sample_values.detach()).pow(2).mean()
+            fisher_loss = pg_fisher_loss + vf_fisher_loss + graph_loss * 1e-8
+            optimizer.acc_stats = True
+            fisher_loss.backward(retain_graph=True)
+            optimizer.acc_stats = False
         optimizer.zero_grad()
         loss = value_loss * value_coef + action_loss + prob_loss * invalid_coef - dist_entropy * entropy_coef + force * graph_loss
         loss.backward()
-        nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
+        if not acktr:
+            nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
         optimizer.step()
         storage.after_update()
         # the infos scan of main.py:159-162, once per update over the [T][N] slabs the lock-steps filled
@@ -133,8 +150,9 @@ def main():
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--fused-loss", action="store_true", help="loss terms and output gradients from one native call (bpp_amd.a2c_loss)")
+    ap.add_argument("--acktr", action="store_true", help="K-FAC with the sampled-Fisher pass (bpp_amd.KFACOptimizer) instead of RMSprop")
     args = ap.parse_args()
-    train(args.envs, args.steps, args.updates, args.rotation, args.gamma, fused_loss=args.fused_loss)
+    train(args.envs, args.steps, args.updates, args.rotation, args.gamma, fused_loss=args.fused_loss, acktr=args.acktr)
 
 
 if __name__ == "__main__":

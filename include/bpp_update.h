@@ -4,7 +4,7 @@
  * mask-prediction loss), their weighted total, and the gradients of that total with respect to the three network outputs
  * (logits, values, predicted mask).  Every coefficient of the total is known before the backward pass starts, so the
  * gradients need no second visit: one wave per row reads logits, location mask and predicted mask once and writes the two
- * gradient arrays once.  The acktr=False path of the reference; K-FAC is not part of it.
+ * gradient arrays once.  The acktr=False path of the reference (K-FAC: include/bpp_kfac.h).
  *
  * Additive to include/bpp_abi.h (BPP_ABI_VERSION stays 16).  Only libbpp_hip.so exports these symbols.
  */

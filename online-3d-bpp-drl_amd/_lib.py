@@ -23,6 +23,7 @@ MCTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_mcts.h")
 PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
 ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
 UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
+KFAC_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_kfac.h")
 # everything a rebuild depends on, by glob: a new .inl or header counts from the moment it exists
 DEPS = sorted(f for d, pats in ((CSRC, ("*.hip", "*.inl")), (os.path.dirname(HDR), ("*.h", "*.inl")))
               for pat in pats for f in glob.glob(os.path.join(d, pat)))
@@ -59,6 +60,10 @@ ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host", "bpp_compu
 # include/bpp_update.h: the same, for the fused loss of the A2C update
 UPDATE_SYMBOLS = ["bpp_a2c_loss", "bpp_a2c_loss_workspace", "bpp_a2c_loss_info"]
 A2C_TERMS = ("value_loss", "action_loss", "dist_entropy", "prob_loss", "graph_loss", "loss")
+# include/bpp_kfac.h: the same, for the Kronecker factors of K-FAC
+KFAC_SYMBOLS = ["bpp_kfac_factor", "bpp_kfac_factor_workspace", "bpp_kfac_factor_info"]
+KFAC_PATCH, KFAC_ROWS, KFAC_NCHW = 0, 1, 2
+KFAC_INFO = ("D", "R", "tile", "rows_per_split", "splits", "chain")
 
 
 class Batch(ctypes.Structure):
@@ -218,6 +223,24 @@ def bind_update(L):
     return L
 
 
+def bind_kfac(L):
+    """Argument types of the KFAC_SYMBOLS on library handle L."""
+    vp, i32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    geom = ctypes.POINTER(i32)
+    L.bpp_kfac_factor.argtypes = [vp, i32, geom, vp, f64, f64, i32, vp, vp]
+    L.bpp_kfac_factor.restype = ctypes.c_int
+    L.bpp_kfac_factor_workspace.argtypes = [i32, geom]
+    L.bpp_kfac_factor_workspace.restype = ctypes.c_size_t
+    L.bpp_kfac_factor_info.argtypes = [i32, geom, geom]
+    L.bpp_kfac_factor_info.restype = ctypes.c_int
+    return L
+
+
+def kfac_geom(values):
+    """A geom[] argument of the KFAC_SYMBOLS."""
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
 def build(force=False, verbose=False):
     """Compile csrc/bpp_kernels.hip for gfx950 into csrc/libbpp_hip.so (in-tree; no-op when fresh)."""
     if LIB != BUILD_LIB:        # an explicitly chosen build is loaded as it is
@@ -321,6 +344,7 @@ def lib():
         bind_mcts(L)
         bind_rollout(L)
         bind_update(L)
+        bind_kfac(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

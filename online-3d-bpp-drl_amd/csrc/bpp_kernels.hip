@@ -38,6 +38,7 @@
 #include "../../include/bpp_pipeline.h"
 #include "../../include/bpp_rollout.h"
 #include "../../include/bpp_update.h"
+#include "../../include/bpp_kfac.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1964,3 +1965,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_mcts.inl"
 #include "bpp_returns.inl"
 #include "bpp_update.inl"
+#include "bpp_kfac.inl"
