@@ -48,15 +48,22 @@ def load_actor(path, side, n_actions, device, hidden=256):
     return actor.to(device).eval()
 
 
-def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10, 10), policy_device=None, limit=None):
+def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10, 10), policy_device=None, limit=None, native=False):
     """-> dict(ratio float64 [n], counter int32 [n], steps int32 [n], seconds): trajectory i of `dataset` played greedily
-    by the checkpoint, all of them at once.  policy_device: where the network runs (default: the env's device)."""
+    by the checkpoint, all of them at once.  policy_device: where the network runs (default: the env's device).
+    native: the network is bpp_amd.NativePolicy (one fused call per lock-step, logits only) instead of torch layers."""
     dev = torch.device(device)
     pdev = torch.device(policy_device) if policy_device else dev
     pool = bpp_amd.sequences.from_dataset(dataset, size, first_index=0)          # row r = trajectory r
     n = pool.shape[0] if limit is None else min(int(limit), pool.shape[0])
     env = bpp_amd.BppVecEnv(n, size, enable_rotation=rotation, pool=pool, device=dev)    # episode 0 of bin g plays row g
-    actor = load_actor(checkpoint, size[0], env.action_space.n, pdev)
+    if native:
+        policy = bpp_amd.NativePolicy.from_checkpoint(checkpoint, size[0], env.action_space.n).to(pdev)
+
+        def actor(x):
+            return policy(x, want=("logits",))[1]
+    else:
+        actor = load_actor(checkpoint, size[0], env.action_space.n, pdev)
     obs = env.reset()
     mask = env.location_masks
     live = torch.ones(n, dtype=torch.bool, device=dev)
@@ -90,8 +97,9 @@ def main():
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--policy-device", default=None)
+    ap.add_argument("--native", action="store_true", help="run the network as bpp_amd.NativePolicy (one fused call per lock-step)")
     args = ap.parse_args()
-    r = evaluate(args.checkpoint, args.dataset, args.rotation, policy_device=args.policy_device)
+    r = evaluate(args.checkpoint, args.dataset, args.rotation, policy_device=args.policy_device, native=args.native)
     print("%d trajectories in one batch, %d lock-steps, %.2f s: average space utilization %.4f, average put item number %.4f, "
           "completely packed bins %d" % (len(r["ratio"]), r["lock_steps"], r["seconds"], r["ratio"].mean(), r["counter"].mean(),
                                          int((r["ratio"] == 1.0).sum())))

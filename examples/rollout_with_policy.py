@@ -45,12 +45,25 @@ class Actor(nn.Module):
         return self.linear(self.actor(self.share(x)))
 
 
+def native_from_actor(actor, hidden=256):
+    """bpp_amd.NativePolicy with the Actor's weights on the Actor's device; the critic and mask heads, which the Actor does
+    not have, are zeros (ask it for logits only)."""
+    n_actions = actor.linear.out_features
+    sd = {("dist." if k.startswith("linear.") else "base.") + k: v for k, v in actor.state_dict().items()}
+    for name, shape in bpp_amd.policy.layer_shapes(actor.side, hidden, n_actions):
+        sd.setdefault(name + ".weight", torch.zeros(shape))
+        sd.setdefault(name + ".bias", torch.zeros(shape[0]))
+    return bpp_amd.NativePolicy(actor.side, n_actions, hidden, device=actor.linear.weight.device).load_state_dict(sd)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=16384)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--bf16", action="store_true", help="run the policy under bf16 autocast")
+    ap.add_argument("--native", action="store_true",
+                    help="the same network as bpp_amd.NativePolicy: one fused float32 call per lock-step instead of torch layers")
     ap.add_argument("--graph", action="store_true", help="capture one lock-step (policy, masked_act, env step) in a HIP graph and replay it")
     ap.add_argument("--stream", action="store_true",
                     help="endless item supply generated on the device (every bin its own random.Random, nothing replayed) "
@@ -67,6 +80,13 @@ def main():
         pool = bpp_amd.sequences.cut2_pool(size, 4096, seed=0)
         envs = bpp_amd.BppVecEnv(args.envs, size, enable_rotation=args.rotation, pool=pool, device=dev)
     policy = Actor(10, envs.action_space.n).to(dev).eval()
+    if args.native:
+        if args.bf16:
+            raise SystemExit("--native is float32")
+        full = native_from_actor(policy)
+
+        def policy(x, net=full):
+            return net(x, want=("logits",))[1]
     obs = envs.reset()
     masks = envs.location_masks
     stats = bpp_amd.EpisodeStats(dev)

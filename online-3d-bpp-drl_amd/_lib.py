@@ -24,6 +24,7 @@ PIPELINE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_pipeline.h")
 ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
 UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
 KFAC_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_kfac.h")
+POLICY_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy.h")
 # everything a rebuild depends on, by glob: a new .inl or header counts from the moment it exists
 DEPS = sorted(f for d, pats in ((CSRC, ("*.hip", "*.inl")), (os.path.dirname(HDR), ("*.h", "*.inl")))
               for pat in pats for f in glob.glob(os.path.join(d, pat)))
@@ -64,6 +65,9 @@ A2C_TERMS = ("value_loss", "action_loss", "dist_entropy", "prob_loss", "graph_lo
 KFAC_SYMBOLS = ["bpp_kfac_factor", "bpp_kfac_factor_workspace", "bpp_kfac_factor_info"]
 KFAC_PATCH, KFAC_ROWS, KFAC_NCHW = 0, 1, 2
 KFAC_INFO = ("D", "R", "tile", "rows_per_split", "splits", "chain")
+# include/bpp_policy.h: the same, for the CNNPro policy forward
+POLICY_SYMBOLS = ["bpp_policy_forward", "bpp_policy_forward_workspace", "bpp_policy_weights_floats", "bpp_policy_forward_info"]
+POLICY_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "bins_per_head_tile", "head_groups", "tile", "padded_rows", "path")
 
 
 class Batch(ctypes.Structure):
@@ -236,6 +240,21 @@ def bind_kfac(L):
     return L
 
 
+def bind_policy(L):
+    """Argument types of the POLICY_SYMBOLS on library handle L."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    geom = ctypes.POINTER(i32)
+    L.bpp_policy_forward.argtypes = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp, vp, vp]
+    L.bpp_policy_forward.restype = ctypes.c_int
+    L.bpp_policy_forward_workspace.argtypes = [geom, i32]
+    L.bpp_policy_forward_workspace.restype = ctypes.c_size_t
+    L.bpp_policy_weights_floats.argtypes = [geom]
+    L.bpp_policy_weights_floats.restype = ctypes.c_size_t
+    L.bpp_policy_forward_info.argtypes = [geom, i32, geom]
+    L.bpp_policy_forward_info.restype = ctypes.c_int
+    return L
+
+
 def kfac_geom(values):
     """A geom[] argument of the KFAC_SYMBOLS."""
     return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
@@ -345,6 +364,7 @@ def lib():
         bind_rollout(L)
         bind_update(L)
         bind_kfac(L)
+        bind_policy(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

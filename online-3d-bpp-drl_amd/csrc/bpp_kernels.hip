@@ -39,6 +39,7 @@
 #include "../../include/bpp_rollout.h"
 #include "../../include/bpp_update.h"
 #include "../../include/bpp_kfac.h"
+#include "../../include/bpp_policy.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1966,3 +1967,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_returns.inl"
 #include "bpp_update.inl"
 #include "bpp_kfac.inl"
+#include "bpp_policy.inl"

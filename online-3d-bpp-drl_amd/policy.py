@@ -1,0 +1,266 @@
+"""The CNNPro policy of the reference (acktr/model.py:265-323 with dist.linear, acktr/distributions.py:72) for inference as ONE
+native call (include/bpp_policy.h): the five 3x3 layers and the 1x1 head convolutions inside the LDS of a
+workgroup, the Linear layers as products over 64 bins, float32 on the matrix cores.
+
+    policy = bpp_amd.NativePolicy.from_checkpoint(path, side=10, n_actions=env.action_space.n).to("cuda:0")
+    value, logits, pred = policy(obs)                   # the callable ReorderSearch, MultiBinPacker and MCTSearch take
+    value, action, log_prob = policy.act(obs, env.location_masks, deterministic=True)
+
+Inference only: nothing here computes a gradient.  Training runs on torch; `refresh(module)` repacks the weights after an
+optimizer step.  A bin's outputs are the same bits whatever batch it is evaluated in.  CPU tensors go through torch_forward, the
+same layers in plain torch.
+"""
+import ctypes
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from .masks import masked_act
+
+HEADS = ("value", "logits", "pred")
+TRUNK = tuple("base.share.%d" % i for i in (0, 2, 4, 6, 8))
+MAX_SIDE, HIDDEN_STEP, MAX_HIDDEN = 15, 32, 512      # what bpp_policy_forward accepts (include/bpp_policy.h)
+_WORKSPACE = {}     # (device, stream, geom) -> float32 tensor, grown to the largest n asked for
+
+
+def layer_shapes(side, hidden, n_actions):
+    """[(name, weight shape)] of every layer in the order of the packed blob (include/bpp_policy.h); the three 1x1 head
+    convolutions share one matrix there."""
+    A = side * side
+    return ([(TRUNK[0], (64, 4, 3, 3))] + [(name, (64, 64, 3, 3)) for name in TRUNK[1:]] +
+            [("base.actor.0", (8, 64, 1, 1)), ("base.mask.0", (8, 64, 1, 1)), ("base.critic.0", (4, 64, 1, 1)),
+             ("base.actor.3", (hidden, 8 * A)), ("dist.linear", (n_actions, hidden)), ("base.mask.3", (hidden, 8 * A)),
+             ("base.mask.5", (n_actions, hidden)), ("base.critic.3", (hidden, 4 * A)), ("base.critic_linear", (1, hidden))])
+
+
+def plain_weights(state, side, hidden, n_actions, device=None):
+    """{name.weight / name.bias: float32 tensor} under the reference's Policy.state_dict() names and shapes, from any of: those
+    names; the K-FAC-split checkpoint form (`<layer>.module.weight`, `<layer>.add_bias._bias` [C, 1]; main.py:66-76); the
+    output of kfac.plain_state_dict.  device: where every tensor is moved to (the entries of `state` may lie on different
+    devices); None leaves them where they are.  ValueError for a missing layer or a wrong size."""
+    seen = {}
+    for k, v in state.items():
+        seen[k.replace("module.", "").replace("add_bias.", "").replace("_bias", "bias")] = v
+    out = {}
+    for name, shape in layer_shapes(side, hidden, n_actions):
+        for suffix, want in ((".weight", shape), (".bias", shape[:1])):
+            if name + suffix not in seen:
+                raise ValueError("the state dict has no %s%s" % (name, suffix))
+            v = seen[name + suffix].detach().to(device=device, dtype=torch.float32)
+            n = 1
+            for d in want:
+                n *= d
+            if v.numel() != n:
+                raise ValueError("%s%s has %d elements, the network needs %r" % (name, suffix, v.numel(), tuple(want)))
+            out[name + suffix] = v.reshape(want)
+    return out
+
+
+def pack_weights(weights, side, hidden, n_actions):
+    """The float32 blob bpp_policy_forward reads, from plain_weights' output: every matrix [k][oc] (weight.view(OC, -1)
+    transposed) followed by its bias, in layer_shapes' order."""
+    parts = []
+    names = [n for n, _ in layer_shapes(side, hidden, n_actions)]
+
+    def put(ws, bs):
+        w = torch.cat([x.reshape(x.shape[0], -1) for x in ws], 0)
+        parts.extend([w.t().contiguous().reshape(-1), torch.cat([b.reshape(-1) for b in bs], 0)])
+
+    for name in names[:5]:
+        put([weights[name + ".weight"]], [weights[name + ".bias"]])
+    put([weights[n + ".weight"] for n in names[5:8]], [weights[n + ".bias"] for n in names[5:8]])
+    for name in names[8:]:
+        put([weights[name + ".weight"]], [weights[name + ".bias"]])
+    return torch.cat([p.to(torch.float32) for p in parts], 0).contiguous()
+
+
+def unpack_weights(blob, side, hidden, n_actions):
+    """pack_weights backwards: plain tensors per layer."""
+    out, at = {}, 0
+    shapes = layer_shapes(side, hidden, n_actions)
+
+    def take(group):
+        nonlocal at
+        oc = sum(s[0] for _, s in group)
+        k = 1
+        for d in group[0][1][1:]:
+            k *= d
+        w = blob[at:at + k * oc].reshape(k, oc).t()
+        b = blob[at + k * oc:at + (k + 1) * oc]
+        at += (k + 1) * oc
+        c = 0
+        for name, s in group:
+            out[name + ".weight"] = w[c:c + s[0]].reshape(s).contiguous()
+            out[name + ".bias"] = b[c:c + s[0]].contiguous()
+            c += s[0]
+
+    for g in [shapes[i:i + 1] for i in range(5)] + [shapes[5:8]] + [shapes[i:i + 1] for i in range(8, len(shapes))]:
+        take(g)
+    if at != blob.numel():
+        raise ValueError("the blob has %d floats, the network %d" % (blob.numel(), at))
+    return out
+
+
+def torch_forward(weights, obs, want=HEADS):
+    """(value [n], logits [n, M], pred [n, M]) of CNNPro + dist.linear in plain torch, in the dtype and on the device of
+    `weights` (plain_weights' names), None for a head not in `want`: what NativePolicy computes for CPU tensors, and what the
+    tests and tools/bench_policy.py compare against."""
+    w = weights
+    dt = w[TRUNK[0] + ".weight"].dtype
+    A = w["base.actor.3.weight"].shape[1] // 8
+    side = int(round(A ** 0.5))
+    x = obs.to(dt)[:, :4 * A].reshape(-1, 4, side, side)       # CNNPro.forward, acktr/model.py:315-316
+    for name in TRUNK:
+        x = F.relu(F.conv2d(x, w[name + ".weight"], w[name + ".bias"], padding=1))
+
+    def head(name):
+        h = F.relu(F.conv2d(x, w[name + ".0.weight"], w[name + ".0.bias"])).flatten(1)
+        return F.relu(F.linear(h, w[name + ".3.weight"], w[name + ".3.bias"]))
+
+    value = logits = pred = None
+    if "value" in want:
+        value = F.linear(head("base.critic"), w["base.critic_linear.weight"], w["base.critic_linear.bias"]).reshape(-1)
+    if "logits" in want:
+        logits = F.linear(head("base.actor"), w["dist.linear.weight"], w["dist.linear.bias"])
+    if "pred" in want:
+        pred = F.relu(F.linear(head("base.mask"), w["base.mask.5.weight"], w["base.mask.5.bias"]))
+    return value, logits, pred
+
+
+def forward_info(geom, n, L=None):
+    """bpp_policy_forward_info as a dict (_lib.POLICY_INFO)."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check((L or _lib.lib()).bpp_policy_forward_info(_lib.kfac_geom(geom), int(n), out))
+    return dict(zip(_lib.POLICY_INFO, (int(v) for v in out)))
+
+
+def policy_forward(obs, weights, geom, want=HEADS):
+    """(value [n], logits [n, M], pred [n, M]) from bpp_policy_forward, None for a head not in `want`: obs float32 [n, >= 4 A]
+    on a HIP device with contiguous rows (a view of a storage's rows will do), weights the packed blob on the same device,
+    geom = (S, H, M).  Only enqueues on the current stream.
+
+    The workspace is kept per (device, stream, geom) and grown to the largest n asked for.  Inside a stream capture the call
+    takes a workspace of its own from the graph's memory pool, as its outputs are, so a captured call keeps its workspace for as
+    long as the graph lives.  Make one call before capturing: the first call per device opts the kernels in to more than
+    64 KiB of LDS, which is no stream operation and should not happen first inside a capture."""
+    S, H, M = (int(v) for v in geom)
+    want = tuple(want)
+    if not want or any(h not in HEADS for h in want):
+        raise ValueError("want must name at least one of %r" % (HEADS,))
+    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
+        raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
+    if obs.device.type != "cuda":
+        raise RuntimeError("policy_forward needs its tensors on a HIP device")
+    n = int(obs.shape[0])
+    if obs.shape[1] < 4 * S * S or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * S * S):
+        raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * S * S))
+    dev = obs.device
+    g = _lib.kfac_geom((S, H, M))
+    L = _lib.lib()
+    floats = int(L.bpp_policy_weights_floats(g))
+    if floats == 0:
+        _lib.check(L.bpp_policy_forward_info(g, n, (ctypes.c_int32 * 8)()))
+    if (not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.device != dev or not weights.is_contiguous()
+            or weights.numel() != floats):
+        raise ValueError("weights must be the packed float32 blob of %d floats on %s" % (floats, dev))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        need = (int(L.bpp_policy_forward_workspace(g, n)) + 3) // 4
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(need, dtype=torch.float32, device=dev)
+        else:
+            key = (dev, stream, (S, H, M))
+            ws = _WORKSPACE.get(key)
+            if ws is None or ws.numel() < need:
+                ws = _WORKSPACE[key] = torch.empty(need, dtype=torch.float32, device=dev)
+        value = torch.empty(n, dtype=torch.float32, device=dev) if "value" in want else None
+        logits = torch.empty((n, M), dtype=torch.float32, device=dev) if "logits" in want else None
+        pred = torch.empty((n, M), dtype=torch.float32, device=dev) if "pred" in want else None
+        ptr = [t.data_ptr() if t is not None else None for t in (value, logits, pred)]
+        _lib.check(L.bpp_policy_forward(obs.data_ptr(), int(obs.stride(0)) if n > 1 else int(obs.shape[1]), n, g, weights.data_ptr(),
+                                        ptr[0], ptr[1], ptr[2], ws.data_ptr(), ctypes.c_void_p(stream)))
+    return value, logits, pred
+
+
+class NativePolicy:
+    """The reference's Policy(CNNPro) for inference: holds the packed weights, `policy(obs) -> (value [n], logits [n, M],
+    pred [n, M])`, the contract of the searches' `policy` argument.  side: the pallet side S (the image is S x S), n_actions: S * S
+    or 2 S * S, hidden: 256 in the reference.  What the native call refuses is refused here, wherever the tensors live: a side
+    whose two LDS images per bin do not fit (S > 15; 20 x 20), a hidden size that is no multiple of 32 or above 512."""
+
+    def __init__(self, side, n_actions, hidden=256, device=None):
+        self.side, self.n_actions, self.hidden = int(side), int(n_actions), int(hidden)
+        if self.n_actions not in (self.side ** 2, 2 * self.side ** 2):
+            raise ValueError("n_actions must be side^2 or 2 side^2")
+        if not 1 <= self.side <= MAX_SIDE:
+            raise ValueError("side must lie in 1 .. %d: the two LDS images of a bin must fit" % MAX_SIDE)
+        if self.hidden < 1 or self.hidden % HIDDEN_STEP or self.hidden > MAX_HIDDEN:
+            raise ValueError("hidden must be a multiple of %d, at most %d" % (HIDDEN_STEP, MAX_HIDDEN))
+        self.geom = (self.side, self.hidden, self.n_actions)
+        floats = sum(s[0] * (1 + _numel(s[1:])) for _, s in layer_shapes(*self._dims()))
+        self.weights = torch.zeros(floats, dtype=torch.float32, device=device)
+        self._plain = None
+
+    def _dims(self):
+        return self.side, self.hidden, self.n_actions
+
+    @property
+    def device(self):
+        return self.weights.device
+
+    def to(self, device):
+        self.weights = self.weights.to(device)
+        self._plain = None
+        return self
+
+    def load_state_dict(self, state):
+        """Pack a state dict in any of the three forms plain_weights takes; its tensors may lie on any devices."""
+        blob = pack_weights(plain_weights(state, *self._dims(), device=self.weights.device), *self._dims())
+        if blob.numel() != self.weights.numel():
+            raise ValueError("packed %d floats, expected %d" % (blob.numel(), self.weights.numel()))
+        self.weights.copy_(blob)
+        self._plain = None
+        return self
+
+    def refresh(self, module_or_state):
+        """Repack after an optimizer step: a module (its state_dict()) or a state dict."""
+        state = module_or_state.state_dict() if hasattr(module_or_state, "state_dict") else module_or_state
+        return self.load_state_dict(state)
+
+    @classmethod
+    def from_checkpoint(cls, path, side, n_actions, hidden=256, device=None):
+        """A reference checkpoint: the (state_dict, ob_rms) pair main.py:186-191 saves.  Observation statistics are refused."""
+        state, ob_rms = torch.load(path, map_location="cpu", weights_only=False)
+        if ob_rms is not None:
+            raise ValueError("checkpoint carries observation statistics (VecNormalize ob=True); the BPP checkpoints do not")
+        return cls(side, n_actions, hidden, device=device).load_state_dict(state)
+
+    def unpack(self):
+        """{name.weight / name.bias: tensor} of every layer under the reference's names, from the blob."""
+        if self._plain is None:
+            self._plain = unpack_weights(self.weights, *self._dims())
+        return self._plain
+
+    def __call__(self, obs, want=HEADS):
+        if obs.device != self.weights.device:
+            raise ValueError("obs is on %s, the weights on %s" % (obs.device, self.weights.device))
+        obs = obs.reshape(obs.shape[0], -1) if obs.dim() != 2 else obs
+        if obs.device.type != "cuda":
+            with torch.no_grad():
+                return torch_forward(self.unpack(), obs.to(torch.float32), want)
+        return policy_forward(obs if obs.dtype == torch.float32 else obs.to(torch.float32), self.weights, self.geom, want)
+
+    def act(self, obs, location_masks, deterministic=False, **sampler):
+        """Policy.act (acktr/model.py:57-68): (value [n, 1], action int64 [n, 1], action_log_probs [n, 1]); the forward, then
+        bpp_amd.masked_act on its logits (`sampler`: its seed / step / counter / out arguments)."""
+        value, logits, _ = self(obs, want=("value", "logits"))
+        action, logp = masked_act(logits, location_masks, deterministic=deterministic, **sampler)
+        return value.reshape(-1, 1), action, logp
+
+
+def _numel(shape):
+    n = 1
+    for d in shape:
+        n *= d
+    return n
