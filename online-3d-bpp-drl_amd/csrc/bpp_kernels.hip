@@ -8,6 +8,9 @@
 //                                              W*L % 4 == 0 and H <= 22 (bpp_rt_kernels.inl);
 //   * bpp_kernel<VEC,MODE>                     any W*L <= 1024 (also W*L % 4 != 0, H up to 255), the fallback.
 // All three run the per-bin step chain stated once in this file (next_row ... step_outcome).
+// Host side: the helpers in the anonymous namespace (errors: fail / hip_fail / ArgCheck / launched; configure, launch, fill_batch),
+// then the entry points in one extern "C" block; the rollout drivers are bpp_drivers.inl, the searches and the training
+// kernels the files included behind it.
 // Work decomposition of the prefix-image kernels:
 //   * a workgroup of 4 waves owns 4*EPW consecutive bins (EPW = 4 for the 10x10 bin, 1 for 20x20); the
 //     bins of a wave are contiguous in every tensor ([E][A] byte heightmap, [E][4A] observation, [E][M]
@@ -557,7 +560,37 @@ int hip_fail(hipError_t e, const char *what) {
     return (int)e;
 }
 
+// The argument errors of one entry point: "<who>: <what>", BPP_E_BADARG.
+struct ArgCheck {
+    const char *who;
+    int bad(const char *what) const {
+        char msg[sizeof g_err];
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return fail(BPP_E_BADARG, msg);
+    }
+};
+
+// Behind every kernel launch: the launch error, if any.  The one place in the library that reads -- and thereby clears -- the
+// runtime's last error.  what: the failing step's name in the message; NULL: behind a runtime call whose failure has been dealt
+// with, the error it left is only cleared so that it cannot surface at the next launch (nothing is reported, 0).
+int launched(const char *what = "kernel launch") {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess || !what ? 0 : hip_fail(e, what);
+}
+
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// More than 64 KiB of dynamic LDS is opted in to once per kernel AND device: `raised` is the kernel's own set of devices.
+template <typename Kern>
+void raise_dynamic_lds(Kern kernel, std::atomic<uint64_t> &raised, int bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(raised.load(std::memory_order_acquire) & bit)) {
+        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        raised.fetch_or(bit, std::memory_order_release);
+    }
+}
 
 int check_geometry(int E, int W, int L, int H, int rotation, int rule) {
     if (E <= 0 || W <= 0 || L <= 0 || H <= 0) return fail(BPP_E_BADARG, "non-positive size");
@@ -607,6 +640,20 @@ void with_tile_geo(int tile, F &&f) {
         case 1: f(std::integral_constant<int, 1>{}); break;
         case 2: f(std::integral_constant<int, 2>{}); break;
         default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
+
+// f(std::integral_constant<int, P>{}) for the width P the 16-lanes-per-bin kernels (sample_kernel, masked_act_kernel) are
+// compiled for: the smallest of 1, 2, 3, 4, 6, 8 quads per lane that holds per = ceil(M / 4 / 16) of them (callers: per <= 8).
+template <typename F>
+void with_sample_width(int per, F &&f) {
+    switch (per) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: case 6: f(std::integral_constant<int, 6>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
     }
 }
 
@@ -730,15 +777,9 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule, bool tile =
 template <int K, bool ROT, int MODE, bool SUB>
 void launch_fast_rot(const Launch &l, hipStream_t s) {
     auto kern = bpp_fast_kernel<K, ROT, MODE, SUB>;
-    if (l.lds > 64 * 1024) {  // large workgroups: opt in to more than 64 KiB of dynamic LDS, once per kernel AND device
+    if (l.lds > 64 * 1024) {  // large workgroups
         static std::atomic<uint64_t> raised{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            raised.fetch_or(bit, std::memory_order_release);
-        }
+        raise_dynamic_lds(kern, raised, 160 * 1024);
     }
     hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
 }
@@ -822,8 +863,7 @@ int launch(const Launch &l, hipStream_t s) {
         hipLaunchKernelGGL((bpp_kernel<true, MODE, SUB>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
     else
         hipLaunchKernelGGL((bpp_kernel<false, MODE, SUB>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
 int fill_batch(Launch &l, const bpp_batch *b, const bpp_step_out *out, bool need_all) {
@@ -944,200 +984,6 @@ __global__ __launch_bounds__(kWave * kCopyWaves) void copy_bins_kernel(const Cop
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int bpp_abi_version(void) { return BPP_ABI_VERSION; }
-
-const char *bpp_last_error(void) { return g_err; }
-
-int bpp_get_knobs(bpp_knobs *out) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_get_knobs: NULL");
-    *out = current_knobs();
-    return 0;
-}
-
-int bpp_set_knobs(const bpp_knobs *k) {
-    if (!k) return fail(BPP_E_BADARG, "bpp_set_knobs: NULL");
-    if (k->bins_per_wave < 0 || k->bins_per_wave > 64 || k->waves_per_group < 0 || k->waves_per_group > kMaxFastWavesPerBlock)
-        return fail(BPP_E_BADARG, "bpp_set_knobs: bins_per_wave must be 0..64, waves_per_group 0..16");
-    (void)current_knobs();
-    std::lock_guard<std::mutex> lock(g_knob_mutex);
-    g_knobs = *k;
-    return 0;
-}
-
-#ifdef BPP_ENABLE_ABLATION
-// profiling builds only: copy the phase timestamps to the host (n = number of uint64 values, <= 4096 * 16)
-int bpp_debug_stamps(unsigned long long *host_out, int n, int clear) {
-    if (!host_out || n <= 0 || n > kStampWaves * kStampSlots) return fail(BPP_E_BADARG, "bpp_debug_stamps: bad argument");
-    hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyFromSymbol");
-    if (clear) {
-        std::vector<unsigned long long> z((size_t)kStampWaves * kStampSlots, 0ull);
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z.data(), z.size() * 8, 0, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyToSymbol");
-    }
-    return 0;
-}
-#endif
-
-int bpp_launch_info(int32_t E, int32_t W, int32_t L, int32_t H, int32_t rotation, int32_t out[6]) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_launch_info: NULL");
-    int rc = check_geometry(E, W, L, H, rotation, BPP_RULE_UTILS);
-    if (rc) return rc;
-    const Launch l = configure(E, W, L, H, rotation, BPP_RULE_UTILS);
-    out[0] = l.kind;
-    out[1] = l.K;
-    out[2] = l.p.epw;
-    out[3] = l.wpb;
-    out[4] = l.blocks;
-    size_t lds = l.lds;
-    if (l.kind == BPP_KERNEL_TILE) {   // step kernel shape
-        with_tile_geo(l.tile, [&](auto g) {
-            constexpr TileGeoEntry t = kTileGeo[decltype(g)::value];
-            lds = tile_lds_block<t.W, t.L, t.K, t.epw>(l);
-        });
-        out[2] = l.p.epw * l.nit;
-    }
-    out[5] = (int32_t)lds;
-    return 0;
-}
-
-int bpp_limits(int32_t out[2]) {
-    if (!out) return fail(BPP_E_BADARG, "bpp_limits: NULL");
-    out[0] = kMaxArea;
-    out[1] = kMaxDim;
-    return 0;
-}
-
-int bpp_reset(const bpp_batch *b, int32_t mode, const bpp_step_out *out, void *stream) {
-    if (!b) return fail(BPP_E_BADARG, "bpp_reset: NULL batch");
-    if (mode != BPP_RESET_INIT && mode != BPP_RESET_ADVANCE) return fail(BPP_E_BADARG, "bpp_reset: bad mode");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
-    if (rc) return rc;
-    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
-    rc = fill_batch(l, b, out, false);
-    if (rc) return rc;
-    return mode == BPP_RESET_INIT ? launch<kResetInit>(l, (hipStream_t)stream)
-                                  : launch<kResetAdvance>(l, (hipStream_t)stream);
-}
-
-int bpp_step(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out, void *stream) {
-    if (!b || !actions) return fail(BPP_E_BADARG, "bpp_step: NULL pointer");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
-    if (rc) return rc;
-    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
-    rc = fill_batch(l, b, out, true);
-    if (rc) return rc;
-    if (out->next_action && !out->mask) return fail(BPP_E_BADARG, "bpp_step: next_action needs mask");
-    l.p.actions = actions;
-    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;  // the generic kernel has no fused sampler ...
-    rc = launch<kStep>(l, (hipStream_t)stream);
-    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action)  // ... a separate launch draws from the mask it wrote
-        rc = bpp_sample_feasible(out->mask, out->next_action, b->num_envs, b->W * b->L * (1 + b->rotation),
-                                 b->env_id_base, out->sample_seed, out->sample_step, stream);
-    return rc;
-}
-
-int bpp_step_subset(const bpp_batch *b, const int64_t *ids, int32_t n, const int64_t *actions, const bpp_step_out *out,
-                    int32_t *bad_ids, void *stream) {
-    if (!b || !ids || !actions) return fail(BPP_E_BADARG, "bpp_step_subset: NULL pointer");
-    if (n < 0) return fail(BPP_E_BADARG, "bpp_step_subset: negative n");
-    if (((uintptr_t)ids & 7u) || ((uintptr_t)actions & 7u) || ((uintptr_t)bad_ids & 3u))
-        return fail(BPP_E_BADARG, "bpp_step_subset: ids / actions must be 8-byte aligned, bad_ids 4-byte aligned");
-    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
-    if (rc) return rc;
-    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule, false);
-    rc = fill_batch(l, b, out, true);
-    if (rc) return rc;
-    if (out->next_action && !out->mask) return fail(BPP_E_BADARG, "bpp_step_subset: next_action needs mask");
-    if (out->next_action && ((uintptr_t)out->next_action & 7u)) return fail(BPP_E_BADARG, "bpp_step_subset: next_action must be 8-byte aligned");
-    if (n == 0) return 0;
-    l.p.actions = actions;
-    l.p.ids = ids;
-    l.p.bad_ids = bad_ids;
-    l.p.nsub = n;
-    l.blocks = ((n + l.p.epw - 1) / l.p.epw + l.wpb - 1) / l.wpb;     // the grid covers the n slots, not the batch
-    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;     // as in bpp_step: a separate launch draws from the mask
-    rc = launch<kStep, true>(l, (hipStream_t)stream);
-    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action) {
-        hipLaunchKernelGGL(sample_ids_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, out->mask, out->next_action, ids, n,
-                           l.p.M, b->env_id_base, out->sample_seed, out->sample_step);
-        const hipError_t e = hipGetLastError();
-        rc = e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-    }
-    return rc;
-}
-
-int bpp_mask_from_obs(const float *obs, float *mask, int32_t E, int32_t W, int32_t L, int32_t H, int32_t rotation,
-                      int32_t rule, void *stream) {
-    if (!obs || !mask) return fail(BPP_E_BADARG, "bpp_mask_from_obs: NULL pointer");
-    int rc = check_geometry(E, W, L, H, rotation, rule);
-    if (rc) return rc;
-    if (!aligned16(obs) || !aligned16(mask)) return fail(BPP_E_BADARG, "buffers must be 16-byte aligned");
-    Launch l = configure(E, W, L, H, rotation, rule);
-    l.p.obs_in = obs;
-    l.p.mask = mask;
-    return launch<kMaskObs>(l, (hipStream_t)stream);
-}
-
-int bpp_mask_from_hmap(const int32_t *hmap, const int32_t *items, float *mask, int32_t E, int32_t W, int32_t L,
-                       int32_t H, int32_t rotation, int32_t rule, void *stream) {
-    if (!hmap || !items || !mask) return fail(BPP_E_BADARG, "bpp_mask_from_hmap: NULL pointer");
-    int rc = check_geometry(E, W, L, H, rotation, rule);
-    if (rc) return rc;
-    if (!aligned16(hmap) || !aligned16(mask)) return fail(BPP_E_BADARG, "buffers must be 16-byte aligned");
-    Launch l = configure(E, W, L, H, rotation, rule);
-    l.p.hmap_in = hmap;
-    l.p.items_in = items;
-    l.p.mask = mask;
-    return launch<kMaskHmap>(l, (hipStream_t)stream);
-}
-
-int bpp_sample_feasible(const float *mask, int64_t *actions, int32_t E, int32_t M, int64_t env_id_base, uint64_t seed,
-                        uint64_t step, void *stream) {
-    if (!mask || !actions) return fail(BPP_E_BADARG, "bpp_sample_feasible: NULL pointer");
-    if (E <= 0 || M <= 0) return fail(BPP_E_BADARG, "bpp_sample_feasible: non-positive size");
-    hipStream_t st = (hipStream_t)stream;
-    const int nq = M / 4;
-    const int per = (nq + 15) / 16;
-    if (M % 4 == 0 && per <= 8 && (((uintptr_t)mask) & 15u) == 0) {
-        const int blocks = (E + 15) / 16;  // 16 bins per 256-thread block
-#define BPP_SAMPLE(P) hipLaunchKernelGGL(sample_kernel<P>, dim3(blocks), dim3(256), 0, st, mask, actions, E, M, env_id_base, seed, step)
-        switch (per) {
-            case 1: BPP_SAMPLE(1); break;
-            case 2: BPP_SAMPLE(2); break;
-            case 3: BPP_SAMPLE(3); break;
-            case 4: BPP_SAMPLE(4); break;
-            case 5: case 6: BPP_SAMPLE(6); break;
-            default: BPP_SAMPLE(8); break;
-        }
-#undef BPP_SAMPLE
-    } else {
-        hipLaunchKernelGGL(sample_kernel_generic, dim3((E + 3) / 4), dim3(256), 0, st, mask, actions, E, M, env_id_base,
-                           seed, step);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-int bpp_epsilon_override(int64_t *actions, int32_t E, int32_t M, int64_t env_id_base, uint64_t seed, uint64_t step, uint32_t eps_q24,
-                         void *stream) {
-    if (!actions) return fail(BPP_E_BADARG, "bpp_epsilon_override: NULL pointer");
-    if (E <= 0 || M <= 0 || eps_q24 > (1u << 24)) return fail(BPP_E_BADARG, "bpp_epsilon_override: bad size / eps_q24 > 2^24");
-    if (eps_q24 == 0) return 0;
-    hipLaunchKernelGGL(eps_override_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, actions, E, M, env_id_base, seed,
-                       step, eps_q24);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-}  // extern "C" (reopened below: a template cannot have C linkage)
-
-namespace {
-
 // Rows [0, n) split over host threads; fn(k0, k1) returns a status, the maximum is returned.
 template <typename F>
 int run_rows_threaded(int n, int threads, F fn) {
@@ -1156,216 +1002,26 @@ int run_rows_threaded(int n, int threads, F fn) {
     return worst;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bpp_gen_cut2(uint8_t *pool, int32_t *lengths, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H, int32_t bound_lo,
-                 int32_t bound_hi, uint64_t seed0, int32_t threads) {
-    if (!pool || !bpp_gen_cut2_args_ok(n, T, W, L, H, bound_lo, bound_hi))
-        return fail(BPP_E_BADARG, "bpp_gen_cut2: bad argument (bin must exceed bound_hi on some side and bound_lo on none)");
-    // same generator as the device stream (bpp_stream_gen.inl), one private random.Random(seed0 + k) per row
-    const int st = run_rows_threaded(n, threads, [=](int k0, int k1) {
-        std::vector<uint32_t> mt(624);
-        const int maxn = stream_work_entries(W, L, H, bound_lo);
-        std::vector<CutBox> boxes((size_t)maxn);
-        std::vector<uint32_t> cut((size_t)maxn);
-        const uint32_t term = (uint32_t)W | ((uint32_t)L << 8) | ((uint32_t)H << 16);
-        int over = 0;
-        for (int k = k0; k < k1; ++k) {
-            StridedMT rng{mt.data(), 1, 624};
-            rng.seed(seed0 + (uint64_t)k);
-            ArrayWork work{boxes.data()};
-            ArrayVals vals{cut.data()};
-            uint32_t *row = (uint32_t *)pool + (size_t)k * T;
-            const int cnt = cut2_generate(rng, work, vals, W, L, H, bound_lo, bound_hi);
-            const int nw = cnt < T - 1 ? cnt : T - 1;
-            for (int t = 0; t < nw; ++t) row[t] = cut[(size_t)t] & 0x00ffffffu;
-            for (int t = nw; t < T; ++t) row[t] = term;
-            if (lengths) lengths[k] = cnt;
-            over |= cnt > T - 1;
-        }
-        return over;
-    });
-    return st ? fail(BPP_E_TOOLARGE, "bpp_gen_cut2: a sequence does not fit in T-1 entries") : 0;
-}
-
-int bpp_gen_cut1(uint8_t *pool, int32_t *lengths, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H,
-                 const int32_t box_range[6], int32_t rotation, uint64_t seed0, int32_t threads) {
-    if (!pool || !bpp_gen_cut1_args_ok(n, T, W, L, H, box_range) || seed0 + (uint64_t)n > (1ull << 32))
-        return fail(BPP_E_BADARG, "bpp_gen_cut1: bad argument (need low >= 1, high >= 2*low - 1, bin >= low, seeds < 2^32)");
-    int32_t rg[6];
-    memcpy(rg, box_range, sizeof rg);
-    const int st = run_rows_threaded(n, threads, [=](int k0, int k1) {
-        return bpp_gen_cut1_range(pool, lengths, k0, k1, T, W, L, H, rg, rotation != 0, seed0);
-    });
-    if (st == 2) return fail(BPP_E_BADARG, "bpp_gen_cut1: a piece fell below the lower bound (the reference asserts here, cutCreator.py:74)");
-    return st ? fail(BPP_E_TOOLARGE, "bpp_gen_cut1: a sequence does not fit in T-1 entries") : 0;
-}
-
-int bpp_gen_rs(uint8_t *pool, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H, const int32_t *box_set, int32_t n_box,
-               uint64_t seed0, int32_t threads) {
-    if (!pool || !bpp_gen_rs_args_ok(n, T, W, L, H, box_set, n_box) || seed0 + (uint64_t)n > (1ull << 32))
-        return fail(BPP_E_BADARG, "bpp_gen_rs: bad argument (item sides 1..255, seeds < 2^32)");
-    run_rows_threaded(n, threads, [=](int k0, int k1) {
-        bpp_gen_rs_range(pool, k0, k1, T, W, L, H, box_set, n_box, seed0);
-        return 0;
-    });
-    return 0;
-}
-
-}  // extern "C"
-
-namespace {
 int masked_act_launch(const float *logits, const float *mask, int64_t *action, float *log_prob, int32_t E, int32_t M, int64_t env_id_base,
-                      uint64_t seed, uint64_t step, const uint64_t *seed_step, int32_t deterministic, void *stream, const char *who) {
-    if (!logits || !mask || !action) return fail(BPP_E_BADARG, who);
-    if (E <= 0 || M <= 0) return fail(BPP_E_BADARG, who);
+                      uint64_t seed, uint64_t step, const uint64_t *seed_step, int32_t deterministic, void *stream, const ArgCheck &ck) {
+    if (!logits || !mask || !action || E <= 0 || M <= 0) return ck.bad("NULL pointer / non-positive size");
     hipStream_t st = (hipStream_t)stream;
     if (M % 4 != 0 || M > 16 * 8 * 4 || !aligned16(logits) || !aligned16(mask)) {  // wave-per-bin kernel: any M, any alignment
         hipLaunchKernelGGL(masked_act_kernel_generic, dim3((E + 3) / 4), dim3(256), 0, st, logits, mask, action, log_prob, E, M,
                            env_id_base, seed, step, deterministic, seed_step);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+        return launched();
     }
-    const int per = (M / 4 + 15) / 16;
     const int blocks = (E + 15) / 16;
-#define BPP_ACT(P)                                                                                                                     \
-    do {                                                                                                                               \
-        if (deterministic)                                                                                                             \
-            hipLaunchKernelGGL((masked_act_kernel<P, true>), dim3(blocks), dim3(256), 0, st, logits, mask, action, log_prob, E, M, env_id_base, seed, step, seed_step); \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((masked_act_kernel<P, false>), dim3(blocks), dim3(256), 0, st, logits, mask, action, log_prob, E, M, env_id_base, seed, step, seed_step); \
-    } while (0)
-    switch (per) {
-        case 1: BPP_ACT(1); break;
-        case 2: BPP_ACT(2); break;
-        case 3: BPP_ACT(3); break;
-        case 4: BPP_ACT(4); break;
-        case 5: case 6: BPP_ACT(6); break;
-        default: BPP_ACT(8); break;
-    }
-#undef BPP_ACT
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-}  // namespace
-
-extern "C" {
-
-int bpp_masked_act(const float *logits, const float *mask, int64_t *action, float *log_prob, int32_t E, int32_t M,
-                   int64_t env_id_base, uint64_t seed, uint64_t step, int32_t deterministic, void *stream) {
-    return masked_act_launch(logits, mask, action, log_prob, E, M, env_id_base, seed, step, nullptr, deterministic, stream,
-                             "bpp_masked_act: NULL pointer / non-positive size");
-}
-
-int bpp_masked_act_counter(const float *logits, const float *mask, int64_t *action, float *log_prob, int32_t E, int32_t M,
-                           int64_t env_id_base, const uint64_t *seed_step, int32_t deterministic, void *stream) {
-    if (!seed_step) return fail(BPP_E_BADARG, "bpp_masked_act_counter: NULL seed_step");
-    return masked_act_launch(logits, mask, action, log_prob, E, M, env_id_base, 0, 0, seed_step, deterministic, stream,
-                             "bpp_masked_act_counter: NULL pointer / non-positive size");
-}
-
-int bpp_masked_evaluate(const float *logits, const float *mask, const int64_t *action, float *log_prob, float *entropy,
-                        float *bad_prob, int32_t E, int32_t M, void *stream) {
-    if (!logits || !mask || !action || !log_prob || !entropy || !bad_prob) return fail(BPP_E_BADARG, "bpp_masked_evaluate: NULL pointer");
-    if (E <= 0 || M <= 0) return fail(BPP_E_BADARG, "bpp_masked_evaluate: non-positive size");
-    hipLaunchKernelGGL(masked_eval_fwd_kernel, dim3((E + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, mask, action, log_prob,
-                       entropy, bad_prob, E, M);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-int bpp_masked_evaluate_backward(const float *logits, const float *mask, const int64_t *action, const float *g_log_prob,
-                                 const float *g_entropy, const float *g_bad_prob, float *grad_logits, int32_t E, int32_t M,
-                                 void *stream) {
-    if (!logits || !mask || !action || !g_log_prob || !g_entropy || !g_bad_prob || !grad_logits)
-        return fail(BPP_E_BADARG, "bpp_masked_evaluate_backward: NULL pointer");
-    if (E <= 0 || M <= 0) return fail(BPP_E_BADARG, "bpp_masked_evaluate_backward: non-positive size");
-    hipLaunchKernelGGL(masked_eval_bwd_kernel, dim3((E + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, mask, action,
-                       g_log_prob, g_entropy, g_bad_prob, grad_logits, E, M);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-}  // extern "C"
-
-namespace {
-// bpp_rollout_uniform, and a chunk of bpp_rollout_uniform_stream: draw_first = the first action comes from the mask left by the
-// previous reset / step (a standalone bpp_sample_feasible launch that reads the whole mask); every step then draws the next
-// one itself (bpp_step_out.next_action, in place), the last one only with draw_last (then `actions` holds the draw for step
-// step0 + nsteps and the next chunk needs no launch of its own for it).
-int rollout_uniform_steps(const bpp_batch *b, const bpp_step_out *out, int64_t *actions, uint64_t seed, uint64_t step0, int32_t nsteps,
-                          bool draw_first, bool draw_last, void *stream) {
-    const int M = b->W * b->L * (1 + b->rotation);
-    int rc = draw_first ? bpp_sample_feasible(out->mask, actions, b->num_envs, M, b->env_id_base, seed, step0, stream) : 0;
-    for (int t = 0; rc == 0 && t < nsteps; ++t) {
-        bpp_step_out o = *out;
-        o.next_action = (t + 1 < nsteps || draw_last) ? actions : nullptr;
-        o.sample_seed = seed;
-        o.sample_step = step0 + (uint64_t)t + 1;
-        rc = bpp_step(b, actions, &o, stream);
-    }
-    return rc;
-}
-}  // namespace
-
-extern "C" {
-
-int bpp_rollout_uniform(const bpp_batch *b, const bpp_step_out *out, int64_t *actions, uint64_t seed, uint64_t step0,
-                        int32_t nsteps, void *stream) {
-    if (!b || !out || !out->mask || !actions) return fail(BPP_E_BADARG, "bpp_rollout_uniform: NULL pointer");
-    if (nsteps < 0) return fail(BPP_E_BADARG, "bpp_rollout_uniform: negative nsteps");
-    if (nsteps == 0) return 0;
-    return rollout_uniform_steps(b, out, actions, seed, step0, nsteps, true, false, stream);
-}
-
-int bpp_fetch_to_host(const void *device_src, void *host_dst, int64_t nbytes, void *stream) {
-    if (!device_src || !host_dst || nbytes <= 0) return fail(BPP_E_BADARG, "bpp_fetch_to_host: NULL pointer / non-positive size");
-    hipError_t e = hipMemcpyAsync(host_dst, device_src, (size_t)nbytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
-    e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamSynchronize");
-}
-
-int bpp_gather_finished(const uint8_t *done, const double *ep_ret, const double *ratio, const int32_t *ep_len,
-                        const int32_t *counter, int32_t E, void *dev, void *host, int32_t n, void *stream) {
-    if (!done || !ep_ret || !ratio || !ep_len || !counter || !host) return fail(BPP_E_BADARG, "bpp_gather_finished: NULL pointer");
-    if (E <= 0 || n < BPP_GATHER_ENQUEUE_ONLY || n > E) return fail(BPP_E_BADARG, "bpp_gather_finished: bad size");
-    if (n == BPP_GATHER_ENQUEUE_ONLY) {
-        // the eager form: the compaction is only ENQUEUED behind the step (arrays laid out for E entries, straight into mapped host
-        // memory); the caller's one synchronisation of the step covers it and the header then tells how many entries there are
-        if (dev) return fail(BPP_E_BADARG, "bpp_gather_finished: BPP_GATHER_ENQUEUE_ONLY writes into mapped host memory (dev must be NULL)");
-        if ((uintptr_t)host & 7u) return fail(BPP_E_BADARG, "bpp_gather_finished: buffers must be 8-byte aligned");
-        int groups0, chunk0;
-        gather_shape(E, groups0, chunk0);
-        hipLaunchKernelGGL(compact_finished_kernel, dim3(groups0), dim3(kGatherThreads), 0, (hipStream_t)stream, done, ep_ret, ratio, ep_len, counter, E,
-                           (unsigned char *)host, E, chunk0);
-        hipError_t e0 = hipGetLastError();
-        return e0 == hipSuccess ? 0 : hip_fail(e0, "kernel launch");
-    }
-    if (((uintptr_t)dev & 7u) || ((uintptr_t)host & 7u)) return fail(BPP_E_BADARG, "bpp_gather_finished: buffers must be 8-byte aligned");
-    // dev == NULL: `host` is page-locked memory mapped into the device and the kernel writes the arrays there itself
-    // (~200 KB of mostly consecutive stores at 65 536 bins) -- no staging buffer, no copy engine
-    int groups, chunk;
-    gather_shape(E, groups, chunk);
-    hipLaunchKernelGGL(compact_finished_kernel, dim3(groups), dim3(kGatherThreads), 0, (hipStream_t)stream, done, ep_ret, ratio, ep_len, counter, E,
-                       (unsigned char *)(dev ? dev : host), n, chunk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    if (dev) {
-        e = hipMemcpyAsync(host, dev, (size_t)BPP_FINISHED_BYTES(n), hipMemcpyDeviceToHost, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
-    }
-    e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    if (*(const int32_t *)host != n) return fail(BPP_E_BADARG, "bpp_gather_finished: n is not the number of finished bins of this step");
-    return 0;
-}
-
-int bpp_wait(void *stream) {
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamSynchronize");
+    with_sample_width((M / 4 + 15) / 16, [&](auto w) {
+        constexpr int P = decltype(w)::value;
+        if (deterministic)
+            hipLaunchKernelGGL((masked_act_kernel<P, true>), dim3(blocks), dim3(256), 0, st, logits, mask, action, log_prob, E, M, env_id_base,
+                               seed, step, seed_step);
+        else
+            hipLaunchKernelGGL((masked_act_kernel<P, false>), dim3(blocks), dim3(256), 0, st, logits, mask, action, log_prob, E, M, env_id_base,
+                               seed, step, seed_step);
+    });
+    return launched();
 }
 
 // Is the page-locked allocation `p` lies in host-coherent?  (the spin-wait reads data the device wrote as soon as the
@@ -1383,7 +1039,7 @@ bool host_flag_coherent(const void *p) {
     unsigned int flags = 0;
     bool coherent = false;
     if (hipHostGetFlags(&flags, const_cast<void *>(p)) == hipSuccess) coherent = (flags & hipHostMallocNonCoherent) == 0;
-    else (void)hipGetLastError();
+    else (void)launched(nullptr);
     std::lock_guard<std::mutex> lock(m);
     if (seen.size() > 256) seen.clear();
     seen.emplace_back(key, coherent);
@@ -1397,278 +1053,6 @@ inline void cpu_relax() {
     __asm__ __volatile__("yield");
 #endif
 }
-
-int bpp_mark(void *host_flag, uint32_t value, void *stream) {
-    if (!host_flag || ((uintptr_t)host_flag & 3u)) return fail(BPP_E_BADARG, "bpp_mark: NULL / misaligned flag");
-    // the stream memory operation is not offered by this runtime / device (hipErrorNotSupported once): marker kernel from then
-    // on.  Any OTHER error of the call is the caller's (a bad stream ...) and is reported, not hidden behind the fallback.
-    static std::atomic<int> use_kernel{0};
-    if (!use_kernel.load(std::memory_order_relaxed) && host_flag_coherent(host_flag)) {
-        const hipError_t w = hipStreamWriteValue32((hipStream_t)stream, host_flag, value, 0);
-        if (w == hipSuccess) return 0;
-        (void)hipGetLastError();
-        if (w != hipErrorNotSupported) return hip_fail(w, "hipStreamWriteValue32");
-        use_kernel.store(1, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(mark_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (uint32_t *)host_flag, value);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-int bpp_wait_mark(const void *host_flag, uint32_t value, void *stream) {
-    if (!host_flag) return fail(BPP_E_BADARG, "bpp_wait_mark: NULL flag");
-    const uint32_t *f = (const uint32_t *)host_flag;
-    const bool coherent = host_flag_coherent(host_flag);
-    for (uint32_t spins = 1;; ++spins) {
-        if (__atomic_load_n(f, __ATOMIC_ACQUIRE) == value) {
-            if (!coherent) {        // the data the word announces may still sit in the device's caches: let the runtime finish the job
-                const hipError_t q = hipStreamSynchronize((hipStream_t)stream);
-                if (q != hipSuccess) return hip_fail(q, "hipStreamSynchronize");
-            }
-            return 0;
-        }
-        if ((spins & 0xfffu) == 0) {            // every few microseconds: is the stream still alive?
-            hipError_t q = hipStreamQuery((hipStream_t)stream);
-            if (q == hipSuccess) {              // all done and the word not seen yet: synchronise, look once more
-                q = hipStreamSynchronize((hipStream_t)stream);
-                if (q != hipSuccess) return hip_fail(q, "hipStreamSynchronize");
-                if (__atomic_load_n(f, __ATOMIC_ACQUIRE) == value) return 0;
-                return fail(BPP_E_BADARG, "bpp_wait_mark: the stream is idle and the flag does not hold the value (no bpp_mark enqueued?)");
-            }
-            if (q != hipErrorNotReady) return hip_fail(q, "hipStreamQuery");
-        }
-        cpu_relax();
-    }
-}
-
-int bpp_step_dropin(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out, void *fin_host, void *host_flag,
-                    uint32_t value, void *stream) {
-    int rc = bpp_step(b, actions, out, stream);
-    if (rc == 0 && fin_host)
-        rc = bpp_gather_finished(out->done, out->ep_ret, out->ratio, out->ep_len, out->counter, b->num_envs, nullptr, fin_host,
-                                 BPP_GATHER_ENQUEUE_ONLY, stream);
-    if (rc == 0 && host_flag) rc = bpp_mark(host_flag, value, stream);
-    return rc;
-}
-
-int bpp_rollout_uniform_sets(const bpp_batch *b, const bpp_step_out *outs, int32_t nsets, const float *first_mask,
-                             int64_t *actions, uint64_t seed, uint64_t step0, int32_t nsteps, int32_t flags, void *stream) {
-    if (!b || !outs || !actions || nsets < 1) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets: NULL pointer / no output set");
-    if (nsteps < 0) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets: negative nsteps");
-    for (int k = 0; k < nsets; ++k)
-        if (!outs[k].mask) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets: every output set needs a mask");
-    if (nsteps == 0) return 0;
-    const int M = b->W * b->L * (1 + b->rotation);
-    const uint32_t eps = BPP_ROLLOUT_EPS_OF(flags);     // SURVEY 8d's failure-path variant: one tiny launch behind every draw
-    int rc = 0;
-    if (!(flags & BPP_ROLLOUT_CONTINUE)) {
-        if (!first_mask) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets: first_mask needed without BPP_ROLLOUT_CONTINUE");
-        rc = bpp_sample_feasible(first_mask, actions, b->num_envs, M, b->env_id_base, seed, step0, stream);
-        if (rc == 0 && eps) rc = bpp_epsilon_override(actions, b->num_envs, M, b->env_id_base, seed, step0, eps, stream);
-    }
-    for (int t = 0; rc == 0 && t < nsteps; ++t) {
-        bpp_step_out o = outs[t % nsets];
-        o.next_action = actions;           // every lock-step draws the next one's actions, the last one included
-        o.sample_seed = seed;
-        o.sample_step = step0 + (uint64_t)t + 1;
-        rc = bpp_step(b, actions, &o, stream);
-        if (rc == 0 && eps) rc = bpp_epsilon_override(actions, b->num_envs, M, b->env_id_base, seed, step0 + (uint64_t)t + 1, eps, stream);
-    }
-    return rc;
-}
-
-}  // extern "C"
-
-namespace {
-// bpp_pipeline (include/bpp_pipeline.h): the side streams and the fork / join events of the pipelined rollout driver, created and
-// owned by the CALLER like bpp_side -- no per-device state in the library.
-struct Pipeline {
-    int device, max_groups;
-    hipStream_t streams[BPP_PIPELINE_MAX_GROUPS - 1];
-    hipEvent_t fork, join[BPP_PIPELINE_MAX_GROUPS - 1];
-};
-
-template <typename T>
-T *rows_from(T *p, int32_t first, size_t row) {   // NULL stays NULL
-    return p ? p + (size_t)first * row : nullptr;
-}
-}  // namespace
-
-extern "C" {
-
-int bpp_pipeline_plan(int32_t E, int32_t groups, int32_t *first, int32_t *count) {
-    if (!first || !count) return fail(BPP_E_BADARG, "bpp_pipeline_plan: NULL pointer");
-    if (E <= 0 || groups < 1 || groups > BPP_PIPELINE_MAX_GROUPS)
-        return fail(BPP_E_BADARG, "bpp_pipeline_plan: need E > 0 and 1 <= groups <= BPP_PIPELINE_MAX_GROUPS");
-    int n = groups;
-    if (n > E / BPP_PIPELINE_MIN_GROUP) n = E / BPP_PIPELINE_MIN_GROUP;
-    if (n < 1) n = 1;
-    // every group but the last holds E / n bins rounded UP to the alignment; the last one takes the remainder, the smallest share --
-    // where rounding up leaves it below the minimum, one group fewer is made
-    for (;; --n) {
-        const int64_t per = (((int64_t)E + n - 1) / n + BPP_PIPELINE_ALIGN - 1) / BPP_PIPELINE_ALIGN * BPP_PIPELINE_ALIGN;
-        const int64_t last = (int64_t)E - per * (n - 1);
-        if (n > 1 && last < BPP_PIPELINE_MIN_GROUP) continue;
-        for (int g = 0; g < n; ++g) {
-            first[g] = (int32_t)(per * g);
-            count[g] = (int32_t)(g + 1 < n ? per : last);
-        }
-        return n;
-    }
-}
-
-int bpp_pipeline_create(void **pipe, int32_t max_groups) {
-    if (!pipe) return fail(BPP_E_BADARG, "bpp_pipeline_create: NULL pointer");
-    *pipe = nullptr;
-    if (max_groups < 1 || max_groups > BPP_PIPELINE_MAX_GROUPS)
-        return fail(BPP_E_BADARG, "bpp_pipeline_create: need 1 <= max_groups <= BPP_PIPELINE_MAX_GROUPS");
-    Pipeline *pl = new Pipeline();
-    pl->max_groups = max_groups;
-    if (hipGetDevice(&pl->device) != hipSuccess) {
-        delete pl;
-        return fail(BPP_E_BADARG, "bpp_pipeline_create: no current device");
-    }
-    const int ns = max_groups - 1;
-    hipError_t e = hipEventCreateWithFlags(&pl->fork, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        delete pl;
-        return hip_fail(e, "hipEventCreateWithFlags");
-    }
-    for (int k = 0; k < ns; ++k) {
-        const char *what = "hipStreamCreateWithPriority";
-        e = hipStreamCreateWithPriority(&pl->streams[k], hipStreamNonBlocking, 0);      // 0: the default priority
-        if (e == hipSuccess) {
-            what = "hipEventCreateWithFlags";
-            e = hipEventCreateWithFlags(&pl->join[k], hipEventDisableTiming);
-            if (e != hipSuccess) (void)hipStreamDestroy(pl->streams[k]);
-        }
-        if (e != hipSuccess) {
-            for (int j = 0; j < k; ++j) {
-                (void)hipEventDestroy(pl->join[j]);
-                (void)hipStreamDestroy(pl->streams[j]);
-            }
-            (void)hipEventDestroy(pl->fork);
-            delete pl;
-            return hip_fail(e, what);
-        }
-    }
-    *pipe = pl;
-    return 0;
-}
-
-int bpp_pipeline_destroy(void *pipe) {
-    if (!pipe) return 0;
-    Pipeline *pl = (Pipeline *)pipe;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < pl->max_groups - 1; ++k) {
-        (void)hipStreamSynchronize(pl->streams[k]);
-        (void)hipEventDestroy(pl->join[k]);
-        const hipError_t ek = hipStreamDestroy(pl->streams[k]);
-        if (e == hipSuccess) e = ek;
-    }
-    (void)hipEventDestroy(pl->fork);
-    delete pl;
-    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamDestroy");
-}
-
-int bpp_rollout_uniform_sets_pipelined(const bpp_batch *b, const bpp_step_out *outs, int32_t nsets, const float *first_mask,
-                                       int64_t *actions, uint64_t seed, uint64_t step0, int32_t nsteps, int32_t flags,
-                                       void *pipe, int32_t groups, void *stream) {
-    if (!b || !outs || !actions || nsets < 1) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: NULL pointer / no output set");
-    if (nsteps < 0) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: negative nsteps");
-    if (groups < 1 || groups > BPP_PIPELINE_MAX_GROUPS)
-        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: need 1 <= groups <= BPP_PIPELINE_MAX_GROUPS");
-    if (b->pool_mode != BPP_POOL_STATIC || b->seq_cache)
-        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: static pools only (ring rows and the row cache are indexed by local bin)");
-    for (int k = 0; k < nsets; ++k) {
-        if (!outs[k].mask) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: every output set needs a mask");
-        if (outs[k].host_reward || outs[k].host_done)
-            return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: output sets with host_reward / host_done are not split");
-    }
-    if (!(flags & BPP_ROLLOUT_CONTINUE) && !first_mask)
-        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: first_mask needed without BPP_ROLLOUT_CONTINUE");
-    int32_t first[BPP_PIPELINE_MAX_GROUPS], count[BPP_PIPELINE_MAX_GROUPS];
-    const int G = bpp_pipeline_plan(b->num_envs, groups, first, count);
-    if (G < 0) return G;
-    if (G == 1) return bpp_rollout_uniform_sets(b, outs, nsets, first_mask, actions, seed, step0, nsteps, flags, stream);
-    Pipeline *pl = (Pipeline *)pipe;
-    if (!pl) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: more than one group needs a pipe (bpp_pipeline_create)");
-    if (G > pl->max_groups) return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: more groups than the pipe was created for");
-    if (nsteps == 0) return 0;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != pl->device)
-        return fail(BPP_E_BADARG, "bpp_rollout_uniform_sets_pipelined: the pipe belongs to another device than the current one");
-
-    const size_t A = (size_t)b->W * b->L, M = A * (1 + b->rotation);
-    const uint32_t eps = BPP_ROLLOUT_EPS_OF(flags);
-    bpp_batch sub[BPP_PIPELINE_MAX_GROUPS];
-    void *st[BPP_PIPELINE_MAX_GROUPS];
-    std::vector<bpp_step_out> so((size_t)G * nsets);      // [g][k]: output set k seen from group g's first bin
-    for (int g = 0; g < G; ++g) {
-        const int32_t f = first[g];
-        sub[g] = *b;
-        sub[g].num_envs = count[g];
-        sub[g].env_id_base = b->env_id_base + f;
-        sub[g].hmap = rows_from(b->hmap, f, A);
-        sub[g].state = rows_from(b->state, f, 1);
-        sub[g].ep_acc = rows_from(b->ep_acc, f, 4);
-        st[g] = g == 0 ? stream : (void *)pl->streams[g - 1];
-        for (int k = 0; k < nsets; ++k) {
-            bpp_step_out &o = so[(size_t)g * nsets + k];
-            o = outs[k];
-            o.obs = rows_from(o.obs, f, 4 * A);
-            o.mask = rows_from(o.mask, f, M);
-            o.reward = rows_from(o.reward, f, 1);
-            o.done = rows_from(o.done, f, 1);
-            o.counter = rows_from(o.counter, f, 1);
-            o.ratio = rows_from(o.ratio, f, 1);
-            o.ep_ret = rows_from(o.ep_ret, f, 1);
-            o.ep_len = rows_from(o.ep_len, f, 1);
-            o.next_action = actions + f;       // every lock-step draws the next one's actions, the last one included
-            o.sample_seed = seed;
-        }
-    }
-    hipError_t e = hipEventRecord(pl->fork, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-    for (int g = 1; g < G; ++g) {
-        e = hipStreamWaitEvent(pl->streams[g - 1], pl->fork, 0);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");     // nothing is enqueued on a side stream yet
-    }
-    int rc = 0;
-    if (!(flags & BPP_ROLLOUT_CONTINUE))
-        for (int g = 0; rc == 0 && g < G; ++g) {
-            rc = bpp_sample_feasible(first_mask + (size_t)first[g] * M, actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0, st[g]);
-            if (rc == 0 && eps) rc = bpp_epsilon_override(actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0, eps, st[g]);
-        }
-    // interleaved: lock-step t of every group, then t + 1 -- all G queues hold work from the first launch on
-    for (int t = 0; rc == 0 && t < nsteps; ++t)
-        for (int g = 0; rc == 0 && g < G; ++g) {
-            bpp_step_out &o = so[(size_t)g * nsets + t % nsets];
-            o.sample_step = step0 + (uint64_t)t + 1;
-            rc = bpp_step(&sub[g], actions + first[g], &o, st[g]);
-            if (rc == 0 && eps)
-                rc = bpp_epsilon_override(actions + first[g], count[g], (int32_t)M, sub[g].env_id_base, seed, step0 + (uint64_t)t + 1, eps, st[g]);
-        }
-    // join, also behind a failed enqueue: whatever did reach a side stream stays ordered in front of the caller's next work
-    for (int g = 1; g < G; ++g) {
-        e = hipEventRecord(pl->join[g - 1], pl->streams[g - 1]);
-        if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, pl->join[g - 1], 0);
-        if (e != hipSuccess && rc == 0) rc = hip_fail(e, "hipEventRecord / hipStreamWaitEvent");
-    }
-    return rc;
-}
-
-}  // extern "C"
-
-namespace {
-// bpp_side: what the overlapped schedule of bpp_rollout_uniform_stream needs beside the caller's stream -- ONE high-priority stream for
-// the refills and three events -- created and owned by the CALLER (bpp_side_create / bpp_side_destroy; one per env), so that the
-// library keeps no per-device state of its own (rounds 3-4 kept one lazily created set per device behind a mutex).
-struct SideStream {
-    hipStream_t stream;
-    hipEvent_t stepped, refilled[2];
-    int device;
-};
 
 int check_stream(const bpp_stream *s) {
     if (!s || !s->ring || !s->mt || !s->work || !s->gen_next || !s->state) return fail(BPP_E_BADARG, "bpp_stream: NULL pointer");
@@ -1715,32 +1099,7 @@ StreamPlan plan_stream(const bpp_stream *s) {
     p.fast = s->pool_len - 1 - kRowHdr >= p.maxn && s->pool_len <= kSortMaxT && p.cut_lds <= 64 * 1024 && p.sort_lds <= 64 * 1024;
     return p;
 }
-}  // namespace
 
-extern "C" {
-
-int bpp_stream_sizes(const bpp_stream *s, int64_t out[2]) {
-    if (!s || !out) return fail(BPP_E_BADARG, "bpp_stream_sizes: NULL pointer");
-    if (s->num_envs <= 0 || s->depth < 4 || !bpp_gen_cut2_args_ok(1, s->pool_len, s->W, s->L, s->H, s->bound_lo, s->bound_hi))
-        return fail(BPP_E_BADARG, "bpp_stream_sizes: fill in num_envs, depth, pool_len, the bin and the bounds first");
-    if (s->rng != BPP_STREAM_RNG_MT19937 && s->rng != BPP_STREAM_RNG_COUNTER) return fail(BPP_E_BADARG, "bpp_stream_sizes: unknown rng");
-    const StreamPlan p = plan_stream(s);
-    out[0] = (int64_t)(s->rng == BPP_STREAM_RNG_COUNTER ? kCtrRec : kMtRec) * s->num_envs;
-    out[1] = (int64_t)(p.fast_bytes > p.legacy_bytes ? p.fast_bytes : p.legacy_bytes);
-    return 0;
-}
-
-int bpp_stream_init(const bpp_stream *s, void *stream) {
-    int rc = check_stream(s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_init_kernel, dim3((s->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, *s);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
-}
-
-}  // extern "C"
-
-namespace {
 // kmax / urgent: see StreamWork.  The plain kernel always brings every bin to `depth` rows.
 int stream_refill(const bpp_stream *s, void *stream, int kmax, int urgent) {
     int rc = check_stream(s);
@@ -1750,8 +1109,7 @@ int stream_refill(const bpp_stream *s, void *stream, int kmax, int urgent) {
     if (!p.fast || current_knobs().stream_legacy == 1) {
         hipLaunchKernelGGL(stream_refill_kernel, dim3((s->num_envs + kStreamLanes - 1) / kStreamLanes), dim3(kStreamLanes),
                            (size_t)kStreamLdsWords * kStreamLanes * 4, st, *s);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+        return launched();
     }
     unsigned char *base = (unsigned char *)s->work;
     const StreamWork w0{(int32_t *)base, (int32_t *)(base + p.off_jobs), (int32_t *)(base + p.off_target), (int64_t *)(base + p.off_rows),
@@ -1770,8 +1128,7 @@ int stream_refill(const bpp_stream *s, void *stream, int kmax, int urgent) {
         const unsigned grid = (unsigned)(waves < 8192 ? waves : 8192);
         if (p.fb == 4) hipLaunchKernelGGL(stream_cut_rows_kernel<4>, dim3(grid), dim3(64), p.rows_lds, st, *s, w);
         else hipLaunchKernelGGL(stream_cut_rows_kernel<8>, dim3(grid), dim3(64), p.rows_lds, st, *s, w);
-        e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+        return launched();
     }
     const StreamWork &w = w0;
     if (s->rng == BPP_STREAM_RNG_COUNTER) {      // no generator state: nothing to regenerate, the lists are all the LDS a cut wave needs
@@ -1786,143 +1143,448 @@ int stream_refill(const bpp_stream *s, void *stream, int kmax, int urgent) {
     }
     const int64_t most = ((int64_t)E * s->depth + 3) / 4;
     hipLaunchKernelGGL(stream_sort_kernel, dim3((unsigned)(most < 2048 ? most : 2048)), dim3(256), p.sort_lds, st, *s, w);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
+
 }  // namespace
 
 extern "C" {
 
-int bpp_stream_refill(const bpp_stream *s, void *stream) { return stream_refill(s, stream, 0, 0); }
+int bpp_abi_version(void) { return BPP_ABI_VERSION; }
 
-int bpp_side_create(void **side) {
-    if (!side) return fail(BPP_E_BADARG, "bpp_side_create: NULL pointer");
-    *side = nullptr;
-    SideStream *ss = new SideStream();
-    if (hipGetDevice(&ss->device) != hipSuccess) {
-        delete ss;
-        return fail(BPP_E_BADARG, "bpp_side_create: no current device");
-    }
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    // (a CU mask on this stream -- refills confined to 32 .. 128 CUs so that the others keep all their workgroup slots
-    // for the step kernel -- was measured: 0.33 - 0.74 G env steps/s against 1.17 - 1.28 G without, the refill becomes
-    // the critical path)
-    hipError_t e = hipStreamCreateWithPriority(&ss->stream, hipStreamNonBlocking, greatest);
-    if (e != hipSuccess) {
-        delete ss;
-        return hip_fail(e, "hipStreamCreateWithPriority");
-    }
-    hipEvent_t *ev[3] = {&ss->stepped, &ss->refilled[0], &ss->refilled[1]};
-    for (int k = 0; k < 3; ++k) {
-        e = hipEventCreateWithFlags(ev[k], hipEventDisableTiming);
-        if (e != hipSuccess) {
-            for (int j = 0; j < k; ++j) (void)hipEventDestroy(*ev[j]);
-            (void)hipStreamDestroy(ss->stream);
-            delete ss;
-            return hip_fail(e, "hipEventCreateWithFlags");
-        }
-    }
-    *side = ss;
+const char *bpp_last_error(void) { return g_err; }
+
+int bpp_get_knobs(bpp_knobs *out) {
+    if (!out) return ArgCheck{"bpp_get_knobs"}.bad("NULL");
+    *out = current_knobs();
     return 0;
 }
 
-int bpp_side_destroy(void *side) {
-    if (!side) return 0;
-    SideStream *ss = (SideStream *)side;
-    (void)hipStreamSynchronize(ss->stream);
-    (void)hipEventDestroy(ss->stepped);
-    (void)hipEventDestroy(ss->refilled[0]);
-    (void)hipEventDestroy(ss->refilled[1]);
-    hipError_t e = hipStreamDestroy(ss->stream);
-    delete ss;
-    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamDestroy");
+int bpp_set_knobs(const bpp_knobs *k) {
+    const ArgCheck ck{"bpp_set_knobs"};
+    if (!k) return ck.bad("NULL");
+    if (k->bins_per_wave < 0 || k->bins_per_wave > 64 || k->waves_per_group < 0 || k->waves_per_group > kMaxFastWavesPerBlock)
+        return ck.bad("bins_per_wave must be 0..64, waves_per_group 0..16");
+    (void)current_knobs();
+    std::lock_guard<std::mutex> lock(g_knob_mutex);
+    g_knobs = *k;
+    return 0;
 }
 
-int bpp_rollout_uniform_stream(const bpp_batch *b, const bpp_step_out *out, int64_t *actions, uint64_t seed, uint64_t step0,
-                               int32_t nsteps, const bpp_stream *s, int32_t refill_every, void *side_handle, void *stream) {
-    if (!b || !s || !out || !out->mask || !actions) return fail(BPP_E_BADARG, "bpp_rollout_uniform_stream: NULL pointer");
-    if (nsteps < 0) return fail(BPP_E_BADARG, "bpp_rollout_uniform_stream: negative nsteps");
-    const int behind = b->seq_cache ? 4 : 3;   // rows a step launch may touch from the current one on (a cache line refers to the row after next)
-    if (b->pool_mode != BPP_POOL_RING || refill_every < 1 || refill_every > s->depth - behind)
-        return fail(BPP_E_BADARG, "bpp_rollout_uniform_stream: needs a ring pool and 1 <= refill_every <= depth - 3 (- 4 with seq_cache)");
-    int rc = 0;
-    // (3 below stands for `behind`.)  With depth >= 2 R + 3 rows per bin the refill that follows a chunk of R lock-steps may run BESIDE the next chunk
-    // (it only rewrites rows of finished episodes): it goes to a side stream, and a chunk starts once the refill issued two
-    // chunks earlier is complete.  Margin m = rows a bin has from its current episode on when a refill scans it (the
-    // previous refill is complete by then: same stream).  A bin advances by at most R episodes per chunk and a step reads
-    // two rows ahead, so it needs m >= R + 3 to get through the chunk that runs beside the refill and m + need >= 2 R + 3
-    // to get through the one after (this refill complete, the next one running).  The scan guarantees the second
-    // (need >= 2 R + 3 - m, `urgent`), which also gives the first for the next scan: m' >= m + need - R >= R + 3.
-    SideStream *side = (current_knobs().stream_overlap && s->depth >= 2 * refill_every + behind) ? (SideStream *)side_handle : nullptr;
-    hipStream_t main = (hipStream_t)stream;
-    if (side) {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev != side->device)
-            return fail(BPP_E_BADARG, "bpp_rollout_uniform_stream: the bpp_side was created on another device");
+#ifdef BPP_ENABLE_ABLATION
+// profiling builds only: copy the phase timestamps to the host (n = number of uint64 values, <= 4096 * 16)
+int bpp_debug_stamps(unsigned long long *host_out, int n, int clear) {
+    const ArgCheck ck{"bpp_debug_stamps"};
+    if (!host_out || n <= 0 || n > kStampWaves * kStampSlots) return ck.bad("bad argument");
+    hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyFromSymbol");
+    if (clear) {
+        std::vector<unsigned long long> z((size_t)kStampWaves * kStampSlots, 0ull);
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z.data(), z.size() * 8, 0, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyToSymbol");
     }
-    int32_t chunk = 0;
-    for (int32_t done = 0; rc == 0 && done < nsteps; done += refill_every, ++chunk) {
-        const int32_t n = nsteps - done < refill_every ? nsteps - done : refill_every;
-        if (side && chunk >= 2) (void)hipStreamWaitEvent(main, side->refilled[chunk & 1], 0);
-        // only the first chunk draws its first action with a launch of its own: the last step of every chunk but the last draws
-        // the next chunk's (the refill in between touches no mask) -- a sampler launch reads the whole mask, 8 / 50 us for 10x10 / 20x20
-        rc = rollout_uniform_steps(b, out, actions, seed, step0 + (uint64_t)done, n, chunk == 0, done + n < nsteps, stream);
-        if (rc) break;
-        if (!side) {
-            rc = bpp_stream_refill(s, stream);
-            continue;
-        }
-        (void)hipEventRecord(side->stepped, main);
-        (void)hipStreamWaitEvent(side->stream, side->stepped, 0);
-        // beside the lock-steps a short refill matters more than a full ring: a bin gets about twice what the average
-        // bin uses in refill_every lock-steps (one sequence per ~9), more only if it would otherwise run out before the
-        // refill after the next one is complete
-        rc = stream_refill(s, side->stream, refill_every < 7 ? 2 : (refill_every + 5) / 6, 2 * refill_every + behind);
-        (void)hipEventRecord(side->refilled[chunk & 1], side->stream);
+    return 0;
+}
+#endif
+
+int bpp_launch_info(int32_t E, int32_t W, int32_t L, int32_t H, int32_t rotation, int32_t out[6]) {
+    const ArgCheck ck{"bpp_launch_info"};
+    if (!out) return ck.bad("NULL");
+    int rc = check_geometry(E, W, L, H, rotation, BPP_RULE_UTILS);
+    if (rc) return rc;
+    const Launch l = configure(E, W, L, H, rotation, BPP_RULE_UTILS);
+    out[0] = l.kind;
+    out[1] = l.K;
+    out[2] = l.p.epw;
+    out[3] = l.wpb;
+    out[4] = l.blocks;
+    size_t lds = l.lds;
+    if (l.kind == BPP_KERNEL_TILE) {   // step kernel shape
+        with_tile_geo(l.tile, [&](auto g) {
+            constexpr TileGeoEntry t = kTileGeo[decltype(g)::value];
+            lds = tile_lds_block<t.W, t.L, t.K, t.epw>(l);
+        });
+        out[2] = l.p.epw * l.nit;
     }
-    if (side) {     // everything enqueued on `stream` after this call sees the refilled ring
-        if (chunk >= 2) (void)hipStreamWaitEvent(main, side->refilled[chunk & 1], 0);
-        if (chunk >= 1) (void)hipStreamWaitEvent(main, side->refilled[(chunk - 1) & 1], 0);
-        hipError_t e = hipGetLastError();
-        if (rc == 0 && e != hipSuccess) rc = hip_fail(e, "side-stream refill");
-        if (rc == 0) rc = bpp_stream_refill(s, stream);     // leave every bin with `depth` rows, as the serial schedule does
+    out[5] = (int32_t)lds;
+    return 0;
+}
+
+int bpp_limits(int32_t out[2]) {
+    const ArgCheck ck{"bpp_limits"};
+    if (!out) return ck.bad("NULL");
+    out[0] = kMaxArea;
+    out[1] = kMaxDim;
+    return 0;
+}
+
+int bpp_reset(const bpp_batch *b, int32_t mode, const bpp_step_out *out, void *stream) {
+    const ArgCheck ck{"bpp_reset"};
+    if (!b) return ck.bad("NULL batch");
+    if (mode != BPP_RESET_INIT && mode != BPP_RESET_ADVANCE) return ck.bad("bad mode");
+    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    if (rc) return rc;
+    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    rc = fill_batch(l, b, out, false);
+    if (rc) return rc;
+    return mode == BPP_RESET_INIT ? launch<kResetInit>(l, (hipStream_t)stream)
+                                  : launch<kResetAdvance>(l, (hipStream_t)stream);
+}
+
+int bpp_step(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out, void *stream) {
+    const ArgCheck ck{"bpp_step"};
+    if (!b || !actions) return ck.bad("NULL pointer");
+    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    if (rc) return rc;
+    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    rc = fill_batch(l, b, out, true);
+    if (rc) return rc;
+    if (out->next_action && !out->mask) return ck.bad("next_action needs mask");
+    l.p.actions = actions;
+    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;  // the generic kernel has no fused sampler ...
+    rc = launch<kStep>(l, (hipStream_t)stream);
+    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action)  // ... a separate launch draws from the mask it wrote
+        rc = bpp_sample_feasible(out->mask, out->next_action, b->num_envs, b->W * b->L * (1 + b->rotation),
+                                 b->env_id_base, out->sample_seed, out->sample_step, stream);
+    return rc;
+}
+
+int bpp_step_subset(const bpp_batch *b, const int64_t *ids, int32_t n, const int64_t *actions, const bpp_step_out *out,
+                    int32_t *bad_ids, void *stream) {
+    const ArgCheck ck{"bpp_step_subset"};
+    if (!b || !ids || !actions) return ck.bad("NULL pointer");
+    if (n < 0) return ck.bad("negative n");
+    if (((uintptr_t)ids & 7u) || ((uintptr_t)actions & 7u) || ((uintptr_t)bad_ids & 3u))
+        return ck.bad("ids / actions must be 8-byte aligned, bad_ids 4-byte aligned");
+    int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
+    if (rc) return rc;
+    Launch l = configure(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule, false);
+    rc = fill_batch(l, b, out, true);
+    if (rc) return rc;
+    if (out->next_action && !out->mask) return ck.bad("next_action needs mask");
+    if (out->next_action && ((uintptr_t)out->next_action & 7u)) return ck.bad("next_action must be 8-byte aligned");
+    if (n == 0) return 0;
+    l.p.actions = actions;
+    l.p.ids = ids;
+    l.p.bad_ids = bad_ids;
+    l.p.nsub = n;
+    l.blocks = ((n + l.p.epw - 1) / l.p.epw + l.wpb - 1) / l.wpb;     // the grid covers the n slots, not the batch
+    if (l.kind == BPP_KERNEL_CELLSCAN) l.p.next_action = nullptr;     // as in bpp_step: a separate launch draws from the mask
+    rc = launch<kStep, true>(l, (hipStream_t)stream);
+    if (rc == 0 && l.kind == BPP_KERNEL_CELLSCAN && out->next_action) {
+        hipLaunchKernelGGL(sample_ids_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, out->mask, out->next_action, ids, n,
+                           l.p.M, b->env_id_base, out->sample_seed, out->sample_step);
+        rc = launched();
     }
     return rc;
 }
 
+int bpp_mask_from_obs(const float *obs, float *mask, int32_t E, int32_t W, int32_t L, int32_t H, int32_t rotation,
+                      int32_t rule, void *stream) {
+    const ArgCheck ck{"bpp_mask_from_obs"};
+    if (!obs || !mask) return ck.bad("NULL pointer");
+    int rc = check_geometry(E, W, L, H, rotation, rule);
+    if (rc) return rc;
+    if (!aligned16(obs) || !aligned16(mask)) return fail(BPP_E_BADARG, "buffers must be 16-byte aligned");
+    Launch l = configure(E, W, L, H, rotation, rule);
+    l.p.obs_in = obs;
+    l.p.mask = mask;
+    return launch<kMaskObs>(l, (hipStream_t)stream);
+}
+
+int bpp_mask_from_hmap(const int32_t *hmap, const int32_t *items, float *mask, int32_t E, int32_t W, int32_t L,
+                       int32_t H, int32_t rotation, int32_t rule, void *stream) {
+    const ArgCheck ck{"bpp_mask_from_hmap"};
+    if (!hmap || !items || !mask) return ck.bad("NULL pointer");
+    int rc = check_geometry(E, W, L, H, rotation, rule);
+    if (rc) return rc;
+    if (!aligned16(hmap) || !aligned16(mask)) return fail(BPP_E_BADARG, "buffers must be 16-byte aligned");
+    Launch l = configure(E, W, L, H, rotation, rule);
+    l.p.hmap_in = hmap;
+    l.p.items_in = items;
+    l.p.mask = mask;
+    return launch<kMaskHmap>(l, (hipStream_t)stream);
+}
+
+int bpp_sample_feasible(const float *mask, int64_t *actions, int32_t E, int32_t M, int64_t env_id_base, uint64_t seed,
+                        uint64_t step, void *stream) {
+    const ArgCheck ck{"bpp_sample_feasible"};
+    if (!mask || !actions) return ck.bad("NULL pointer");
+    if (E <= 0 || M <= 0) return ck.bad("non-positive size");
+    hipStream_t st = (hipStream_t)stream;
+    const int nq = M / 4;
+    const int per = (nq + 15) / 16;
+    if (M % 4 == 0 && per <= 8 && (((uintptr_t)mask) & 15u) == 0) {
+        const int blocks = (E + 15) / 16;  // 16 bins per 256-thread block
+        with_sample_width(per, [&](auto w) {
+            hipLaunchKernelGGL(sample_kernel<decltype(w)::value>, dim3(blocks), dim3(256), 0, st, mask, actions, E, M, env_id_base, seed, step);
+        });
+    } else {
+        hipLaunchKernelGGL(sample_kernel_generic, dim3((E + 3) / 4), dim3(256), 0, st, mask, actions, E, M, env_id_base,
+                           seed, step);
+    }
+    return launched();
+}
+
+int bpp_epsilon_override(int64_t *actions, int32_t E, int32_t M, int64_t env_id_base, uint64_t seed, uint64_t step, uint32_t eps_q24,
+                         void *stream) {
+    const ArgCheck ck{"bpp_epsilon_override"};
+    if (!actions) return ck.bad("NULL pointer");
+    if (E <= 0 || M <= 0 || eps_q24 > (1u << 24)) return ck.bad("bad size / eps_q24 > 2^24");
+    if (eps_q24 == 0) return 0;
+    hipLaunchKernelGGL(eps_override_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, actions, E, M, env_id_base, seed,
+                       step, eps_q24);
+    return launched();
+}
+
+int bpp_gen_cut2(uint8_t *pool, int32_t *lengths, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H, int32_t bound_lo,
+                 int32_t bound_hi, uint64_t seed0, int32_t threads) {
+    const ArgCheck ck{"bpp_gen_cut2"};
+    if (!pool || !bpp_gen_cut2_args_ok(n, T, W, L, H, bound_lo, bound_hi))
+        return ck.bad("bad argument (bin must exceed bound_hi on some side and bound_lo on none)");
+    // same generator as the device stream (bpp_stream_gen.inl), one private random.Random(seed0 + k) per row
+    const int st = run_rows_threaded(n, threads, [=](int k0, int k1) {
+        std::vector<uint32_t> mt(624);
+        const int maxn = stream_work_entries(W, L, H, bound_lo);
+        std::vector<CutBox> boxes((size_t)maxn);
+        std::vector<uint32_t> cut((size_t)maxn);
+        const uint32_t term = (uint32_t)W | ((uint32_t)L << 8) | ((uint32_t)H << 16);
+        int over = 0;
+        for (int k = k0; k < k1; ++k) {
+            StridedMT rng{mt.data(), 1, 624};
+            rng.seed(seed0 + (uint64_t)k);
+            ArrayWork work{boxes.data()};
+            ArrayVals vals{cut.data()};
+            uint32_t *row = (uint32_t *)pool + (size_t)k * T;
+            const int cnt = cut2_generate(rng, work, vals, W, L, H, bound_lo, bound_hi);
+            const int nw = cnt < T - 1 ? cnt : T - 1;
+            for (int t = 0; t < nw; ++t) row[t] = cut[(size_t)t] & 0x00ffffffu;
+            for (int t = nw; t < T; ++t) row[t] = term;
+            if (lengths) lengths[k] = cnt;
+            over |= cnt > T - 1;
+        }
+        return over;
+    });
+    return st ? fail(BPP_E_TOOLARGE, "bpp_gen_cut2: a sequence does not fit in T-1 entries") : 0;
+}
+
+int bpp_gen_cut1(uint8_t *pool, int32_t *lengths, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H,
+                 const int32_t box_range[6], int32_t rotation, uint64_t seed0, int32_t threads) {
+    const ArgCheck ck{"bpp_gen_cut1"};
+    if (!pool || !bpp_gen_cut1_args_ok(n, T, W, L, H, box_range) || seed0 + (uint64_t)n > (1ull << 32))
+        return ck.bad("bad argument (need low >= 1, high >= 2*low - 1, bin >= low, seeds < 2^32)");
+    int32_t rg[6];
+    memcpy(rg, box_range, sizeof rg);
+    const int st = run_rows_threaded(n, threads, [=](int k0, int k1) {
+        return bpp_gen_cut1_range(pool, lengths, k0, k1, T, W, L, H, rg, rotation != 0, seed0);
+    });
+    if (st == 2) return ck.bad("a piece fell below the lower bound (the reference asserts here, cutCreator.py:74)");
+    return st ? fail(BPP_E_TOOLARGE, "bpp_gen_cut1: a sequence does not fit in T-1 entries") : 0;
+}
+
+int bpp_gen_rs(uint8_t *pool, int32_t n, int32_t T, int32_t W, int32_t L, int32_t H, const int32_t *box_set, int32_t n_box,
+               uint64_t seed0, int32_t threads) {
+    const ArgCheck ck{"bpp_gen_rs"};
+    if (!pool || !bpp_gen_rs_args_ok(n, T, W, L, H, box_set, n_box) || seed0 + (uint64_t)n > (1ull << 32))
+        return ck.bad("bad argument (item sides 1..255, seeds < 2^32)");
+    run_rows_threaded(n, threads, [=](int k0, int k1) {
+        bpp_gen_rs_range(pool, k0, k1, T, W, L, H, box_set, n_box, seed0);
+        return 0;
+    });
+    return 0;
+}
+
+int bpp_masked_act(const float *logits, const float *mask, int64_t *action, float *log_prob, int32_t E, int32_t M,
+                   int64_t env_id_base, uint64_t seed, uint64_t step, int32_t deterministic, void *stream) {
+    return masked_act_launch(logits, mask, action, log_prob, E, M, env_id_base, seed, step, nullptr, deterministic, stream,
+                             ArgCheck{"bpp_masked_act"});
+}
+
+int bpp_masked_act_counter(const float *logits, const float *mask, int64_t *action, float *log_prob, int32_t E, int32_t M,
+                           int64_t env_id_base, const uint64_t *seed_step, int32_t deterministic, void *stream) {
+    const ArgCheck ck{"bpp_masked_act_counter"};
+    if (!seed_step) return ck.bad("NULL seed_step");
+    return masked_act_launch(logits, mask, action, log_prob, E, M, env_id_base, 0, 0, seed_step, deterministic, stream, ck);
+}
+
+int bpp_masked_evaluate(const float *logits, const float *mask, const int64_t *action, float *log_prob, float *entropy,
+                        float *bad_prob, int32_t E, int32_t M, void *stream) {
+    const ArgCheck ck{"bpp_masked_evaluate"};
+    if (!logits || !mask || !action || !log_prob || !entropy || !bad_prob) return ck.bad("NULL pointer");
+    if (E <= 0 || M <= 0) return ck.bad("non-positive size");
+    hipLaunchKernelGGL(masked_eval_fwd_kernel, dim3((E + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, mask, action, log_prob,
+                       entropy, bad_prob, E, M);
+    return launched();
+}
+
+int bpp_masked_evaluate_backward(const float *logits, const float *mask, const int64_t *action, const float *g_log_prob,
+                                 const float *g_entropy, const float *g_bad_prob, float *grad_logits, int32_t E, int32_t M,
+                                 void *stream) {
+    const ArgCheck ck{"bpp_masked_evaluate_backward"};
+    if (!logits || !mask || !action || !g_log_prob || !g_entropy || !g_bad_prob || !grad_logits)
+        return ck.bad("NULL pointer");
+    if (E <= 0 || M <= 0) return ck.bad("non-positive size");
+    hipLaunchKernelGGL(masked_eval_bwd_kernel, dim3((E + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, mask, action,
+                       g_log_prob, g_entropy, g_bad_prob, grad_logits, E, M);
+    return launched();
+}
+
+int bpp_fetch_to_host(const void *device_src, void *host_dst, int64_t nbytes, void *stream) {
+    const ArgCheck ck{"bpp_fetch_to_host"};
+    if (!device_src || !host_dst || nbytes <= 0) return ck.bad("NULL pointer / non-positive size");
+    hipError_t e = hipMemcpyAsync(host_dst, device_src, (size_t)nbytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamSynchronize");
+}
+
+int bpp_gather_finished(const uint8_t *done, const double *ep_ret, const double *ratio, const int32_t *ep_len,
+                        const int32_t *counter, int32_t E, void *dev, void *host, int32_t n, void *stream) {
+    const ArgCheck ck{"bpp_gather_finished"};
+    if (!done || !ep_ret || !ratio || !ep_len || !counter || !host) return ck.bad("NULL pointer");
+    if (E <= 0 || n < BPP_GATHER_ENQUEUE_ONLY || n > E) return ck.bad("bad size");
+    if (n == BPP_GATHER_ENQUEUE_ONLY) {
+        // the eager form: the compaction is only ENQUEUED behind the step (arrays laid out for E entries, straight into mapped host
+        // memory); the caller's one synchronisation of the step covers it and the header then tells how many entries there are
+        if (dev) return ck.bad("BPP_GATHER_ENQUEUE_ONLY writes into mapped host memory (dev must be NULL)");
+        if ((uintptr_t)host & 7u) return ck.bad("buffers must be 8-byte aligned");
+        int groups0, chunk0;
+        gather_shape(E, groups0, chunk0);
+        hipLaunchKernelGGL(compact_finished_kernel, dim3(groups0), dim3(kGatherThreads), 0, (hipStream_t)stream, done, ep_ret, ratio, ep_len, counter, E,
+                           (unsigned char *)host, E, chunk0);
+        return launched();
+    }
+    if (((uintptr_t)dev & 7u) || ((uintptr_t)host & 7u)) return ck.bad("buffers must be 8-byte aligned");
+    // dev == NULL: `host` is page-locked memory mapped into the device and the kernel writes the arrays there itself
+    // (~200 KB of mostly consecutive stores at 65 536 bins) -- no staging buffer, no copy engine
+    int groups, chunk;
+    gather_shape(E, groups, chunk);
+    hipLaunchKernelGGL(compact_finished_kernel, dim3(groups), dim3(kGatherThreads), 0, (hipStream_t)stream, done, ep_ret, ratio, ep_len, counter, E,
+                       (unsigned char *)(dev ? dev : host), n, chunk);
+    if (const int rc = launched()) return rc;
+    hipError_t e = hipSuccess;
+    if (dev) {
+        e = hipMemcpyAsync(host, dev, (size_t)BPP_FINISHED_BYTES(n), hipMemcpyDeviceToHost, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
+    }
+    e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    if (*(const int32_t *)host != n) return ck.bad("n is not the number of finished bins of this step");
+    return 0;
+}
+
+int bpp_wait(void *stream) {
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "hipStreamSynchronize");
+}
+
+int bpp_mark(void *host_flag, uint32_t value, void *stream) {
+    const ArgCheck ck{"bpp_mark"};
+    if (!host_flag || ((uintptr_t)host_flag & 3u)) return ck.bad("NULL / misaligned flag");
+    // the stream memory operation is not offered by this runtime / device (hipErrorNotSupported once): marker kernel from then
+    // on.  Any OTHER error of the call is the caller's (a bad stream ...) and is reported, not hidden behind the fallback.
+    static std::atomic<int> use_kernel{0};
+    if (!use_kernel.load(std::memory_order_relaxed) && host_flag_coherent(host_flag)) {
+        const hipError_t w = hipStreamWriteValue32((hipStream_t)stream, host_flag, value, 0);
+        if (w == hipSuccess) return 0;
+        (void)launched(nullptr);
+        if (w != hipErrorNotSupported) return hip_fail(w, "hipStreamWriteValue32");
+        use_kernel.store(1, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(mark_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (uint32_t *)host_flag, value);
+    return launched();
+}
+
+int bpp_wait_mark(const void *host_flag, uint32_t value, void *stream) {
+    const ArgCheck ck{"bpp_wait_mark"};
+    if (!host_flag) return ck.bad("NULL flag");
+    const uint32_t *f = (const uint32_t *)host_flag;
+    const bool coherent = host_flag_coherent(host_flag);
+    for (uint32_t spins = 1;; ++spins) {
+        if (__atomic_load_n(f, __ATOMIC_ACQUIRE) == value) {
+            if (!coherent) {        // the data the word announces may still sit in the device's caches: let the runtime finish the job
+                const hipError_t q = hipStreamSynchronize((hipStream_t)stream);
+                if (q != hipSuccess) return hip_fail(q, "hipStreamSynchronize");
+            }
+            return 0;
+        }
+        if ((spins & 0xfffu) == 0) {            // every few microseconds: is the stream still alive?
+            hipError_t q = hipStreamQuery((hipStream_t)stream);
+            if (q == hipSuccess) {              // all done and the word not seen yet: synchronise, look once more
+                q = hipStreamSynchronize((hipStream_t)stream);
+                if (q != hipSuccess) return hip_fail(q, "hipStreamSynchronize");
+                if (__atomic_load_n(f, __ATOMIC_ACQUIRE) == value) return 0;
+                return ck.bad("the stream is idle and the flag does not hold the value (no bpp_mark enqueued?)");
+            }
+            if (q != hipErrorNotReady) return hip_fail(q, "hipStreamQuery");
+        }
+        cpu_relax();
+    }
+}
+
+int bpp_step_dropin(const bpp_batch *b, const int64_t *actions, const bpp_step_out *out, void *fin_host, void *host_flag,
+                    uint32_t value, void *stream) {
+    int rc = bpp_step(b, actions, out, stream);
+    if (rc == 0 && fin_host)
+        rc = bpp_gather_finished(out->done, out->ep_ret, out->ratio, out->ep_len, out->counter, b->num_envs, nullptr, fin_host,
+                                 BPP_GATHER_ENQUEUE_ONLY, stream);
+    if (rc == 0 && host_flag) rc = bpp_mark(host_flag, value, stream);
+    return rc;
+}
+
+int bpp_stream_sizes(const bpp_stream *s, int64_t out[2]) {
+    const ArgCheck ck{"bpp_stream_sizes"};
+    if (!s || !out) return ck.bad("NULL pointer");
+    if (s->num_envs <= 0 || s->depth < 4 || !bpp_gen_cut2_args_ok(1, s->pool_len, s->W, s->L, s->H, s->bound_lo, s->bound_hi))
+        return ck.bad("fill in num_envs, depth, pool_len, the bin and the bounds first");
+    if (s->rng != BPP_STREAM_RNG_MT19937 && s->rng != BPP_STREAM_RNG_COUNTER) return ck.bad("unknown rng");
+    const StreamPlan p = plan_stream(s);
+    out[0] = (int64_t)(s->rng == BPP_STREAM_RNG_COUNTER ? kCtrRec : kMtRec) * s->num_envs;
+    out[1] = (int64_t)(p.fast_bytes > p.legacy_bytes ? p.fast_bytes : p.legacy_bytes);
+    return 0;
+}
+
+int bpp_stream_init(const bpp_stream *s, void *stream) {
+    int rc = check_stream(s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_init_kernel, dim3((s->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, *s);
+    return launched();
+}
+
+int bpp_stream_refill(const bpp_stream *s, void *stream) { return stream_refill(s, stream, 0, 0); }
+
 int bpp_episode_stats(const uint8_t *done, const double *ep_ret, const double *ratio, const int32_t *ep_len, int32_t E,
                       double *acc, void *stream) {
-    if (!done || !ep_ret || !ratio || !ep_len || !acc) return fail(BPP_E_BADARG, "bpp_episode_stats: NULL pointer");
-    if (E <= 0) return fail(BPP_E_BADARG, "bpp_episode_stats: non-positive size");
+    const ArgCheck ck{"bpp_episode_stats"};
+    if (!done || !ep_ret || !ratio || !ep_len || !acc) return ck.bad("NULL pointer");
+    if (E <= 0) return ck.bad("non-positive size");
     hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(BPP_REDUCE_LANES), 0, (hipStream_t)stream, done, ep_ret, ratio, ep_len, E, acc);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
 int bpp_episode_acc_reduce(double *ep_acc, int32_t E, double *acc, int32_t clear, void *scratch, void *stream) {
-    if (!ep_acc || !acc) return fail(BPP_E_BADARG, "bpp_episode_acc_reduce: NULL pointer");
-    if (E <= 0) return fail(BPP_E_BADARG, "bpp_episode_acc_reduce: non-positive size");
-    if ((uintptr_t)ep_acc & 31u) return fail(BPP_E_BADARG, "bpp_episode_acc_reduce: ep_acc must be 32-byte aligned");
+    const ArgCheck ck{"bpp_episode_acc_reduce"};
+    if (!ep_acc || !acc) return ck.bad("NULL pointer");
+    if (E <= 0) return ck.bad("non-positive size");
+    if ((uintptr_t)ep_acc & 31u) return ck.bad("ep_acc must be 32-byte aligned");
     if (scratch != nullptr) {
-        if ((uintptr_t)scratch & 7u) return fail(BPP_E_BADARG, "bpp_episode_acc_reduce: scratch must be 8-byte aligned");
+        if ((uintptr_t)scratch & 7u) return ck.bad("scratch must be 8-byte aligned");
         hipLaunchKernelGGL(acc_reduce_wide_kernel, dim3(kAccWideGroups), dim3(256), 0, (hipStream_t)stream, ep_acc, E, acc, clear,
                            (double *)scratch);
     } else {
         hipLaunchKernelGGL(acc_reduce_kernel, dim3(1), dim3(BPP_REDUCE_LANES), 0, (hipStream_t)stream, ep_acc, E, acc, clear);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
-
 int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, const int64_t *dst, int32_t n, void *stream) {
-    if (!b || !src || !dst || !b->hmap || !b->state) return fail(BPP_E_BADARG, "bpp_copy_bins: NULL pointer");
-    if (n < 0) return fail(BPP_E_BADARG, "bpp_copy_bins: negative n");
+    const ArgCheck ck{"bpp_copy_bins"};
+    if (!b || !src || !dst || !b->hmap || !b->state) return ck.bad("NULL pointer");
+    if (n < 0) return ck.bad("negative n");
     int rc = check_geometry(b->num_envs, b->W, b->L, b->H, b->rotation, b->mask_rule);
     if (rc) return rc;
     if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u) || ((uintptr_t)b->hmap & 3u) || !aligned16(b->state) || ((uintptr_t)b->seq_cache & 127u))
-        return fail(BPP_E_BADARG, "bpp_copy_bins: misaligned buffer");
+        return ck.bad("misaligned buffer");
     CopyArgs c;
     memset(&c, 0, sizeof c);
     c.E = b->num_envs;
@@ -1933,12 +1595,12 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
     c.src = src;
     c.dst = dst;
     if (b->pool_mode == BPP_POOL_RING) {
-        if (!s) return fail(BPP_E_BADARG, "bpp_copy_bins: a ring pool needs its bpp_stream");
+        if (!s) return ck.bad("a ring pool needs its bpp_stream");
         rc = check_stream(s);
         if (rc) return rc;
         if (s->num_envs != b->num_envs || (const void *)s->ring != (const void *)b->seq_pool || s->state != b->state ||
             (int64_t)s->depth * s->num_envs != b->pool_size || s->pool_len != b->pool_len)
-            return fail(BPP_E_BADARG, "bpp_copy_bins: the bpp_stream is not the one of this batch's ring");
+            return ck.bad("the bpp_stream is not the one of this batch's ring");
         c.T = s->pool_len;
         c.depth = s->depth;
         c.rec4 = (s->rng == BPP_STREAM_RNG_COUNTER ? kCtrRec : kMtRec) / 4;
@@ -1947,19 +1609,19 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
         c.gen_next = s->gen_next;
         c.cache = (unsigned char *)b->seq_cache;
     } else if (b->pool_mode == BPP_POOL_STATIC) {
-        if (s) return fail(BPP_E_BADARG, "bpp_copy_bins: a bpp_stream goes with BPP_POOL_RING");
+        if (s) return ck.bad("a bpp_stream goes with BPP_POOL_RING");
         if (b->seq_cache) return fail(BPP_E_BADARG, "bpp_batch: seq_cache goes with BPP_POOL_RING");
     } else {
         return fail(BPP_E_BADARG, "bpp_batch: unknown pool_mode");
     }
     if (n == 0) return 0;
     hipLaunchKernelGGL(copy_bins_kernel, dim3((unsigned)((n + kCopyWaves - 1) / kCopyWaves)), dim3(kWave * kCopyWaves), 0, (hipStream_t)stream, c);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
+    return launched();
 }
 
 }  // extern "C"
 
+#include "bpp_drivers.inl"
 #include "bpp_search_common.inl"
 #include "bpp_reorder.inl"
 #include "bpp_multibin.inl"

@@ -315,18 +315,6 @@ int policy_shape(const int32_t *g, int32_t n, bool need_n, const ArgCheck &ck, P
     return 0;
 }
 
-// more than 64 KiB of dynamic LDS is opted in to once per kernel and device
-template <typename Kern>
-void policy_raise_lds(Kern kern, std::atomic<uint64_t> &raised) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-        raised.fetch_or(bit, std::memory_order_release);
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -367,7 +355,7 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
     t.obs = obs, t.obs_stride = obs_stride, t.w = weights, t.feat = (float *)workspace;
     if (s.trunk_lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        policy_raise_lds(policy_trunk_kernel, raised);
+        raise_dynamic_lds(policy_trunk_kernel, raised, kPolLdsBytes);
     }
     hipLaunchKernelGGL(policy_trunk_kernel, dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), (size_t)s.trunk_lds, st, t);
     if (const int rc = launched()) return rc;
@@ -380,7 +368,7 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
     }
     if (s.head_lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        policy_raise_lds(policy_head_kernel, raised);
+        raise_dynamic_lds(policy_head_kernel, raised, kPolLdsBytes);
     }
     hipLaunchKernelGGL(policy_head_kernel, dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), (size_t)s.head_lds,
                        st, h);

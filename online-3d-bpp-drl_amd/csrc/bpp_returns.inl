@@ -134,19 +134,10 @@ __global__ __launch_bounds__(V == 4 ? kReturnsVecLanes : kReturnsLanes) void ret
     }
 }
 
-int returns_check(const ReturnsArgs &a, const char *who) {
-    if (a.T < 1 || a.N < 1) {
-        snprintf(g_err, sizeof g_err, "%s: T and N must be >= 1", who);
-        return BPP_E_BADARG;
-    }
-    if (!a.rewards || !a.value_preds || !a.next_value || !a.returns) {
-        snprintf(g_err, sizeof g_err, "%s: NULL pointer", who);
-        return BPP_E_BADARG;
-    }
-    if (!a.done && !a.masks) {
-        snprintf(g_err, sizeof g_err, "%s: give done or masks", who);
-        return BPP_E_BADARG;
-    }
+int returns_check(const ReturnsArgs &a, const ArgCheck &ck) {
+    if (a.T < 1 || a.N < 1) return ck.bad("T and N must be >= 1");
+    if (!a.rewards || !a.value_preds || !a.next_value || !a.returns) return ck.bad("NULL pointer");
+    if (!a.done && !a.masks) return ck.bad("give done or masks");
     return 0;
 }
 
@@ -184,7 +175,7 @@ int bpp_compute_returns(const float *rewards, float *value_preds, const float *n
                         int32_t use_proper_time_limits, double gamma, double gae_lambda, void *stream) {
     const ReturnsArgs a = returns_args(rewards, value_preds, next_value, done, masks, bad_masks, returns, advantages, T, N, use_gae,
                                        use_proper_time_limits, gamma, gae_lambda);
-    const int rc = returns_check(a, "bpp_compute_returns");
+    const int rc = returns_check(a, ArgCheck{"bpp_compute_returns"});
     if (rc) return rc;
     if (returns_bins_per_lane(a) == 4) {
         hipLaunchKernelGGL(returns_kernel<4>, dim3(returns_workgroups(a, 4)), dim3(kReturnsVecLanes), 0, (hipStream_t)stream, a);
@@ -199,12 +190,10 @@ int bpp_compute_returns_info(const float *rewards, float *value_preds, const flo
                              int32_t use_proper_time_limits, double gamma, double gae_lambda, int32_t out[3]) {
     const ReturnsArgs a = returns_args(rewards, value_preds, next_value, done, masks, bad_masks, returns, advantages, T, N, use_gae,
                                        use_proper_time_limits, gamma, gae_lambda);
-    const int rc = returns_check(a, "bpp_compute_returns_info");
+    const ArgCheck ck{"bpp_compute_returns_info"};
+    const int rc = returns_check(a, ck);
     if (rc) return rc;
-    if (!out) {
-        snprintf(g_err, sizeof g_err, "bpp_compute_returns_info: NULL out");
-        return BPP_E_BADARG;
-    }
+    if (!out) return ck.bad("NULL out");
     const int V = returns_bins_per_lane(a);
     out[0] = V, out[1] = V == 4 ? kReturnsVecLanes : kReturnsLanes, out[2] = (int32_t)returns_workgroups(a, V);
     return 0;
@@ -215,7 +204,7 @@ int bpp_compute_returns_host(const float *rewards, float *value_preds, const flo
                              int32_t use_proper_time_limits, double gamma, double gae_lambda) {
     const ReturnsArgs a = returns_args(rewards, value_preds, next_value, done, masks, bad_masks, returns, advantages, T, N, use_gae,
                                        use_proper_time_limits, gamma, gae_lambda);
-    const int rc = returns_check(a, "bpp_compute_returns_host");
+    const int rc = returns_check(a, ArgCheck{"bpp_compute_returns_host"});
     if (rc) return rc;
     const size_t n_bins = (size_t)N;
     for (size_t n = 0; n < n_bins; ++n) {

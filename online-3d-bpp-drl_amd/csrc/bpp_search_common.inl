@@ -1,7 +1,8 @@
 // bpp_search_common.inl -- what the three lookahead searches (bpp_reorder.inl, bpp_multibin.inl, bpp_mcts.inl) share,
 // included from bpp_kernels.hip right before them.  Every rule of the reference that more than one search restates is
 // stated here once: the float32 softmax of a logits row, numpy's argmax tie rules, the 4-plane observation row, the item
-// reward; then the host side: argument messages, the common batch checks and the launch of a one-wave-per-slot kernel.
+// reward; then the host side: the common batch checks and the launch of a one-wave-per-slot kernel (the argument messages,
+// ArgCheck, and launched() are the whole library's: bpp_kernels.hip).
 namespace {
 
 constexpr int kSearchWaves = 4;      // waves (= search slots) per workgroup of a one-wave-per-slot kernel
@@ -106,16 +107,6 @@ __device__ __forceinline__ uint32_t item_volume(uint32_t it) { return (it & 255u
 __device__ __forceinline__ double volume_reward(uint32_t vol, double binvol) { return ((double)vol / binvol) * 10.0; }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-// The argument errors of one entry point: "<who>: <what>", BPP_E_BADARG.
-struct ArgCheck {
-    const char *who;
-    int bad(const char *what) const {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(BPP_E_BADARG, msg);
-    }
-};
-
 // What every search checks of its batch before anything else (cfg: the search's own struct).  norot: the search's words
 // for a batch with rotation.  need_pool: the search reads the batch's static item pool.
 int check_search_batch(const bpp_batch *b, const void *cfg, const ArgCheck &ck, const char *norot, bool need_pool) {
@@ -126,11 +117,6 @@ int check_search_batch(const bpp_batch *b, const void *cfg, const ArgCheck &ck, 
     if (need_pool && b->pool_mode != BPP_POOL_STATIC) return ck.bad("the reorder search needs a static item pool (BPP_POOL_STATIC)");
     if ((need_pool && !b->seq_pool) || !b->hmap || !b->state) return ck.bad("NULL batch buffer");
     return 0;
-}
-
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "kernel launch");
 }
 
 // Launch `kernel` with one wave per slot for n slots / one thread per item for n items; nothing to do for n == 0.

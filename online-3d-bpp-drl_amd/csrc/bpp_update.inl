@@ -283,8 +283,9 @@ size_t bpp_a2c_loss_workspace(int32_t E, int32_t M) {
 }
 
 int bpp_a2c_loss_info(int32_t E, int32_t M, int32_t out[4]) {
-    if (E < 1 || M < 1) return fail(BPP_E_BADARG, "bpp_a2c_loss_info: E and M must be >= 1");
-    if (!out) return fail(BPP_E_BADARG, "bpp_a2c_loss_info: NULL out");
+    const ArgCheck ck{"bpp_a2c_loss_info"};
+    if (E < 1 || M < 1) return ck.bad("E and M must be >= 1");
+    if (!out) return ck.bad("NULL out");
     int iters, groups;
     a2c_shape(E, iters, groups);
     out[0] = 4 * iters, out[1] = groups, out[2] = a2c_regs(M) > 0, out[3] = kA2cWidth;
@@ -295,10 +296,11 @@ int bpp_a2c_loss(const float *logits, const float *location_masks, const int64_t
                  const float *pred_mask, double value_loss_coef, double entropy_coef, double invalid_coef, double mask_coef,
                  float *grad_logits, float *grad_values, float *grad_pred_mask, float *rows, float *terms, void *workspace, int32_t E,
                  int32_t M, void *stream) {
-    if (E < 1 || M < 1) return fail(BPP_E_BADARG, "bpp_a2c_loss: E and M must be >= 1");
+    const ArgCheck ck{"bpp_a2c_loss"};
+    if (E < 1 || M < 1) return ck.bad("E and M must be >= 1");
     if (!logits || !location_masks || !action || !values || !returns || !grad_logits || !grad_values || !terms || !workspace)
-        return fail(BPP_E_BADARG, "bpp_a2c_loss: NULL pointer");
-    if (pred_mask && !grad_pred_mask) return fail(BPP_E_BADARG, "bpp_a2c_loss: pred_mask without grad_pred_mask");
+        return ck.bad("NULL pointer");
+    if (pred_mask && !grad_pred_mask) return ck.bad("pred_mask without grad_pred_mask");
     A2cArgs a;
     a.logits = logits, a.mask = location_masks, a.values = values, a.returns = returns, a.pred = pred_mask, a.action = action;
     a.g_logits = grad_logits, a.g_values = grad_values, a.g_pred = grad_pred_mask, a.rows = rows, a.partial = (double *)workspace;

@@ -4,6 +4,7 @@ emulator (tests/emu/emu_runtime.cpp, tests/emu/hip/hip_runtime.h).  Same C ABI a
 pointers, so the numpy front-end written for the oracle library drives it unchanged: this module is a second
 instance of oracle/oracle.py bound to the emulated library.  Used by the CPU test suite to check kernel
 LOGIC against the oracle without a GPU; it is never imported by the product and measures nothing."""
+import ctypes
 import glob
 import importlib.util
 import os
@@ -43,6 +44,11 @@ def load():
     m.LIB = LIB
     m.build = build
     m._lib = None
-    m.lib()
+    L = m.lib()
     m.EmuEnv = m.OracleEnv
+    # include/bpp_pipeline.h: exported by the product only, so bound here and not in the front-end the oracle library shares
+    sets = L.bpp_rollout_uniform_sets.argtypes
+    L.bpp_pipeline_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]
+    L.bpp_pipeline_destroy.argtypes = [ctypes.c_void_p]
+    L.bpp_rollout_uniform_sets_pipelined.argtypes = sets[:-1] + [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     return m
