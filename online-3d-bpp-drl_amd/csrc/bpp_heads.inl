@@ -1,7 +1,37 @@
-// bpp_heads.inl -- the action-selection kernels, included by bpp_kernels.hip inside its anonymous namespace (round 6: moved out
-// of that file unchanged): the uniform-feasible samplers of the benchmark policy (bpp_sample_feasible), the masked categorical
-// head of the policy (bpp_masked_act / bpp_masked_act_counter; acktr/distributions.py:71-84) and its training half
-// (bpp_masked_evaluate / _backward; acktr/model.py:90-96).  Host entry points: bpp_kernels.hip.
+// bpp_heads.inl -- the action-selection kernels, included by bpp_kernels.hip inside its anonymous namespace after bpp_wave.inl (the
+// wave primitives): the uniform-feasible samplers of the benchmark policy (bpp_sample_feasible), the masked categorical head of
+// the policy (bpp_masked_act / bpp_masked_act_counter; acktr/distributions.py:71-84) and its training half (bpp_masked_evaluate
+// / _backward; acktr/model.py:90-96).  The head's float32 expressions are stated once, right below, and the training half's row
+// body once (row_stats, row_terms): bpp_a2c_loss (bpp_update.inl) is a third instantiation of it.  Host entry points: bpp_kernels.hip.
+
+// ---- the masked head's expressions (acktr/distributions.py:71-101), float32, built with -ffp-contract=off ------------------
+//   lx = softmax(x - 14 (1 - mask)) + 1e-5,   p = lx / sum(lx),   log(clamp(p)) with torch's probs_to_logits clamp
+// Whoever needs one of them calls it from here, so operation order and associativity are the same everywhere.
+constexpr float kProbEps = 1.1920928955078125e-7f;   // torch.finfo(float32).eps, probs_to_logits clamp
+constexpr float kProbFloor = 1e-5f;                  // distributions.py:79-80
+__device__ __forceinline__ float masked_logit(float x, float m) { return x - (1.0f - m) * 14.0f; }   // distributions.py:76-79
+__device__ __forceinline__ float clamp_log(float p) { return logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps)); }
+struct RowStats {
+    float mq, ma, sq, sa, tot;   // maxima and denominators of the masked / plain softmax, sum of lx
+    __device__ __forceinline__ float eq(float x, float m) const { return expf(masked_logit(x, m) - mq); }
+    __device__ __forceinline__ float ea(float x) const { return expf(x - ma); }
+    __device__ __forceinline__ float q(float x, float m) const { return eq(x, m) / sq; }      // masked softmax
+    __device__ __forceinline__ float av(float x) const { return ea(x) / sa; }                 // plain softmax
+    __device__ __forceinline__ float p(float q) const { return (q + kProbFloor) / tot; }
+};
+// d loss / d p_k given lg = clamp_log(p): the entropy term, and the log-probability term on the entry that is the action taken
+// (the clamp's derivative is 0 outside)
+__device__ __forceinline__ float head_hk(bool taken, float p, float lg, float gl, float ge) {
+    const bool inside = p > kProbEps && p < 1.0f - kProbEps;
+    const float pc = fminf(fmaxf(p, kProbEps), 1.0f - kProbEps);
+    float h = -ge * (lg + (inside ? p / pc : 0.0f));
+    if (taken) h += inside ? gl / pc : 0.0f;
+    return h;
+}
+// log-probability of action a of row (x, m); an action outside [0, M) is no entry of the row: log(clamp(eps))
+__device__ __forceinline__ float action_logp(const float *x, const float *m, int M, int64_t a, const RowStats &r) {
+    return clamp_log((a >= 0 && a < M) ? r.p(r.q(x[a], m[a])) : kProbEps);
+}
 
 // Sub-groups of 16 lanes per bin (4 bins per wave): each lane owns `per` consecutive float4 quads of
 // the bin's mask row (16-byte loads), an inclusive scan inside the 16-lane row locates the pick-th set
@@ -22,12 +52,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *mask, int64_t 
         q[k] = (active && qi < nq) ? m[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
         cnt += (q[k].x != 0.f) + (q[k].y != 0.f) + (q[k].z != 0.f) + (q[k].w != 0.f);
     }
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-        const int o = __shfl_up(incl, d, 16);
-        if (sl >= d) incl += o;
-    }
+    const int incl = wave_scan_incl<16>(cnt, sl);
     const int total = __shfl(incl, 15, 16);
     if (!active) return;
     if (total == 0) {
@@ -65,38 +90,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *mask, int64_t 
 // a quad past the end of the row is a -inf logit instead of a predicate per element, the sampled entry is found by
 // COUNTING the cumulative sums below the target, and the lane that owns the chosen entry writes the outputs (no broadcast
 // of its probability): ~340 instructions per wave.
-// row_ror:n rotates within every 16-lane row; row_shr:n shifts, lanes without a source keep `old`
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v, float old) {
-    (void)old;
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v, int old) {
-    (void)old;
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_f<0x128>(v, v)); v = fmaxf(v, dpp_f<0x124>(v, v)); v = fmaxf(v, dpp_f<0x122>(v, v)); v = fmaxf(v, dpp_f<0x121>(v, v));
-    return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_f<0x128>(v, v); v += dpp_f<0x124>(v, v); v += dpp_f<0x122>(v, v); v += dpp_f<0x121>(v, v);
-    return v;
-}
-__device__ __forceinline__ int row16_min(int v) {
-    v = min(v, dpp_i<0x128>(v, v)); v = min(v, dpp_i<0x124>(v, v)); v = min(v, dpp_i<0x122>(v, v)); v = min(v, dpp_i<0x121>(v, v));
-    return v;
-}
-__device__ __forceinline__ int row16_isum(int v) {
-    v += dpp_i<0x128>(v, v); v += dpp_i<0x124>(v, v); v += dpp_i<0x122>(v, v); v += dpp_i<0x121>(v, v);
-    return v;
-}
-__device__ __forceinline__ float row16_scan(float v) {   // inclusive prefix sum along the row
-    v += dpp_f<0x111>(v, 0.0f); v += dpp_f<0x112>(v, 0.0f); v += dpp_f<0x114>(v, 0.0f); v += dpp_f<0x118>(v, 0.0f);
-    return v;
-}
-
+// The dpp_* / row16_* helpers: bpp_wave.inl.
 template <int PER, bool DET>
 __global__ __launch_bounds__(256) void masked_act_kernel(const float *logits, const float *mask, int64_t *action,
                                                          float *log_prob, int E, int M, int64_t env_id_base,
@@ -123,10 +117,10 @@ __global__ __launch_bounds__(256) void masked_act_kernel(const float *logits, co
     float mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
-        z[k][0] = xv[k].x - (1.0f - mv[k].x) * 14.0f;  // distributions.py:76-79
-        z[k][1] = xv[k].y - (1.0f - mv[k].y) * 14.0f;
-        z[k][2] = xv[k].z - (1.0f - mv[k].z) * 14.0f;
-        z[k][3] = xv[k].w - (1.0f - mv[k].w) * 14.0f;
+        z[k][0] = masked_logit(xv[k].x, mv[k].x);
+        z[k][1] = masked_logit(xv[k].y, mv[k].y);
+        z[k][2] = masked_logit(xv[k].z, mv[k].z);
+        z[k][3] = masked_logit(xv[k].w, mv[k].w);
         mx = fmaxf(fmaxf(mx, fmaxf(z[k][0], z[k][1])), fmaxf(z[k][2], z[k][3]));
     }
     mx = row16_max(mx);
@@ -218,11 +212,6 @@ __global__ __launch_bounds__(256) void masked_act_kernel(const float *logits, co
 // Same selection for rows the 16-lane kernel cannot take (M not a multiple of 4, or M > 512 such as the
 // 20x20 bin with rotation, M = 800): one wave per bin, entry k lives in lane k % 64, chunk k / 64; the CDF
 // walks the chunks in order with an inclusive wave scan per chunk.
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 __global__ __launch_bounds__(256) void masked_act_kernel_generic(const float *logits, const float *mask, int64_t *action,
                                                                  float *log_prob, int E, int M, int64_t env_id_base,
                                                                  uint64_t seed, uint64_t step, int deterministic, const uint64_t *seed_step) {
@@ -233,35 +222,27 @@ __global__ __launch_bounds__(256) void masked_act_kernel_generic(const float *lo
     const float *x = logits + (size_t)e * M, *m = mask + (size_t)e * M;
     const int nchunk = (M + kWave - 1) / kWave;
     float mx = -INFINITY;
-    for (int k = lane; k < M; k += kWave) mx = fmaxf(mx, x[k] - (1.0f - m[k]) * 14.0f);  // distributions.py:76-79
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, kWave));
+    for (int k = lane; k < M; k += kWave) mx = fmaxf(mx, masked_logit(x[k], m[k]));
+    mx = wave_max(mx);
     float part = 0.0f;
-    for (int k = lane; k < M; k += kWave) part += expf(x[k] - (1.0f - m[k]) * 14.0f - mx);
-    const float sum = wave_sum_f(part);
+    for (int k = lane; k < M; k += kWave) part += expf(masked_logit(x[k], m[k]) - mx);
+    const float sum = wave_sum(part);
+    const auto lx = [&](int k) { return expf(masked_logit(x[k], m[k]) - mx) / sum + kProbFloor; };
     float lane_tot = 0.0f, best = -1.0f;
     int best_i = 0;
     for (int k = lane; k < M; k += kWave) {
-        const float pk = expf(x[k] - (1.0f - m[k]) * 14.0f - mx) / sum + 1e-5f;  // distributions.py:79-80
+        const float pk = lx(k);
         lane_tot += pk;
         if (pk > best) {
             best = pk;
             best_i = k;
         }
     }
-    const float tot = wave_sum_f(lane_tot);
+    const float tot = wave_sum(lane_tot);
     int a;
     float pa;
     if (deterministic) {  // dist.mode(): first index of the maximum
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const float ob = __shfl_xor(best, d, kWave);
-            const int oi = __shfl_xor(best_i, d, kWave);
-            if (ob > best || (ob == best && oi < best_i)) {
-                best = ob;
-                best_i = oi;
-            }
-        }
+        wave_argmax(best, best_i, false);
         a = best_i;
         pa = best;
     } else {
@@ -271,41 +252,25 @@ __global__ __launch_bounds__(256) void masked_act_kernel_generic(const float *lo
         int cand = 0x7fffffff;
         for (int c = 0; c < nchunk; ++c) {  // wave-uniform trip count
             const int k = c * kWave + lane;
-            const float pk = k < M ? expf(x[k] - (1.0f - m[k]) * 14.0f - mx) / sum + 1e-5f : 0.0f;
-            float incl = pk;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const float o = __shfl_up(incl, d, kWave);
-                if (lane >= d) incl += o;
-            }
+            const float pk = k < M ? lx(k) : 0.0f;
+            const float incl = wave_scan_incl(pk, lane);
             if (cand == 0x7fffffff && k < M && base + incl > target) {
                 cand = k;
                 pm = pk;
             }
             base += __shfl(incl, kWave - 1, kWave);
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const int oc = __shfl_xor(cand, d, kWave);
-            const float op = __shfl_xor(pm, d, kWave);
-            if (oc < cand) {
-                cand = oc;
-                pm = op;
-            }
-        }
+        wave_min_keyed(cand, pm);
         if (cand == 0x7fffffff) {  // rounding at u ~ 1: the last entry
             cand = M - 1;
-            pm = expf(x[M - 1] - (1.0f - m[M - 1]) * 14.0f - mx) / sum + 1e-5f;
+            pm = lx(M - 1);
         }
         a = cand;
         pa = pm;
     }
     if (lane == 0) {
         action[e] = a;
-        if (log_prob) {
-            const float eps = 1.1920928955078125e-7f;
-            log_prob[e] = logf(fminf(fmaxf(pa / tot, eps), 1.0f - eps));
-        }
+        if (log_prob) log_prob[e] = clamp_log(pa / tot);
     }
 }
 
@@ -314,38 +279,137 @@ __global__ __launch_bounds__(256) void masked_act_kernel_generic(const float *lo
 //   logp  = log(clamp(p[a]))            p = lx / sum(lx), lx = softmax(x - 14 (1 - mask)) + 1e-5   (dist.log_probs)
 //   ent   = -sum_k p_k log(clamp(p_k))                                                           (dist.entropy())
 //   bad   = sum_k softmax(x)_k (1 - mask_k)                                                      (row sum of `bx`)
-// and the backward kernel the gradient of  g_logp * logp + g_ent * ent + g_bad * bad  with respect to the logits
-// (clamp = torch's probs_to_logits clamp to [eps, 1 - eps], derivative 0 outside).
-struct RowStats {
-    float mq, ma, sq, sa, tot;   // maxima and denominators of the masked / plain softmax, sum of lx
+// and the gradient of  gl * logp + ge * ent + gb * bad  with respect to the logits.
+//
+// A lane's view of one row, in two forms.  Entry k lives in lane k % 64; each(f) calls f(j, k) for the lane's entries
+// k = lane + 64 j < M in ascending k.  The row body computes the per-entry values (the two exponentials, then q and av, then h) in
+// passes; put_*() hands each to the row where it is first computed and the getters give it to the later passes.  MemRow keeps
+// nothing and computes it again from x and m -- the same expression, so the same bits; RegRow<NJ> (M <= 64 NJ) keeps all of
+// them in registers and has issued every load of the row before any arithmetic.
+struct HeadGrad {
+    int64_t act;        // the action taken
+    float gl, ge, gb;   // weights of logp, ent and bad in the loss
 };
-__device__ __forceinline__ float wave_max_f(float v) {
+struct MemRow {
+    const float *xs, *ms;
+    int M, lane;
+    __device__ __forceinline__ MemRow(const float *x, const float *m, int M_, int lane_) : xs(x), ms(m), M(M_), lane(lane_) {}
+    template <typename F>
+    __device__ __forceinline__ void each(F f) const {
+        for (int k = lane; k < M; k += kWave) f(0, k);
+    }
+    __device__ __forceinline__ float x(int, int k) const { return xs[k]; }
+    __device__ __forceinline__ float m(int, int k) const { return ms[k]; }
+    __device__ __forceinline__ float eq(int, int k, const RowStats &r) const { return r.eq(xs[k], ms[k]); }
+    __device__ __forceinline__ float ea(int, int k, const RowStats &r) const { return r.ea(xs[k]); }
+    __device__ __forceinline__ float q(int, int k, const RowStats &r) const { return r.q(xs[k], ms[k]); }
+    __device__ __forceinline__ float av(int, int k, const RowStats &r) const { return r.av(xs[k]); }
+    __device__ __forceinline__ float h(int, int k, const RowStats &r, const HeadGrad &w) const {
+        const float p = r.p(r.q(xs[k], ms[k]));
+        return head_hk(k == w.act, p, clamp_log(p), w.gl, w.ge);
+    }
+    __device__ __forceinline__ void put_e(int, float, float) const {}
+    __device__ __forceinline__ void put_q(int, float) const {}
+    __device__ __forceinline__ void put_av(int, float) const {}
+    __device__ __forceinline__ void put_h(int, float) const {}
+};
+template <int NJ>
+struct RegRow {
+    float xv[NJ], mv[NJ], qv[NJ], avv[NJ], hv[NJ];   // logit, mask; masked exponential -> q; plain exponential -> av; h
+    int M, lane;
+    __device__ __forceinline__ RegRow(const float *x, const float *m, int M_, int lane_) : M(M_), lane(lane_) {
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ RowStats masked_row_stats(const float *x, const float *m, int M, int lane) {
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + kWave * j;
+            const bool ok = k < M;
+            xv[j] = ok ? x[k] : 0.0f;
+            mv[j] = ok ? m[k] : 0.0f;
+        }
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(F f) const {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (lane + kWave * j < M) f(j, lane + kWave * j);
+    }
+    __device__ __forceinline__ float x(int j, int) const { return xv[j]; }
+    __device__ __forceinline__ float m(int j, int) const { return mv[j]; }
+    // Order contract: a slot holds a pass's value until the next pass overwrites it.  qv[j] is the masked exponential from
+    // put_e until put_q and q from then on; avv[j] is the plain exponential from put_e until put_av and av from then on.  So
+    // eq() / ea() are valid only before, q() / av() only after the matching put: the order row_stats and row_terms keep.
+    __device__ __forceinline__ float eq(int j, int, const RowStats &) const { return qv[j]; }     // before put_q
+    __device__ __forceinline__ float ea(int j, int, const RowStats &) const { return avv[j]; }    // before put_av
+    __device__ __forceinline__ float q(int j, int, const RowStats &) const { return qv[j]; }      // after put_q
+    __device__ __forceinline__ float av(int j, int, const RowStats &) const { return avv[j]; }    // after put_av
+    __device__ __forceinline__ float h(int j, int, const RowStats &, const HeadGrad &) const { return hv[j]; }
+    __device__ __forceinline__ void put_e(int j, float e, float a) { qv[j] = e, avv[j] = a; }
+    __device__ __forceinline__ void put_q(int j, float v) { qv[j] = v; }
+    __device__ __forceinline__ void put_av(int j, float v) { avv[j] = v; }
+    __device__ __forceinline__ void put_h(int j, float v) { hv[j] = v; }
+};
+
+// One wave, one row, in two steps.  A lane adds its entries in ascending k; row sums and maxima go through wave_sum / wave_max.
+// row_stats: the row statistics, in every lane.
+template <typename Row>
+__device__ __forceinline__ RowStats row_stats(Row &row) {
     RowStats r;
     float mq = -INFINITY, ma = -INFINITY;
-    for (int k = lane; k < M; k += kWave) {
-        mq = fmaxf(mq, x[k] - (1.0f - m[k]) * 14.0f);
-        ma = fmaxf(ma, x[k]);
-    }
-    r.mq = wave_max_f(mq);
-    r.ma = wave_max_f(ma);
+    row.each([&](int j, int k) {
+        mq = fmaxf(mq, masked_logit(row.x(j, k), row.m(j, k)));
+        ma = fmaxf(ma, row.x(j, k));
+    });
+    r.mq = wave_max(mq);
+    r.ma = wave_max(ma);
     float sq = 0.0f, sa = 0.0f;
-    for (int k = lane; k < M; k += kWave) {
-        sq += expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq);
-        sa += expf(x[k] - r.ma);
-    }
-    r.sq = wave_sum_f(sq);
-    r.sa = wave_sum_f(sa);
+    row.each([&](int j, int k) {
+        const float e = r.eq(row.x(j, k), row.m(j, k)), a = r.ea(row.x(j, k));
+        row.put_e(j, e, a);
+        sq += e;
+        sa += a;
+    });
+    r.sq = wave_sum(sq);
+    r.sa = wave_sum(sa);
     float tot = 0.0f;
-    for (int k = lane; k < M; k += kWave) tot += expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq + 1e-5f;
-    r.tot = wave_sum_f(tot);
+    row.each([&](int j, int k) {
+        const float q = row.eq(j, k, r) / r.sq;
+        row.put_q(j, q);
+        tot += q + kProbFloor;
+    });
+    r.tot = wave_sum(tot);
     return r;
 }
-constexpr float kProbEps = 1.1920928955078125e-7f;   // torch.finfo(float32).eps, probs_to_logits clamp
+// row_terms: ent (with ENT) and bad in every lane, and with GRAD the gradient into g[0 .. M).
+template <bool ENT, bool GRAD, typename Row>
+__device__ __forceinline__ void row_terms(Row &row, const RowStats &r, const HeadGrad &w, float *g, float &ent, float &bad) {
+    float h = 0.0f, b = 0.0f, c = 0.0f;   // entropy, bad mass, sum_j p_j h_j
+    row.each([&](int j, int k) {
+        const float p = r.p(row.q(j, k, r));
+        const float lg = clamp_log(p);
+        if constexpr (ENT) h -= p * lg;
+        const float av = row.ea(j, k, r) / r.sa;
+        row.put_av(j, av);
+        b += av * (1.0f - row.m(j, k));
+        if constexpr (GRAD) {
+            const float hk = head_hk(k == w.act, p, lg, w.gl, w.ge);
+            row.put_h(j, hk);
+            c += p * hk;
+        }
+    });
+    if constexpr (ENT) h = wave_sum(h);
+    b = wave_sum(b);
+    if constexpr (GRAD) {
+        c = wave_sum(c);
+        float v = 0.0f;   // sum_j q_j u_j,  u_j = (h_j - c) / tot
+        row.each([&](int j, int k) { v += row.q(j, k, r) * (row.h(j, k, r, w) - c) / r.tot; });
+        v = wave_sum(v);
+        row.each([&](int j, int k) {
+            const float u = (row.h(j, k, r, w) - c) / r.tot;
+            g[k] = row.q(j, k, r) * (u - v) + w.gb * row.av(j, k, r) * ((1.0f - row.m(j, k)) - b);
+        });
+    }
+    ent = h;
+    bad = b;
+}
 
 __global__ __launch_bounds__(256) void masked_eval_fwd_kernel(const float *logits, const float *mask, const int64_t *action,
                                                               float *logp, float *entropy, float *bad, int E, int M) {
@@ -353,19 +417,12 @@ __global__ __launch_bounds__(256) void masked_eval_fwd_kernel(const float *logit
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
     const float *x = logits + (size_t)e * M, *m = mask + (size_t)e * M;
-    const RowStats r = masked_row_stats(x, m, M, lane);
-    float h = 0.0f, b = 0.0f;
-    for (int k = lane; k < M; k += kWave) {
-        const float p = (expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq + 1e-5f) / r.tot;
-        h -= p * logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
-        b += expf(x[k] - r.ma) / r.sa * (1.0f - m[k]);
-    }
-    h = wave_sum_f(h);
-    b = wave_sum_f(b);
+    MemRow row(x, m, M, lane);
+    float h, b;
+    const RowStats r = row_stats(row);
+    row_terms<true, false>(row, r, HeadGrad{}, nullptr, h, b);
     if (lane == 0) {
-        const int64_t a = action[e];
-        const float pa = (a >= 0 && a < M) ? (expf(x[a] - (1.0f - m[a]) * 14.0f - r.mq) / r.sq + 1e-5f) / r.tot : kProbEps;
-        logp[e] = logf(fminf(fmaxf(pa, kProbEps), 1.0f - kProbEps));
+        logp[e] = action_logp(x, m, M, action[e], r);
         entropy[e] = h;
         bad[e] = b;
     }
@@ -377,39 +434,11 @@ __global__ __launch_bounds__(256) void masked_eval_bwd_kernel(const float *logit
     const int lane = threadIdx.x & (kWave - 1);
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
-    const float *x = logits + (size_t)e * M, *m = mask + (size_t)e * M;
-    float *g = grad + (size_t)e * M;
-    const RowStats r = masked_row_stats(x, m, M, lane);
-    const int64_t a = action[e];
-    const float gl = g_logp[e], ge = g_ent[e], gb = g_bad[e];
-    // h_k = dLoss/dp_k
-    auto hk = [&](int k, float p) {
-        const bool inside = p > kProbEps && p < 1.0f - kProbEps;
-        const float pc = fminf(fmaxf(p, kProbEps), 1.0f - kProbEps);
-        float h = -ge * (logf(pc) + (inside ? p / pc : 0.0f));
-        if (k == a) h += inside ? gl / pc : 0.0f;
-        return h;
-    };
-    float c = 0.0f, b = 0.0f;
-    for (int k = lane; k < M; k += kWave) {
-        const float p = (expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq + 1e-5f) / r.tot;
-        c += p * hk(k, p);
-        b += expf(x[k] - r.ma) / r.sa * (1.0f - m[k]);
-    }
-    c = wave_sum_f(c);   // sum_j p_j h_j
-    b = wave_sum_f(b);   // bad
-    float v = 0.0f;      // sum_j q_j u_j,  u_j = (h_j - c) / tot
-    for (int k = lane; k < M; k += kWave) {
-        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
-        v += q * (hk(k, (q + 1e-5f) / r.tot) - c) / r.tot;
-    }
-    v = wave_sum_f(v);
-    for (int k = lane; k < M; k += kWave) {
-        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
-        const float u = (hk(k, (q + 1e-5f) / r.tot) - c) / r.tot;
-        const float av = expf(x[k] - r.ma) / r.sa;
-        g[k] = q * (u - v) + gb * av * ((1.0f - m[k]) - b);
-    }
+    MemRow row(logits + (size_t)e * M, mask + (size_t)e * M, M, lane);
+    const RowStats r = row_stats(row);
+    const HeadGrad w{action[e], g_logp[e], g_ent[e], g_bad[e]};   // per-row weights
+    float h, b;
+    row_terms<false, true>(row, r, w, grad + (size_t)e * M, h, b);
 }
 
 // One wave draws a uniform-feasible entry of mask row r, that of the bin with global id env_id_base + bin, into actions[r] (0
@@ -422,12 +451,7 @@ __device__ __forceinline__ void sample_row_wave(const float *mask, int64_t *acti
     const int b = min(lane * per, M), en = min(b + per, M);
     int cnt = 0;
     for (int k = b; k < en; ++k) cnt += (m[k] != 0.0f);
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int o = __shfl_up(incl, d, kWave);
-        if (lane >= d) incl += o;
-    }
+    const int incl = wave_scan_incl(cnt, lane);
     const int total = __shfl(incl, kWave - 1, kWave);
     if (total == 0) {
         if (lane == 0) actions[r] = 0;

@@ -537,6 +537,7 @@ __device__ __forceinline__ float4 quad_floats(uint32_t v) {
 #include "bpp_tile_kernel.inl"
 #include "bpp_stream_gen.inl"
 
+#include "bpp_wave.inl"
 #include "bpp_heads.inl"
 #include "bpp_stats.inl"
 

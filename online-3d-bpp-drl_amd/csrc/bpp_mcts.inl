@@ -598,11 +598,7 @@ __global__ __launch_bounds__(kWave * kSearchWaves) void mcts_advance_kernel(cons
                 sb = dst[bq + 1 + j].block;
                 if (sb >= 0) sz = 1 + src[sb].n;
             }
-            int off = sz;                                        // inclusive prefix of the block sizes over the lanes
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int o = __shfl_up(off, d, kWave);
-                if (lane >= d) off += o;
-            }
+            int off = wave_scan_incl(sz, lane);                  // inclusive prefix of the block sizes over the lanes
             const int total = __shfl(off, kWave - 1, kWave);
             off -= sz;
             if (sb >= 0) dst[bq + 1 + j].block = next + off;

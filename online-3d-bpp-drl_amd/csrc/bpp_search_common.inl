@@ -2,7 +2,8 @@
 // included from bpp_kernels.hip right before them.  Every rule of the reference that more than one search restates is
 // stated here once: the float32 softmax of a logits row, numpy's argmax tie rules, the 4-plane observation row, the item
 // reward; then the host side: the common batch checks and the launch of a one-wave-per-slot kernel (the argument messages,
-// ArgCheck, and launched() are the whole library's: bpp_kernels.hip).
+// ArgCheck, and launched() are the whole library's: bpp_kernels.hip; the wave reductions wave_sum / wave_max / wave_argmax
+// are the whole library's too: bpp_wave.inl).
 namespace {
 
 constexpr int kSearchWaves = 4;      // waves (= search slots) per workgroup of a one-wave-per-slot kernel
@@ -37,24 +38,9 @@ __device__ __forceinline__ bool slot_bins(const Args &a, int i, int &e, int &sid
     int e = 0, sid = 0;              \
     const bool ok = slot_bins(a, i, e, sid);
 
-// ---- wave-wide reductions: the xor butterfly 32 .. 1, every lane ends with the result ------------------------------------
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, kWave));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, kWave));
-    return v;
-}
-
 // model_loader.evaluate's softmax of a logits row, float32: mx = max(lg), sum = sum(exp(lg - mx)), lane-strided and then
-// the butterfly.  A probability is expf(lg[c] - mx) / sum (IEEE division).  each(c, expf(lg[c] - mx)) runs in the summing
-// pass, for a caller that stores the terms or counts something else along the way.
+// the butterfly (bpp_wave.inl).  A probability is expf(lg[c] - mx) / sum (IEEE division).  each(c, expf(lg[c] - mx)) runs in
+// the summing pass, for a caller that stores the terms or counts something else along the way.
 template <typename Each>
 __device__ __forceinline__ void row_softmax_stats(const float *lg, int n, int lane, float &mx, float &sum, Each each) {
     mx = -INFINITY;
@@ -70,16 +56,6 @@ __device__ __forceinline__ void row_softmax_stats(const float *lg, int n, int la
 }
 __device__ __forceinline__ void row_softmax_stats(const float *lg, int n, int lane, float &mx, float &sum) {
     row_softmax_stats(lg, n, lane, mx, sum, [](int, float) {});
-}
-
-// The wave's argmax of per-lane candidates (best, bi) under numpy's tie rules: the first maximum (np.argmax) or, with
-// `last`, the last one (argsort()[-1]).  A lane's own scan keeps its first / last maximum the same way before it calls this.
-__device__ __forceinline__ void wave_argmax(float &best, int &bi, bool last) {
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ob = __shfl_xor(best, m, kWave);
-        const int oi = __shfl_xor(bi, m, kWave);
-        if (ob > best || (ob == best && (last ? oi > bi : oi < bi))) best = ob, bi = oi;
-    }
 }
 
 // Cells [c0, c0 + 4) of an observation row of n cells per plane (cur_observation: heights h, then the item's x, y, z

@@ -190,8 +190,7 @@ __global__ __launch_bounds__(kGatherThreads) void compact_finished_kernel(const 
     } else {
         for (int i = t; i < c_lo; i += kGatherThreads) before += done[i] != 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+    before = wave_sum(before);
     if (lane == 0) wave_tot[wave] = before;
     __syncthreads();
     int base = 0;
@@ -214,12 +213,7 @@ __global__ __launch_bounds__(kGatherThreads) void compact_finished_kernel(const 
                 if (e0 + k < c_hi && done[e0 + k]) m |= 1u << k;
         }
         const int cnt = __popc(m);
-        int incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
+        const int incl = wave_scan_incl(cnt, lane);
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();
         if (t == 0) {

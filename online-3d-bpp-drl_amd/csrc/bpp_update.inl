@@ -1,12 +1,12 @@
 // bpp_update.inl -- the loss of the A2C update and its gradients in one pass (include/bpp_update.h), included at the
 // end of bpp_kernels.hip: the five terms of acktr/algo/acktr_pipeline.py:45-92 and d loss / d (logits, values, pred_mask).
 //
-// One wave per row, four rows at a time per 256-lane workgroup, as the evaluate kernels of bpp_heads.inl -- whose expressions
-// these are, in the same operation order: entry k of a row lives in lane k % 64, a lane adds its entries in ascending k, row sums
-// go through wave_sum_f.  What differs is how often memory is visited: for M <= 512 a lane keeps its <= 8 entries of logits,
-// location mask and predicted mask in registers, together with the values the evaluate kernels compute two to four times (the
-// two exponentials, the probability and its logarithm), so each input array is read once per row and each gradient array is
-// written once.  Longer rows walk memory like masked_eval_*_kernel do.  Same bits either way (float32, -ffp-contract=off).
+// One wave per row, four rows at a time per 256-lane workgroup, as the evaluate kernels of bpp_heads.inl -- and through the same
+// row body, row_stats and row_terms, built from the same expressions: the bits are theirs by construction.  What differs is how
+// often memory is visited: for M <= 512 the row is a RegRow, a lane keeps its <= 8 entries of logits and location mask in
+// registers together with the values the evaluate kernels compute two to four times (the two exponentials, the probability's
+// h), so each input array is read once per row and each gradient array is written once.  Longer rows are a MemRow, as in
+// masked_eval_*_kernel.
 //
 // The sums of the five per-row terms are taken in double, without atomics, in an order fixed by E alone: a workgroup owns
 // `4 * iters` consecutive rows and publishes one partial, at most kA2cWidth partials exist, one final workgroup adds them.
@@ -25,183 +25,36 @@ struct A2cArgs {
     float cE, g_ent, g_bad, c_v, c_p;
 };
 
-// d loss / d p_k of masked_eval_bwd_kernel (its `hk`), given lg = logf(clamp(p)): the entropy term, and the log-probability
-// term on the entry that is the action taken
-__device__ __forceinline__ float a2c_hk(bool taken, float p, float lg, float gl, float ge) {
-    const bool inside = p > kProbEps && p < 1.0f - kProbEps;
-    const float pc = fminf(fmaxf(p, kProbEps), 1.0f - kProbEps);
-    float h = -ge * (lg + (inside ? p / pc : 0.0f));
-    if (taken) h += inside ? gl / pc : 0.0f;
-    return h;
-}
-
-__device__ __forceinline__ float a2c_logp(const float *x, const float *m, int M, int64_t a, float mq, float sq, float tot) {
-    const float pa = (a >= 0 && a < M) ? (expf(x[a] - (1.0f - m[a]) * 14.0f - mq) / sq + 1e-5f) / tot : kProbEps;
-    return logf(fminf(fmaxf(pa, kProbEps), 1.0f - kProbEps));
-}
-
-// Row e with NJ entries per lane in registers (M <= 64 * NJ).  out = {adv * adv, -(adv * logp), ent, bad, sq}, in every lane.
+// Row e through row_stats and row_terms (bpp_heads.inl): NJ > 0 entries per lane in registers (M <= 64 * NJ), NJ = 0 a row of
+// any length walked in memory.  out = {adv * adv, -(adv * logp), ent, bad, sq}, in every lane.
 template <int NJ>
 __device__ __forceinline__ void a2c_row(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
+    constexpr bool kRegs = NJ > 0;
     const int M = a.M;
     const size_t off = e * (size_t)M;
     const float *x = a.logits + off, *m = a.mask + off;
-    float *g = a.g_logits + off;
-    float xv[NJ], om[NJ];       // logit; 1 - mask
-    float s = 0.0f;
-    if (a.pred) {               // every load of the row is issued before any arithmetic
-        float mv[NJ], pv[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = lane + kWave * j;
-            const bool ok = k < M;
-            xv[j] = ok ? x[k] : 0.0f;
-            mv[j] = ok ? m[k] : 0.0f;
-            pv[j] = ok ? a.pred[off + k] : 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = lane + kWave * j;
-            if (k < M) {
-                const float d = pv[j] - mv[j];
-                s += d * d;
-                a.g_pred[off + k] = a.c_p * d;
-            }
-            om[j] = 1.0f - mv[j];
-        }
-        s = wave_sum_f(s);
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = lane + kWave * j;
-            const bool ok = k < M;
-            xv[j] = ok ? x[k] : 0.0f;
-            om[j] = 1.0f - (ok ? m[k] : 0.0f);
-        }
-    }
-    const float adv = a.returns[e] - a.values[e];
-    const int64_t act = a.action[e];
-    const float gl = -(adv * a.cE), ge = a.g_ent, gb = a.g_bad;
-    // masked_row_stats
-    float q[NJ], av[NJ];        // masked logit -> its exponential -> q; exponential of the plain softmax -> av
-    float mq = -INFINITY, ma = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-        if (lane + kWave * j < M) {
-            q[j] = xv[j] - om[j] * 14.0f;
-            mq = fmaxf(mq, q[j]);
-            ma = fmaxf(ma, xv[j]);
-        }
-    mq = wave_max_f(mq);
-    ma = wave_max_f(ma);
-    float sq = 0.0f, sa = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-        if (lane + kWave * j < M) {
-            q[j] = expf(q[j] - mq);
-            av[j] = expf(xv[j] - ma);
-            sq += q[j];
-            sa += av[j];
-        }
-    sq = wave_sum_f(sq);
-    sa = wave_sum_f(sa);
-    float tot = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-        if (lane + kWave * j < M) {
-            q[j] = q[j] / sq;
-            tot += q[j] + 1e-5f;
-        }
-    tot = wave_sum_f(tot);
-    // masked_eval_fwd_kernel's entropy and bad mass; masked_eval_bwd_kernel's c
-    float hv[NJ];               // h_k
-    float h = 0.0f, b = 0.0f, c = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = lane + kWave * j;
-        if (k < M) {
-            const float p = (q[j] + 1e-5f) / tot;
-            const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
-            h -= p * lg;
-            av[j] = av[j] / sa;
-            b += av[j] * om[j];
-            hv[j] = a2c_hk(k == act, p, lg, gl, ge);
-            c += p * hv[j];
-        }
-    }
-    h = wave_sum_f(h);
-    b = wave_sum_f(b);
-    c = wave_sum_f(c);
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-        if (lane + kWave * j < M) v += q[j] * (hv[j] - c) / tot;
-    v = wave_sum_f(v);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = lane + kWave * j;
-        if (k < M) {
-            const float u = (hv[j] - c) / tot;
-            g[k] = q[j] * (u - v) + gb * av[j] * (om[j] - b);
-        }
-    }
-    const float logp = a2c_logp(x, m, M, act, mq, sq, tot);
-    if (lane == 0) a.g_values[e] = a.c_v * adv;
-    out[0] = adv * adv, out[1] = -(adv * logp), out[2] = h, out[3] = b, out[4] = s;
-}
-
-// The same for a row of any length: the loops of masked_eval_fwd_kernel and masked_eval_bwd_kernel over memory.
-__device__ __forceinline__ void a2c_row_looped(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
-    const int M = a.M;
-    const size_t off = e * (size_t)M;
-    const float *x = a.logits + off, *m = a.mask + off;
-    float *g = a.g_logits + off;
+    std::conditional_t<kRegs, RegRow<kRegs ? NJ : 1>, MemRow> row(x, m, M, lane);
     float s = 0.0f;
     if (a.pred) {
-        for (int k = lane; k < M; k += kWave) {
-            const float d = a.pred[off + k] - m[k];
+        float pv[kRegs ? NJ : 1];       // the register form: every load of the row is issued before any arithmetic
+        if constexpr (kRegs) row.each([&](int j, int k) { pv[j] = a.pred[off + k]; });
+        row.each([&](int j, int k) {
+            const float d = (kRegs ? pv[j] : a.pred[off + k]) - row.m(j, k);
             s += d * d;
             a.g_pred[off + k] = a.c_p * d;
-        }
-        s = wave_sum_f(s);
+        });
+        s = wave_sum(s);
     }
     const float adv = a.returns[e] - a.values[e];
-    const int64_t act = a.action[e];
-    const float gl = -(adv * a.cE), ge = a.g_ent, gb = a.g_bad;
-    const RowStats r = masked_row_stats(x, m, M, lane);
-    float h = 0.0f, b = 0.0f, c = 0.0f;
-    for (int k = lane; k < M; k += kWave) {
-        const float p = (expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq + 1e-5f) / r.tot;
-        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
-        h -= p * lg;
-        b += expf(x[k] - r.ma) / r.sa * (1.0f - m[k]);
-        c += p * a2c_hk(k == act, p, lg, gl, ge);
-    }
-    h = wave_sum_f(h);
-    b = wave_sum_f(b);
-    c = wave_sum_f(c);
-    float v = 0.0f;
-    for (int k = lane; k < M; k += kWave) {
-        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
-        const float p = (q + 1e-5f) / r.tot;
-        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
-        v += q * (a2c_hk(k == act, p, lg, gl, ge) - c) / r.tot;
-    }
-    v = wave_sum_f(v);
-    for (int k = lane; k < M; k += kWave) {
-        const float q = expf(x[k] - (1.0f - m[k]) * 14.0f - r.mq) / r.sq;
-        const float p = (q + 1e-5f) / r.tot;
-        const float lg = logf(fminf(fmaxf(p, kProbEps), 1.0f - kProbEps));
-        const float u = (a2c_hk(k == act, p, lg, gl, ge) - c) / r.tot;
-        const float avk = expf(x[k] - r.ma) / r.sa;
-        g[k] = q * (u - v) + gb * avk * ((1.0f - m[k]) - b);
-    }
-    const float logp = a2c_logp(x, m, M, act, r.mq, r.sq, r.tot);
+    const HeadGrad w{a.action[e], -(adv * a.cE), a.g_ent, a.g_bad};
+    float h, b;
+    const RowStats r = row_stats(row);
+    row_terms<true, true>(row, r, w, a.g_logits + off, h, b);
+    const float logp = action_logp(x, m, M, w.act, r);
     if (lane == 0) a.g_values[e] = a.c_v * adv;
     out[0] = adv * adv, out[1] = -(adv * logp), out[2] = h, out[3] = b, out[4] = s;
 }
 
-// NJ = 0: the looped form
 template <int NJ>
 __global__ __launch_bounds__(256) void a2c_loss_kernel(A2cArgs a) {
     static __shared__ double part[4][5];
@@ -212,8 +65,7 @@ __global__ __launch_bounds__(256) void a2c_loss_kernel(A2cArgs a) {
         const size_t e = e0 + 4u * (size_t)i + (size_t)wave;
         if (e >= (size_t)a.E) break;       // a whole wave: its later rows lie further out still
         float r[5];
-        if constexpr (NJ > 0) a2c_row<NJ>(a, e, lane, r);
-        else a2c_row_looped(a, e, lane, r);
+        a2c_row<NJ>(a, e, lane, r);
 #pragma unroll
         for (int j = 0; j < 5; ++j) acc[j] = acc[j] + (double)r[j];
         if (lane == 0 && a.rows) {

@@ -18,6 +18,7 @@ from oracle import ref_shims
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import a2c_cases as ac  # noqa: E402
+import head_normative as hn  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BADARG = -1
@@ -86,6 +87,17 @@ def test_terms_and_gradients_against_float64_autograd_of_the_reference(results, 
     # the two gradients that are one float32 product each
     np.testing.assert_allclose(out["grad_values"], ref["grad_values"], rtol=4 * ac.EPS, atol=0)
     np.testing.assert_allclose(out["grad_pred_mask"], ref["grad_pred_mask"], rtol=4 * ac.EPS, atol=0)
+
+
+@pytest.mark.parametrize("M", hn.MS)
+def test_rows_and_gradient_equal_the_normative_statement_bit_for_bit(emu_lib, M):
+    """Against tests/head_normative.py, which shares no code with the kernels (the check above compares them with each other)."""
+    c, want = hn.case(M)
+    out = ac.run_host(emu_lib, c)
+    assert out["rc"] == 0
+    rows = np.stack([-(c["adv"] * want["logp"]), want["ent"], want["bad"]], axis=1)
+    np.testing.assert_array_equal(hn.bits(out["rows"][:, 1:4]), hn.bits(rows))
+    np.testing.assert_array_equal(hn.bits(out["grad_logits"]), hn.bits(want["grad"]))
 
 
 def test_other_coefficients(emu, emu_lib):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import head_normative as hn
 from test_masked_act import make_case
 
 
@@ -71,6 +72,17 @@ def test_oracle_masked_evaluate_matches_torch_autograd(oracle, E, M):
 def test_emulated_masked_evaluate_matches_torch_autograd(emu, E, M):
     """The product kernels (wave-level reductions included), compiled by g++ against the SIMT emulator."""
     check(emu.masked_evaluate, emu.masked_evaluate_backward, E, M, seed=E + M)
+
+
+@pytest.mark.parametrize("M", hn.MS)
+def test_emulated_masked_evaluate_equals_the_normative_statement_bit_for_bit(emu, M):
+    """Both evaluate kernels against tests/head_normative.py, which shares no code with them: every register template of the
+    update kernel on both sides of its edge, the looped path with a tail, fewer entries than lanes; actions -1 and M."""
+    c, want = hn.case(M)
+    got = dict(zip(("logp", "ent", "bad"), emu.masked_evaluate(c["x"], c["m"], c["a"])))
+    got["grad"] = emu.masked_evaluate_backward(c["x"], c["m"], c["a"], *c["g"])
+    for k in ("logp", "ent", "bad", "grad"):
+        np.testing.assert_array_equal(hn.bits(got[k]), hn.bits(want[k]), err_msg=k)
 
 
 def test_oracle_masked_evaluate_against_the_reference_policy(oracle):

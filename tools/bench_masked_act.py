@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Timing of bpp_masked_act against the equivalent PyTorch ops of Policy.act
-(acktr/model.py:56-68, acktr/distributions.py:71-84).  HBM-bound: reads 2 * 4M bytes per bin."""
+(acktr/model.py:56-68, acktr/distributions.py:71-84).  HBM-bound: reads 2 * 4M bytes per bin.
+
+    python tools/bench_masked_act.py [bins]        (default 65 536)"""
 import json
 import os
 import sys
@@ -9,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bpp_amd
 
-E = 65536
+E = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 out = {}
 for M in (100, 200, 400):
     x = torch.randn(E, M, device="cuda")
@@ -62,6 +64,24 @@ for M in (100, 200, 400):
     a = torch.randint(0, M, (E,), device="cuda")
     adv = torch.randn(E, 1, device="cuda")
     xg = x.clone().requires_grad_(True)
+    # its two kernels alone, as above: 200 launches back to back through the C ABI, one event pair
+    outs = [torch.empty(E, device="cuda") for _ in range(3)]
+    gw = [torch.randn(E, device="cuda") for _ in range(3)]
+    grad = torch.empty_like(x)
+    alone = {"evaluate": lambda: L.bpp_masked_evaluate(x.data_ptr(), m.data_ptr(), a.data_ptr(), *[o.data_ptr() for o in outs], E, M, sp),
+             "evaluate_backward": lambda: L.bpp_masked_evaluate_backward(x.data_ptr(), m.data_ptr(), a.data_ptr(), *[g.data_ptr() for g in gw],
+                                                                         grad.data_ptr(), E, M, sp)}
+    for name, call in alone.items():
+        for t in range(20):
+            call()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for t in range(200):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        res["kernel_us_back_to_back_%s" % name] = round(e0.elapsed_time(e1) / 200 * 1e3, 2)
 
     def fused_eval(t):
         xg.grad = None
