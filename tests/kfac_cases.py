@@ -17,7 +17,10 @@ BADARG = -1
 
 
 def conv_of(k=1, s=1, p=0):
-    return dict(kernel_size=(k, k), stride=(s, s), padding=(p, p))
+    """k, s, p: an int for a square kernel / stride / padding, or a pair (height, width)."""
+    def pair(v):
+        return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+    return dict(kernel_size=pair(k), stride=pair(s), padding=pair(p))
 
 
 def geom(case):
@@ -155,6 +158,33 @@ EXACT = {
 }
 
 
+def _wide(layout, shape, seed, conv=None):
+    c = dict(layout=layout, x=_ints(shape, seed), kind=None, running=True)
+    if conv:
+        c["conv"] = conv
+    return c
+
+
+# the geometries the header accepts beyond the shipped layers
+EXACT.update({
+    "patch_c10_d90": _wide(PATCH, (3, 10, 4, 5), 1, conv_of(3, 1, 1)),                # a block that straddles channels, D no multiple of 64
+    "patch_c15_d135": _wide(PATCH, (2, 15, 3, 3), 2, conv_of(3, 1, 1)),               # three blocks
+    "patch_k2x3_s2x1_p0x2": _wide(PATCH, (3, 5, 5, 4), 3, conv_of((2, 3), (2, 1), (0, 2))),
+    "patch_k3x2_s1x3_p2x0": _wide(PATCH, (2, 12, 3, 7), 4, conv_of((3, 2), (1, 3), (2, 0))),
+    "patch_1x1_c130": _wide(PATCH, (2, 130, 3, 3), 5, conv_of(1, 1, 0)),
+    "patch_one_position": _wide(PATCH, (5, 8, 3, 3), 6, conv_of(3, 1, 0)),
+    "patch_k5_c3": _wide(PATCH, (2, 3, 6, 5), 7, conv_of(5, 1, 2)),
+    "nchw_d70_s65": _wide(NCHW, (2, 70, 5, 13), 8),                                   # two feature blocks; chunks of 33 and 32 positions
+    "nchw_d130_s25": _wide(NCHW, (3, 130, 5, 5), 9),
+    "nchw_d33_s1": _wide(NCHW, (7, 33, 1, 1), 10),                                    # one position per sample
+    "nchw_d8_s129": _wide(NCHW, (2, 8, 3, 43), 11),                                   # three chunks of 43
+    "rows_r129_d65": _wide(ROWS, (129, 65), 12),
+    "rows_r1_d200": _wide(ROWS, (1, 200), 13),
+    "rows_r65_d32": _wide(ROWS, (65, 32), 14),
+    "rows_r3_d31": _wide(ROWS, (3, 31), 15),
+})
+
+
 def check_exact(run, case):
     """Every product, sum and scaling is exact in float32, so the result equals an int64 evaluation bit for bit whatever the
     order.  running: also a second accumulation with rho = 0.5 onto the first result (c1 = 1, c2 = 0.5: exact)."""
@@ -204,7 +234,45 @@ REAL = {
     "rows_d400": lambda: real_case(ROWS, (15, 400), 18, "linear_a"),
     "rows_d256": lambda: real_case(ROWS, (15, 256), 19, "linear_g"),
     "rows_d100": lambda: real_case(ROWS, (15, 100), 20, "linear_g"),
+    "patch_c10_d90": lambda: real_case(PATCH, (3, 10, 10, 10), 22, "conv_a", conv_of(3, 1, 1)),
+    "patch_k3x2_s1x3_p2x0": lambda: real_case(PATCH, (3, 12, 7, 9), 23, "conv_a", conv_of((3, 2), (1, 3), (2, 0))),
+    "nchw_d130": lambda: real_case(NCHW, (3, 130, 5, 5), 24, "conv_g"),
+    "nchw_d70_s65": lambda: real_case(NCHW, (2, 70, 5, 13), 25, "conv_g"),
+    "rows_r129_d65": lambda: real_case(ROWS, (129, 65), 26, "linear_a"),
 }
+
+# ---- the recorded bits of the emulator's fmaf chains on real-valued data (tests/golden/make_mfma_chain_bits.py) ----------------
+# name -> the arguments of real_case: x and x2 come from numpy.random.RandomState alone, so every machine regenerates them
+CHAIN_CASES = {
+    "kfac_patch_c10": (PATCH, (3, 10, 10, 10), 31, "conv_a", conv_of(3, 1, 1)),
+    "kfac_patch_c15": (PATCH, (3, 15, 10, 10), 32, "conv_a", conv_of(3, 1, 1)),
+    "kfac_nchw_d64": (NCHW, (3, 64, 10, 10), 33, "conv_g"),
+    "kfac_rows_r15_d100": (ROWS, (15, 100), 34, "linear_g"),
+    "kfac_rows_r129_d65": (ROWS, (129, 65), 35, "linear_a"),
+}
+
+
+def crc(a):
+    import zlib
+    return np.uint32(zlib.crc32(np.ascontiguousarray(a).tobytes()))
+
+
+def chain_entries(run, name):
+    """{key: array} of one case for the fixture: the CRC32 of the bytes of both batches, the bits of m after the first batch
+    and after the second (rho = 0.99, the scale of reference_scale); and the case itself."""
+    case = real_case(*CHAIN_CASES[name])
+    D = rows64(case).shape[1]
+    m1 = run(case, case["x"], np.full((D, D), np.nan, np.float32), True, case["scale"], case["rho"])
+    m2 = run(case, case["x2"], m1, False, case["scale"], case["rho"])
+    return {name + ".crc.x": crc(case["x"]), name + ".crc.x2": crc(case["x2"]), name + ".m1": bits(m1), name + ".m2": bits(m2)}, case
+
+
+def ulps(a, b):
+    """The largest distance of two float32 arrays, given as bits, in units of the last place."""
+    def ordered(x):
+        i = np.ascontiguousarray(x).view(np.uint32).astype(np.int64)
+        return np.where(i & 0x80000000, 0x80000000 - i, i)
+    return int(np.abs(ordered(a) - ordered(b)).max())
 
 
 def split_case(rows_per_split, D=40):

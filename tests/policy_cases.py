@@ -1,6 +1,6 @@
 """Shared cases of the policy-forward tests (tests/test_policy_forward.py on the emulator, tests/test_gpu_policy_forward.py on the
-device): exact-integer networks whose outputs are known in int64, real-valued networks on states of a recorded rollout with a
-float64 reference, and the runners that call bpp_policy_forward (include/bpp_policy.h) with host or device pointers."""
+device): exact-integer networks whose outputs are known in int64, real-valued networks on states of a recorded rollout (10 x 10) or
+on synthetic states (every other side) with a float64 reference, the inputs of the recorded chain bits, and the runners that call bpp_policy_forward (include/bpp_policy.h) with host or device pointers."""
 import ctypes
 import os
 
@@ -133,12 +133,41 @@ def exact_case(S, H, M, n, seed, stride=None):
                 want=dict(value=value.reshape(n).astype(np.float32), logits=logits.astype(np.float32), pred=pred.astype(np.float32)))
 
 
-def exact_specs(P, T):
+# The accepted geometries beyond the shipped 10 x 10 network: (S, H, M, bins relative to the P of that side or None, n, seed).
+# n is what the seed was chosen for (exact_case asserts its own preconditions); where `relative` is k, n means P + k for the
+# side's own P and exact_specs takes P from bpp_policy_forward_info.
+WIDE_SPECS = {
+    "s1_h32_m2": (1, 32, 2, 1, 3, 42),            # A = 1: K1 = 8 and 4 (a Linear shorter than one batch of MFMAs), 2 rows in a tile of 32
+    "s2_h32_m4": (2, 32, 4, 1, 3, 40),            # both bins in one partial tile
+    "s3_h64_m9": (3, 64, 9, 1, 3, 40),            # H = 64: two of a wave's four column tiles exist
+    "s4_h96_m32": (4, 96, 32, None, 2, 40),       # rows = 32 exactly, M = 2 A = one column tile, H = 96
+    "s7_h160_m49": (7, 160, 49, None, 2, 40),     # PW odd, PP = 81; H = 160: the second column group has one tile
+    "s8_h288_m64": (8, 288, 64, None, 2, 40),     # a second pass over H with 32 columns
+    "s5_h288_m50": (5, 288, 50, 1, 3, 40),
+    "s9_h32_m81": (9, 32, 81, None, 2, 40),       # PW = 11
+    "s11_h32_m121": (11, 32, 121, 1, 2, 40),      # one bin per trunk workgroup, PP = 169
+    "s14_h32_m196": (14, 32, 196, 2, 3, 40),      # PP = 257
+    "s12_h64_m288": (12, 64, 288, 1, 2, 40),      # PP = 197, M = 2 A > 256: the second Linear loops
+    "s13_h320_m169": (13, 320, 169, None, 1, 40),
+    "s15_h512_m225": (15, 512, 225, None, 1, 40), # the largest side and hidden size: both LDS budgets near 150 KB
+    "s15_h512_m450": (15, 512, 450, 1, 2, 40),    # and the largest M
+    "s5_h512_nT1": (5, 512, 25, None, 65, 40),   # two full passes over H, T + 1 bins
+}
+
+
+def exact_specs(P, T, bins=None):
     """name -> arguments of exact_case: the smallest shapes at which each mechanism can go wrong.  P: bins per trunk
-    workgroup, T: bins per head tile (both from bpp_policy_forward_info)."""
+    workgroup at 10 x 10, T: bins per head tile (both from bpp_policy_forward_info); bins: geom -> the bins per trunk workgroup of
+    that geometry (None: the names are all that is wanted, n is the figure of WIDE_SPECS)."""
     specs = {"s10_n1": (10, 256, 100, 1, 1), "s10_nP1": (10, 256, 100, P + 1, 2), "s10_rot_n3": (10, 256, 200, 3, 3),
              "s5_n1": (5, 32, 25, 1, 4), "s5_n2": (5, 32, 25, 2, 5), "s5_nP1": (5, 32, 25, P + 1, 6), "s5_nT1": (5, 32, 25, T + 1, 7),
              "s6_rot": (6, 32, 72, 2, 8), "s5_stride": (5, 32, 25, 3, 9, 4 * 25 + 3)}
+    for name, (S, H, M, relative, n, seed) in WIDE_SPECS.items():
+        if name.endswith("_nT1"):
+            n = T + 1
+        elif bins is not None and relative is not None:
+            n = bins((S, H, M)) + relative
+        specs[name] = (S, H, M, n, seed)
     return specs
 
 
@@ -173,13 +202,83 @@ def deep_states(rot, count=16):
 
 def real_case(rot, seed=11):
     S, H, M = 10, 256, 200 if rot else 100
-    plain = real_weights(S, H, M, seed)
-    obs = deep_states(rot)
+    return with_references((S, H, M), real_weights(S, H, M, seed), deep_states(rot))
+
+
+# The shapes of the real-valued cases beyond 10 x 10.  Sides up to 3 are left out: the float32 torch forward of a 9-term network
+# is no stable yardstick (ratios up to 6.3 were seen for the logits) and at S = 1 the pred head is identically zero; the exact
+# cases and the recorded chain bits (tests/golden/make_mfma_chain_bits.py) cover those sides.
+WIDE_REAL = [(15, 512, 450), (15, 512, 225), (13, 320, 338), (12, 96, 144), (7, 160, 49)]
+
+
+def synthetic_states(S, count=16, seed=5):
+    """`count` observation rows [count, 4 A] float32 for a side no rollout was recorded at: plane 0 integers uniform in [0, S],
+    planes 1 - 3 each one constant from [1, max(1, S // 2)] (an item's extents).  Sixteen states, as deep_states gives: on three
+    the float32 torch error of the value head is three numbers' luck."""
+    rng = np.random.RandomState(seed)
+    A = S * S
+    obs = np.empty((count, 4, A), np.float32)
+    obs[:, 0] = rng.randint(0, S + 1, (count, A))
+    obs[:, 1:] = rng.randint(1, max(1, S // 2) + 1, (count, 3))[:, :, None]
+    return obs.reshape(count, 4 * A)
+
+
+def with_references(geom, plain, obs):
+    """The case dict of real_case for any weights and states: the float64 and the float32 torch forward beside the blob."""
     with torch.no_grad():
         ref64 = pol.torch_forward({k: v.double() for k, v in plain.items()}, torch.from_numpy(obs).double())
         ref32 = pol.torch_forward(plain, torch.from_numpy(obs))
-    return dict(geom=(S, H, M), obs=obs, plain=plain, blob=pol.pack_weights(plain, S, H, M).numpy(),
+    return dict(geom=tuple(geom), obs=obs, plain=plain, blob=pol.pack_weights(plain, *geom).numpy(),
                 ref64={h: t.numpy() for h, t in zip(HEADS, ref64)}, ref32={h: t.numpy() for h, t in zip(HEADS, ref32)})
+
+
+def wide_real_case(S, H, M, seed=11):
+    return with_references((S, H, M), real_weights(S, H, M, seed), synthetic_states(S))
+
+
+# ---- the recorded bits of the emulator's fmaf chains on real-valued data (tests/golden/make_mfma_chain_bits.py) ----------------
+CHAIN_FIXTURE = "mfma_chain_emulator_bits"
+CHAIN_CASES = [(10, 256, 100, 3), (5, 32, 25, 3), (3, 64, 9, 3), (12, 96, 144, 2), (15, 512, 450, 2)]        # (S, H, M, n)
+
+
+def chain_name(S, H, M, n):
+    return "policy_s%d_h%d_m%d_n%d" % (S, H, M, n)
+
+
+def chain_case(S, H, M, n, seed=7):
+    """Inputs that numpy.random.RandomState alone determines, so that every machine regenerates the same bytes: weights normal
+    * sqrt(2 / fan_in), biases uniform in +-0.1, the states of synthetic_states.  dict(geom, obs, blob, plain)."""
+    rng = np.random.RandomState(seed)
+    plain = {}
+    for name, shape in pol.layer_shapes(S, H, M):
+        fan_in = int(np.prod(shape[1:]))
+        plain[name + ".weight"] = torch.from_numpy((rng.standard_normal(shape) * np.sqrt(2.0 / fan_in)).astype(np.float32))
+        plain[name + ".bias"] = torch.from_numpy(rng.uniform(-0.1, 0.1, shape[0]).astype(np.float32))
+    return dict(geom=(S, H, M), obs=synthetic_states(S, n), plain=plain, blob=pol.pack_weights(plain, S, H, M).numpy())
+
+
+def crc(a):
+    import zlib
+    return np.uint32(zlib.crc32(np.ascontiguousarray(a).tobytes()))
+
+
+def chain_entries(run, spec):
+    """{key: array} of one case for the fixture: the CRC32 of the bytes of each input and the bits of every head from `run`."""
+    case, name = chain_case(*spec), chain_name(*spec)
+    out = {name + ".crc.obs": crc(case["obs"]), name + ".crc.blob": crc(case["blob"])}
+    got = run(case["obs"], case["geom"], case["blob"])
+    for h in HEADS:
+        out[name + "." + h] = np.ascontiguousarray(got[h], np.float32).view(np.uint32)
+    return out
+
+
+def ulps(a, b):
+    """The largest distance of two float32 arrays (given as floats or as bits) in units of the last place."""
+    def ordered(x):
+        x = np.ascontiguousarray(x)
+        i = (x.view(np.uint32) if x.dtype != np.uint32 else x).astype(np.int64)
+        return np.where(i & 0x80000000, 0x80000000 - i, i)
+    return int(np.abs(ordered(a) - ordered(b)).max())
 
 
 def rel_err(out, ref64):

@@ -1,5 +1,6 @@
 """bpp_policy_forward and bpp_amd.NativePolicy on the device (include/bpp_policy.h): the cases and checks of
-tests/test_policy_forward.py through bpp_amd.policy_forward -- here the MFMA itself runs --, batch independence across runs,
+tests/test_policy_forward.py through bpp_amd.policy_forward -- here the MFMA itself runs, at the shipped shapes and across the
+accepted ones, and is compared with the emulator's recorded chain bits --, batch independence across runs,
 streams and a replayed graph, act(), and the reference's checkpoints: every recorded state of the 2 100 trajectories teacher-forced,
 then the whole-set evaluation of examples/evaluate_checkpoint.py --native.  Reads nothing of the reference."""
 import json
@@ -52,7 +53,8 @@ def tiled(case, n):
 
 @pytest.mark.parametrize("name", sorted(pc.exact_specs(2, 64)))
 def test_gpu_exact_integer_networks_equal_int64_numpy_bit_for_bit(bpp, tiles, name):
-    pc.check_exact(pc.device_runner(DEV), pc.exact_case(*pc.exact_specs(*tiles)[name]))
+    spec = pc.exact_specs(*tiles, bins=lambda g: pc.info(bpp._lib.lib(), g, 1)["bins_per_trunk_group"])[name]
+    pc.check_exact(pc.device_runner(DEV), pc.exact_case(*spec))
 
 
 @pytest.mark.parametrize("n", [257, 1025])
@@ -66,6 +68,87 @@ def test_gpu_real_networks_within_eight_times_the_float32_torch_error(bpp, rot):
     case = pc.real_case(rot)
     got = pc.device_runner(DEV)(case["obs"], case["geom"], case["blob"])
     pc.check_real(got, case["ref64"], case["ref32"], "device, rotation %d:" % rot)
+
+
+@pytest.mark.parametrize("geom", pc.WIDE_REAL, ids=lambda g: "s%d_h%d_m%d" % tuple(g))
+def test_gpu_real_networks_at_the_other_accepted_shapes(bpp, geom):
+    """16 synthetic states against the float64 forward under the same rule; the ratios are printed."""
+    case = pc.wide_real_case(*geom)
+    pc.check_real(pc.device_runner(DEV)(case["obs"], case["geom"], case["blob"]), case["ref64"], case["ref32"], "device, %r:" % (geom,))
+
+
+@pytest.mark.parametrize("geom", [(12, 96, 144), (15, 512, 450)], ids=lambda g: "s%d_h%d_m%d" % tuple(g))
+def test_gpu_a_bin_gives_the_same_bits_where_every_workgroup_is_another_bin(bpp, geom):
+    """P = 1: one state alone, and as first / middle / last row of n = 3."""
+    assert pc.info(bpp._lib.lib(), geom, 3)["bins_per_trunk_group"] == 1
+    run = pc.device_runner(DEV)
+    blob = pc.pol.pack_weights(pc.real_weights(*geom, 11), *geom).numpy()
+    states = pc.synthetic_states(geom[0], 4)
+    one = run(states[3:4], geom, blob)
+    for rows in ((3, 0, 3), (1, 3, 2)):
+        got = run(states[list(rows)], geom, blob)
+        for at, r in enumerate(rows):
+            for h in pc.HEADS:
+                assert pc.same_bits(got[h][at], one[h][0]) == (r == 3), (h, rows, at)
+
+
+def test_gpu_a_bin_gives_the_same_bits_over_two_passes_of_the_hidden_layer(bpp, tiles):
+    """(5, 512, 25): n = 1, n = T + 1 in rows 0, 32 and 64, and a view whose rows lie 103 floats apart."""
+    P, T = tiles
+    policy = bpp.NativePolicy(5, 25, 512).load_state_dict(pc.real_weights(5, 512, 25, 11)).to(DEV)
+    states = torch.from_numpy(pc.synthetic_states(5, T + 2)).to(DEV)
+    one = policy(states[T + 1:])
+    batch = states[:T + 1].clone()
+    batch[[0, T // 2, T]] = states[T + 1]
+    got = policy(batch)
+    for at in (0, T // 2, T):
+        assert all(torch.equal(a[at], b[0]) for a, b in zip(got, one)), at
+        assert not torch.equal(got[1][at + 1 if at < T else 1], one[1][0])
+    padded = torch.full((P + 1, 103), 9.0, device=DEV)
+    padded[:, :100] = states[:P + 1]
+    padded[P, :100] = states[T + 1]
+    got = policy(padded[:, :100])
+    assert padded[:, :100].stride(0) == 103 and all(torch.equal(a[P], b[0]) for a, b in zip(got, one))
+
+
+def test_gpu_the_largest_policy_grows_its_workspace_and_acts(bpp):
+    """NativePolicy(15, 450, 512): n = 1, then n = 70 -- the workspace of this stream and geometry grows -- gives the n = 1 bits in
+    its row; act() on the 70 bins is masked_act on the same logits."""
+    policy = bpp.NativePolicy(15, 450, 512).load_state_dict(pc.real_weights(15, 512, 450, 11)).to(DEV)
+    states = torch.from_numpy(pc.synthetic_states(15, 70)).to(DEV)
+    key = (states.device, torch.cuda.current_stream(DEV).cuda_stream, policy.geom)
+    pc.pol._WORKSPACE.pop(key, None)
+    one = [t.clone() for t in policy(states[41:42])]
+    small = pc.pol._WORKSPACE[key].numel()
+    out = policy(states)
+    assert small == 20 * 225 and pc.pol._WORKSPACE[key].numel() == 70 * small
+    assert all(torch.equal(a[41], b[0]) for a, b in zip(out, one)) and not torch.equal(out[1][40], one[1][0])
+    again = policy(states[41:42])                                                   # the grown workspace serves n = 1 as well
+    assert pc.pol._WORKSPACE[key].numel() == 70 * small and all(torch.equal(a, b) for a, b in zip(again, one))
+    mask = torch.from_numpy((np.random.RandomState(3).rand(70, 450) < 0.3).astype(np.float32)).to(DEV)
+    mask[:, 7] = 1.0
+    for det, kw in ((True, {}), (False, dict(seed=5, step=3))):
+        value, action, logp = policy.act(states, mask, deterministic=det, **kw)
+        a2, lp2 = bpp.masked_act(out[1], mask, deterministic=det, **kw)
+        assert torch.equal(action, a2) and torch.equal(logp, lp2) and action.shape == (70, 1)
+        assert torch.equal(value.reshape(-1), out[0])
+
+
+def test_gpu_the_mfma_gives_the_bits_of_the_emulators_fmaf_chain(bpp):
+    """tests/golden/mfma_chain_emulator_bits.npz: real-valued networks at five shapes, every head.  The inputs are regenerated
+    here and their CRC32 compared first; then v_mfma_f32_32x32x2_f32 on the device against the sequential fmaf chain of the
+    emulator, bit for bit.  The largest distance per case is printed in float32 ulps."""
+    g = load_golden(pc.CHAIN_FIXTURE)
+    for spec in pc.CHAIN_CASES:
+        got = pc.chain_entries(pc.device_runner(DEV), spec)
+        name = pc.chain_name(*spec)
+        for key in got:
+            if ".crc." in key:
+                assert got[key] == g[key], ("%s: the inputs regenerated here are not the bytes tests/golden/make_mfma_chain_bits.py "
+                                            "drew (numpy's RandomState or the packing, not the kernel)" % key)
+        dist = {h: pc.ulps(got[name + "." + h], g[name + "." + h]) for h in pc.HEADS}
+        print("%s: device against emulator, ulps per head: %r" % (name, dist))
+        assert all(d == 0 for d in dist.values()), (name, dist)
 
 
 def test_gpu_a_bin_gives_the_same_bits_in_every_batch_run_and_stream(bpp, tiles, real_policy):

@@ -68,6 +68,15 @@ def test_real_cases_within_the_derived_bound_symmetric_and_repeatable(emu_lib, r
         assert i["splits"] == 3 and i["R"] == 2 * i["rows_per_split"] + 1
 
 
+def test_the_recorded_chain_bits_are_what_the_emulator_computes(emu_lib):
+    """tests/golden/mfma_chain_emulator_bits.npz (make_mfma_chain_bits.py) against the emulator as it is now: the fixture the
+    device is compared with cannot drift from the code."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "mfma_chain_emulator_bits.npz"))
+    for name in kc.CHAIN_CASES:
+        for key, v in kc.chain_entries(kc.host_runner(emu_lib), name)[0].items():
+            assert np.array_equal(g[key], v), "%s: rerun tests/golden/make_mfma_chain_bits.py if the change is meant" % key
+
+
 def _reference_factor(case, x, m0, first):
     """compute_cov_a / compute_cov_g and update_running_stat of the live reference on float32 tensors."""
     from acktr.algo import kfac as ref

@@ -1,7 +1,7 @@
 """bpp_policy_forward (include/bpp_policy.h) and bpp_amd.NativePolicy without a GPU: the product kernels of
 csrc/bpp_policy.inl compiled by g++ against the SIMT emulator, bound with _lib.bind_policy.  Exact-integer networks bit for bit
-against int64 numpy; real-valued networks against a float64 forward within 8 x the error of the float32 torch forward; batch
-independence; optional heads; the refusals of the header on the product library, which has no device here; the three
+against int64 numpy at the shipped shapes and across the accepted ones (S = 1 .. 15, H = 32 .. 512); real-valued networks against a
+float64 forward within 8 x the error of the float32 torch forward; batch independence; the recorded chain bits; optional heads; the refusals of the header on the product library, which has no device here; the three
 state-dict forms; the live reference's own Policy.  Helpers: tests/policy_cases.py."""
 import ctypes
 import os
@@ -61,7 +61,21 @@ def real_results(emu_lib):
 
 @pytest.mark.parametrize("name", sorted(pc.exact_specs(2, 64)))
 def test_exact_integer_networks_equal_int64_numpy_bit_for_bit(emu_lib, tiles, name):
-    pc.check_exact(pc.host_runner(emu_lib), pc.exact_case(*pc.exact_specs(*tiles)[name]))
+    spec = pc.exact_specs(*tiles, bins=lambda g: pc.info(emu_lib, g, 1)["bins_per_trunk_group"])[name]
+    pc.check_exact(pc.host_runner(emu_lib), pc.exact_case(*spec))
+
+
+def test_info_tells_one_bin_per_trunk_group_from_side_11_on(lib, emu_lib):
+    for L in (lib, emu_lib):
+        for S in range(1, 16):
+            for H, M in ((32, S * S), (512, 2 * S * S)):
+                i = pc.info(L, (S, H, M), 3)
+                assert i["bins_per_trunk_group"] == (2 if S <= 10 else 1), S
+                assert i["trunk_lds_bytes"] <= 160 * 1024 and i["trunk_groups"] == -(-3 // i["bins_per_trunk_group"])
+        assert pc.info(L, (15, 512, 450), 1)["trunk_lds_bytes"] == 151296
+    for name, (S, H, M, relative, n, seed) in pc.WIDE_SPECS.items():        # n of a spec is what "P + k" comes to for its side
+        if relative is not None:
+            assert pc.exact_specs(2, 64, bins=lambda g: pc.info(emu_lib, g, 1)["bins_per_trunk_group"])[name][3] == n, name
 
 
 @pytest.mark.parametrize("rot", [False, True])
@@ -70,6 +84,61 @@ def test_real_networks_within_eight_times_the_float32_torch_error(real_results, 
     and 2.5 for every head (printed)."""
     case, got = real_results(rot)
     pc.check_real(got, case["ref64"], case["ref32"], "emulator, rotation %d:" % rot)
+
+
+@pytest.mark.parametrize("geom", pc.WIDE_REAL, ids=lambda g: "s%d_h%d_m%d" % tuple(g))
+def test_real_networks_at_the_other_accepted_shapes(emu_lib, geom):
+    """Emulator, 16 synthetic states, against the float64 forward under the same rule.  Measured here: e_native / e_torch32
+    between 1.1 and 3.7 for every head (printed)."""
+    case = pc.wide_real_case(*geom)
+    pc.check_real(pc.host_runner(emu_lib)(case["obs"], case["geom"], case["blob"]), case["ref64"], case["ref32"], "emulator, %r:" % (geom,))
+
+
+@pytest.mark.parametrize("geom", [(12, 96, 144), (15, 512, 450)], ids=lambda g: "s%d_h%d_m%d" % tuple(g))
+def test_a_bin_gives_the_same_bits_where_every_workgroup_is_another_bin(emu_lib, geom):
+    """P = 1: one state alone, and as first / middle / last row of n = 3."""
+    assert pc.info(emu_lib, geom, 3)["bins_per_trunk_group"] == 1
+    run = pc.host_runner(emu_lib)
+    S = geom[0]
+    blob = pc.pol.pack_weights(pc.real_weights(*geom, 11), *geom).numpy()
+    states = pc.synthetic_states(S, 4)
+    one = run(states[3:4], geom, blob)
+    for rows in ((3, 0, 3), (1, 3, 2)):                                 # first and last in one batch, the middle in another
+        got = run(states[list(rows)], geom, blob)
+        for at, r in enumerate(rows):
+            for h in pc.HEADS:
+                assert pc.same_bits(got[h][at], one[h][0]) == (r == 3), (h, rows, at)
+
+
+def test_a_bin_gives_the_same_bits_over_two_passes_of_the_hidden_layer(emu_lib, tiles):
+    """(5, 512, 25): n = 1, n = T + 1 in rows 0, 32 and 64 (both row tiles, the second head tile), and under a padded stride."""
+    P, T = tiles
+    geom = (5, 512, 25)
+    run = pc.host_runner(emu_lib)
+    blob = pc.pol.pack_weights(pc.real_weights(*geom, 11), *geom).numpy()
+    states = pc.synthetic_states(5, T + 2)
+    one = run(states[T + 1:], geom, blob)
+    batch = states[:T + 1].copy()
+    batch[[0, T // 2, T]] = states[T + 1]
+    got = run(batch, geom, blob)
+    for at in (0, T // 2, T):
+        for h in pc.HEADS:
+            assert pc.same_bits(got[h][at], one[h][0]) and not pc.same_bits(got[h][at + 1 if at < T else 1], one[h][0]), (h, at)
+    padded = np.full((P + 1, 103), 9.0, np.float32)
+    padded[:, :100] = states[:P + 1]
+    padded[P, :100] = states[T + 1]
+    got = run(padded, geom, blob)
+    for h in pc.HEADS:
+        assert pc.same_bits(got[h][P], one[h][0]), h
+
+
+def test_the_recorded_chain_bits_are_what_the_emulator_computes(emu_lib):
+    """tests/golden/mfma_chain_emulator_bits.npz (make_mfma_chain_bits.py) against the emulator as it is now: the fixture the
+    device is compared with cannot drift from the code."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", pc.CHAIN_FIXTURE + ".npz"))
+    for spec in pc.CHAIN_CASES:
+        for key, v in pc.chain_entries(pc.host_runner(emu_lib), spec).items():
+            assert np.array_equal(g[key], v), "%s: rerun tests/golden/make_mfma_chain_bits.py if the change is meant" % key
 
 
 def test_a_bin_gives_the_same_bits_in_every_batch(emu_lib, tiles, real_results):
