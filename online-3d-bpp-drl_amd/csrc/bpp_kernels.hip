@@ -658,6 +658,13 @@ void with_sample_width(int per, F &&f) {
     }
 }
 
+// f(std::integral_constant<int, FB>{}) for the field width FB (stream_field_bits: 4 or 8) the stream's cut kernels are compiled for.
+template <typename F>
+void with_field_bits(int fb, F &&f) {
+    if (fb == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
 // Tuning knobs (include/bpp_abi.h: bpp_knobs).  Initialised ONCE per process from the environment
 // (BPP_EPW, BPP_WPB, BPP_XCD, BPP_FORCE_GENERIC, BPP_ABLATE), afterwards only bpp_set_knobs changes them:
 // a launch never looks at the environment.
@@ -1120,30 +1127,28 @@ int stream_refill(const bpp_stream *s, void *stream, int kmax, int urgent) {
     const int E = s->num_envs;
     hipLaunchKernelGGL(stream_scan_kernel, dim3((E + kScanThreads - 1) / kScanThreads), dim3(kScanThreads), 2 * (kScanThreads / 64) * 4 * sizeof(int), st,
                        *s, w0);
-    if (p.rows && current_knobs().stream_legacy != 2) {     // counter generator, one lane per sequence, no sort kernel
-        StreamWork w = w0;
-        if (current_knobs().stream_legacy == 3) w.cap = w.cap < 10 ? w.cap : 10, w.stage = w.stage < 24 ? w.stage : 24;
-        const int64_t waves = ((int64_t)E * s->depth + 63) / 64;
-        // one wave per 64 rows, all at once: a grid bounded to 256 / 512 / 1 024 waves that walk through the rows -- the refill
-        // spread over more of the window -- costs the lock-steps beside it MORE (profiles/r5x_*: -10 / -6 / -2 %)
-        const unsigned grid = (unsigned)(waves < 8192 ? waves : 8192);
-        if (p.fb == 4) hipLaunchKernelGGL(stream_cut_rows_kernel<4>, dim3(grid), dim3(64), p.rows_lds, st, *s, w);
-        else hipLaunchKernelGGL(stream_cut_rows_kernel<8>, dim3(grid), dim3(64), p.rows_lds, st, *s, w);
-        return launched();
-    }
-    const StreamWork &w = w0;
-    if (s->rng == BPP_STREAM_RNG_COUNTER) {      // no generator state: nothing to regenerate, the lists are all the LDS a cut wave needs
-        const size_t lds = (size_t)stream_cut_lds_bytes(p.cap, p.fb) - (size_t)64 * kRingStride;
-        if (p.fb == 4) hipLaunchKernelGGL(stream_cut_ctr_kernel<4>, dim3(p.nslots / 64), dim3(64), lds, st, *s, w);
-        else hipLaunchKernelGGL(stream_cut_ctr_kernel<8>, dim3(p.nslots / 64), dim3(64), lds, st, *s, w);
-    } else {
-        hipLaunchKernelGGL(stream_pretwist_kernel, dim3((unsigned)((E + 3) / 4 < 2048 ? (E + 3) / 4 : 2048)), dim3(256),
-                           4 * kTwistWords * sizeof(uint32_t), st, *s, w);
-        if (p.fb == 4) hipLaunchKernelGGL(stream_cut_kernel<4>, dim3(p.nslots / 64), dim3(64), p.cut_lds, st, *s, w);
-        else hipLaunchKernelGGL(stream_cut_kernel<8>, dim3(p.nslots / 64), dim3(64), p.cut_lds, st, *s, w);
-    }
-    const int64_t most = ((int64_t)E * s->depth + 3) / 4;
-    hipLaunchKernelGGL(stream_sort_kernel, dim3((unsigned)(most < 2048 ? most : 2048)), dim3(256), p.sort_lds, st, *s, w);
+    with_field_bits(p.fb, [&](auto fb) {
+        constexpr int FB = decltype(fb)::value;
+        if (p.rows && current_knobs().stream_legacy != 2) {     // counter generator, one lane per sequence, no sort kernel
+            StreamWork w = w0;
+            if (current_knobs().stream_legacy == 3) w.cap = w.cap < 10 ? w.cap : 10, w.stage = w.stage < 24 ? w.stage : 24;
+            const int64_t waves = ((int64_t)E * s->depth + 63) / 64;
+            // one wave per 64 rows, all at once: a grid bounded to 256 / 512 / 1 024 waves that walk through the rows -- the refill
+            // spread over more of the window -- costs the lock-steps beside it MORE (profiles/r5x_*: -10 / -6 / -2 %)
+            hipLaunchKernelGGL(stream_cut_rows_kernel<FB>, dim3((unsigned)(waves < 8192 ? waves : 8192)), dim3(64), p.rows_lds, st, *s, w);
+            return;
+        }
+        const StreamWork &w = w0;
+        if (s->rng == BPP_STREAM_RNG_COUNTER) {      // no generator state: nothing to regenerate, the lists are all the LDS a cut wave needs
+            hipLaunchKernelGGL(stream_cut_ctr_kernel<FB>, dim3(p.nslots / 64), dim3(64), p.cut_lds - (size_t)64 * kRingStride, st, *s, w);
+        } else {
+            hipLaunchKernelGGL(stream_pretwist_kernel, dim3((unsigned)((E + 3) / 4 < 2048 ? (E + 3) / 4 : 2048)), dim3(256),
+                               4 * kTwistWords * sizeof(uint32_t), st, *s, w);
+            hipLaunchKernelGGL(stream_cut_kernel<FB>, dim3(p.nslots / 64), dim3(64), p.cut_lds, st, *s, w);
+        }
+        const int64_t most = ((int64_t)E * s->depth + 3) / 4;
+        hipLaunchKernelGGL(stream_sort_kernel, dim3((unsigned)(most < 2048 ? most : 2048)), dim3(256), p.sort_lds, st, *s, w);
+    });
     return launched();
 }
 

@@ -12,6 +12,16 @@
 // the plain-C one of include/bpp_gen.inl): same draws in the same order, so sequence k of a bin equals the k-th
 // sequence `random.Random(seed0 + id)` yields through the reference creator.  It is written once for host and
 // device: `Rng` supplies u32(), `Work` the pending-box list.
+//
+// Where one VISIT of that list walk (a split attempt, :59-130) is stated:
+//   cut2_generate                      the plain statement, host and device (bpp_gen_cut2, the stream_legacy = 1 kernel);
+//   walk_apply / walk_apply_general    what a decided visit does to a lane's lists and row in the fast pipelines, once
+//                                      without branches (lists in LDS) and once in plain form (lists of any length), on
+//                                      one walk state (Walk) and one side choice (long_sides*);
+//   cut_visit_lds / _general / _ctr / _ctr_general   only how the two draws of a visit are obtained: rejection loops over
+//                                      the lane's ring of MT19937 outputs, or two calls of CtrRng::below.
+// Ring addresses (ring_row), the terminator (stream_terminator) and the look-ahead hand-over (lookahead_slot,
+// place_lookahead) are stated once for every writer of the ring.
 
 // pending box: a = x | y << 8 | z << 16, b = low | high << 8 | alive << 31   (sides and heights <= 255)
 struct CutBox {
@@ -149,6 +159,13 @@ __host__ __device__ inline int cut2_generate(Rng &rng, Work &work, Vals &vals, i
 }
 
 // ---- CPython's random.Random on MT19937 with the state words at a stride (1 everywhere today) -------------------------------
+__host__ __device__ inline uint32_t mt_temper(uint32_t y) {
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return y;
+}
 struct StridedMT {
     uint32_t *mt;
     size_t stride;
@@ -195,12 +212,7 @@ struct StridedMT {
             }
             idx = 0;
         }
-        uint32_t y = w(idx++);
-        y ^= y >> 11;
-        y ^= (y << 7) & 0x9d2c5680u;
-        y ^= (y << 15) & 0xefc60000u;
-        y ^= y >> 18;
-        return y;
+        return mt_temper(w(idx++));
     }
     __host__ __device__ uint32_t below(uint32_t n) { return getrandbits_below(*this, n); }
 };
@@ -240,14 +252,6 @@ __host__ __device__ inline uint8_t *mt_out8(uint32_t *rec) { return (uint8_t *)(
 constexpr int kCtrRec = 4;      // BPP_STREAM_RNG_COUNTER: words per bin -- the 64-bit stream id (+ 2 reserved)
 
 __host__ __device__ inline int stream_work_entries(int W, int L, int H, int lo) { return W * L * H / (lo * lo * lo) + 8; }
-
-__host__ __device__ inline uint32_t mt_temper(uint32_t y) {
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-}
 
 // ======================================================================================================================
 // Refill, fast pipeline: four kernels per bpp_stream_refill.
@@ -301,6 +305,33 @@ constexpr int kTopUpEvery = 8;         // iterations between top-ups
 constexpr int kTwistWords = 640;       // scratch of a wave-wide twist (624 used)
 constexpr int kSortMaxT = 2048;        // longest row the sort kernel stages in LDS
 constexpr int kScanThreads = 1024;
+
+// Ring row of `episode` of bin `bin`: kRowHdr look-ahead entries, then the items.
+__device__ __forceinline__ uint32_t *ring_row(const bpp_stream &s, int episode, int bin) {
+    const size_t E = (size_t)s.num_envs, T = (size_t)s.pool_len;
+    const int D = s.depth;
+    return (uint32_t *)s.ring + ((size_t)(episode % D) * E + bin) * T;
+}
+// The whole bin as a pending box of FB-bit fields (base height 0); with byte fields it is the item that ends a row.
+template <int FB>
+__device__ __forceinline__ uint32_t bin_box(const bpp_stream &s) {
+    return (uint32_t)s.W | ((uint32_t)s.L << FB) | ((uint32_t)s.H << (2 * FB));
+}
+__device__ __forceinline__ uint32_t stream_terminator(const bpp_stream &s) { return bin_box<8>(s); }
+// Where item k (0 / 1) of row `episode` is repeated for the steps that look ahead: item 1 in entry 0 of the row before,
+// item 0 in entry 1 of the row two before.  has_lookahead: the bin has that row.
+__device__ __forceinline__ bool has_lookahead(int episode, int k) { return episode >= 2 - k; }
+__device__ __forceinline__ uint32_t *lookahead_slot(const bpp_stream &s, int bin, int episode, int k) {
+    return ring_row(s, episode - 2 + k, bin) + (1 - k);
+}
+__device__ __forceinline__ void place_lookahead(const bpp_stream &s, int bin, int episode, uint32_t item0, uint32_t item1) {
+    if (has_lookahead(episode, 1)) *lookahead_slot(s, bin, episode, 1) = item1;
+    if (has_lookahead(episode, 0)) *lookahead_slot(s, bin, episode, 0) = item0;
+}
+__device__ __forceinline__ uint64_t ctr_stream_id(const bpp_stream &s, int bin) {     // BPP_STREAM_RNG_COUNTER: the bin's record
+    const uint32_t *rc = s.mt + (size_t)bin * kCtrRec;
+    return (uint64_t)rc[0] | ((uint64_t)rc[1] << 32);
+}
 
 // LDS entries per pending list for sequences of at most maxn boxes.  Measured peaks: 10^3 bins 10 on average, above 16
 // in 0.5 % of the sequences, 21 at most in 3000; 20^3 bins 68.  Longer lists continue in global memory (the wave then
@@ -457,15 +488,177 @@ struct PendLists {
 };
 
 // State of one lane's list walk.  A pending box is x | y << FB | z << 2 FB | base height << 3 FB (its top is base + z).
-struct CutLane {
-    uint32_t box, v;        // box being visited; side being cut (valid in state 1)
-    int st, f;              // 0: the next output chooses the side (random.choice), 1: it is the cut position (randint)
+struct Walk {
+    uint32_t box;           // box being visited
     int i, tail_a, tail_b;  // position in this pass's list, its length, length of the survivors' list
     int side;               // which LDS list is this pass's (0 / 1)
     int nv;                 // boxes cut so far
-    uint32_t *row;
+    uint32_t *row;          // the ring row's items
+};
+__device__ __forceinline__ Walk walk_begin(uint32_t whole, uint32_t *row) { return Walk{whole, 0, 1, 0, 0, 0, row}; }
+// (wave-uniform use) a list of the lane may leave its LDS part during the next visit
+__device__ __forceinline__ bool walk_may_spill(const Walk &c, int cap) { return c.tail_a + 2 > cap || c.tail_b + 1 > cap; }
+struct CutLane : Walk {     // MT19937: a visit may take several iterations
+    uint32_t v;             // side being cut (valid in state 1)
+    int st, f;              // 0: the next output chooses the side (random.choice), 1: it is the cut position (randint)
     int used;               // outputs consumed since the job started
 };
+struct CtrLane : Walk {     // counter generator: a visit is always decided in the iteration that starts it
+    CtrRng rng;
+};
+
+// ---- predicates as all-ones / zero words.  On this part a v_cndmask_b32 costs as much as five to nine plain vector
+// instructions (tools/ubench.hip: 9.8 ns per wave against 1.1 - 1.8 ns), so the branch-free visit below selects with
+// and / or / bit-field-insert on such masks instead.  All operands are small non-negative numbers (< 2^31).
+__device__ __forceinline__ uint32_t m_lt(uint32_t a, uint32_t b) { return (uint32_t)((int32_t)(a - b) >> 31); }   // a < b
+__device__ __forceinline__ uint32_t m_eq(uint32_t a, uint32_t b) { return m_lt(a ^ b, 1u); }
+__device__ __forceinline__ uint32_t m_sel(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }       // m ? a : b
+
+// ---- the part of a visit both generators share ----------------------------------------------------------------------
+// The sides of `box` that exceed hi (mdCreator.py:60-66) and random.choice among them (:68) for the draw x < their
+// number nf (returned): the x-th long side in the order x, y, z.  Once in mask form (mfx / mfy: x / y is long), once plain.
+template <int FB>
+__device__ __forceinline__ uint32_t long_sides_m(uint32_t box, uint32_t hi, uint32_t &mfx, uint32_t &mfy) {
+    constexpr uint32_t FM = (1u << FB) - 1u;
+    mfx = m_lt(hi, box & FM), mfy = m_lt(hi, (box >> FB) & FM);
+    return 0u - (mfx + mfy + m_lt(hi, (box >> (2 * FB)) & FM));
+}
+__device__ __forceinline__ uint32_t chosen_side_m(uint32_t mfx, uint32_t mfy, uint32_t x) {
+    const uint32_t f0 = (2u + mfy) & ~mfx;                                              // first long side
+    const uint32_t f1 = 2u + (mfx & mfy);                                               // second long side
+    return m_sel(m_lt(x, 1u), f0, m_sel(m_eq(x, 1u), f1, 2u));
+}
+template <int FB>
+__device__ __forceinline__ uint32_t long_sides(uint32_t box, uint32_t hi, bool &fx, bool &fy) {
+    constexpr uint32_t FM = (1u << FB) - 1u;
+    fx = (box & FM) > hi, fy = ((box >> FB) & FM) > hi;
+    return (uint32_t)fx + (uint32_t)fy + (uint32_t)(((box >> (2 * FB)) & FM) > hi);
+}
+__device__ __forceinline__ uint32_t chosen_side(bool fx, bool fy, uint32_t x) {
+    return x == 0u ? (fx ? 0u : (fy ? 1u : 2u)) : (x == 1u ? ((fx && fy) ? 1u : 2u) : 2u);
+}
+template <int FB>
+__device__ __forceinline__ uint32_t side_of(uint32_t box, uint32_t f) { return (box >> ((uint32_t)FB * f)) & ((1u << FB) - 1u); }
+
+// Where a visit's finished boxes go: straight into the ring row, unsorted (the sort kernel ranks them later) ...
+struct EmitToRow {
+    uint32_t *row;
+    __device__ __forceinline__ void operator()(uint32_t m, uint32_t nv, uint32_t v) const {
+        if (m) row[nv] = v;
+    }
+};
+// ... or into the lane's staging column in LDS (stream_cut_rows_kernel, which ranks them itself); entry `dummy` takes the
+// stores that do not apply;
+// there it is also counted (level `nolevel` for the stores that do not apply).  Level counters of a lane: two 16-bit counters
+// per word -- a row has fewer than 2 048 boxes --, level l in half l & 1 of word (l >> 1) * 64.
+__device__ __forceinline__ uint32_t level_count(uint32_t *cnt, uint32_t level) {      // returns the level's count before
+    const uint32_t sh = (level & 1u) * 16u;
+    return (atomicAdd(&cnt[(level >> 1) * 64], 1u << sh) >> sh) & 0xffffu;
+}
+template <class Col, int FB>
+struct EmitToStage {
+    Col st;
+    uint32_t *cnt;
+    uint32_t dummy, nolevel;
+    __device__ __forceinline__ void operator()(uint32_t m, uint32_t nv, uint32_t v) const {
+        st.set(m_sel(m, nv, dummy), v);
+        const uint32_t level = m_sel(m, v >> (3 * FB), nolevel);
+        atomicAdd(&cnt[(level >> 1) * 64], 1u << ((level & 1u) * 16u));
+    }
+};
+
+// A decided visit (mdCreator.py:69-100 benchmark_split for side f of length v and the cut position r, and its bookkeeping
+// in gen_benchmark, :110-130) for a lane whose lists are certain to stay inside LDS (!walk_may_spill): the statement of
+// walk_apply_general below without divergent branches and without selects on condition codes.  mdecided: all-ones for
+// a lane whose visit is decided in this iteration, zero for a lane that does nothing; monly: side f is the only long
+// one.  Returns the mask "sequence complete".
+template <int FB, class Col, class Emit>
+__device__ __forceinline__ uint32_t walk_apply(Walk &c, const Col col, int cap, uint32_t mdecided, uint32_t monly, uint32_t f, uint32_t v,
+                                               uint32_t r, uint32_t lo, uint32_t hi, const Emit emit) {
+    constexpr uint32_t FM = (1u << FB) - 1u;
+    const uint32_t dummy = 2u * (uint32_t)cap;
+    const uint32_t abase = (uint32_t)cap & (0u - (uint32_t)c.side), bbase = (uint32_t)cap - abase;
+    const uint32_t box = c.box;
+    const uint32_t mgood = ~(m_lt(r, lo) | m_lt(v - r, lo));                            // :74, :84, :94
+    const uint32_t msplit = mdecided & mgood, mfail = mdecided & ~mgood;
+    const uint32_t mf2 = m_eq(f, 2u);
+    const uint32_t sh = (uint32_t)FB * f, p1 = m_sel(mf2, v - r, r), p2 = v - p1;
+    const uint32_t rest = box & ~(FM << sh);
+    const uint32_t c1 = rest | (p1 << sh);
+    const uint32_t c2 = (rest | (p2 << sh)) + ((p1 << (3 * FB)) & mf2);                 // :97-98: the upper part starts at high - r
+    const uint32_t me1 = msplit & monly & ~m_lt(hi, p1), me2 = msplit & monly & ~m_lt(hi, p2);   // is_valid, :110-115
+    const uint32_t mq1 = msplit & ~me1, mq2 = msplit & ~me2;
+    uint32_t nv = (uint32_t)c.nv, tail_a = (uint32_t)c.tail_a, tail_b = (uint32_t)c.tail_b, i = (uint32_t)c.i;
+    emit(me1, nv, c1);
+    nv -= me1;
+    emit(me2, nv, c2);
+    nv -= me2;
+    col.set(m_sel(mfail, bbase + tail_b, dummy), box);            // stays in invalid_box for the next pass
+    tail_b -= mfail;
+    col.set(m_sel(mq1, abase + tail_a, dummy), c1);               // appended: visited later in this pass
+    tail_a -= mq1;
+    col.set(m_sel(mq2, abase + tail_a, dummy), c2);
+    tail_a -= mq2;
+    i -= mdecided;
+    // the two entries after the visited box (the first is skipped after a split, :124) and the head of the survivors
+    const uint32_t n1 = col.get(abase + min(i, (uint32_t)cap - 1u)), n2 = col.get(abase + min(i + 1u, (uint32_t)cap - 1u));
+    const uint32_t mskip = msplit & m_lt(i, tail_a);
+    col.set(m_sel(mskip, bbase + tail_b, dummy), n1);
+    tail_b -= mskip;
+    i -= mskip;
+    const uint32_t b0 = col.get(bbase);
+    const uint32_t mpass = mdecided & ~m_lt(i, tail_a);           // end of the `for`: next pass over the survivors, or done
+    const uint32_t mdone = mpass & m_eq(tail_b, 0u);
+    c.box = m_sel(mdecided, m_sel(mpass, b0, m_sel(mskip, n2, n1)), box);
+    c.side ^= (int)(mpass & 1u);
+    c.tail_a = (int)m_sel(mpass, tail_b, tail_a);
+    c.tail_b = (int)(tail_b & ~mpass);
+    c.i = (int)(i & ~mpass);
+    c.nv = (int)nv;
+    return mdone;
+}
+
+// The same in plain form, for one lane and lists of any length (entries beyond the LDS part live in global memory); nf:
+// the number of long sides.  Returns true when the sequence is complete.  This is the statement walk_apply is checked
+// against (tests/test_stream_supply.py, tests/test_stream_counter.py: geometries whose lists spill, bit for bit against
+// the oracle): a wave runs it whenever one of its lanes' lists may leave LDS.
+// (`f == 0 ? v <= lo : v < lo`, :71 / :81 / :91, cannot hold: the side was chosen because it exceeds hi, and bpp_stream
+// requires hi >= 2 lo - 1 >= lo; cut2_generate keeps the test.)
+template <int FB>
+__device__ __forceinline__ bool walk_apply_general(Walk &c, const PendLists<FB> &pend, uint32_t nf, uint32_t f, uint32_t v, uint32_t r,
+                                                   uint32_t lo, uint32_t hi) {
+    constexpr uint32_t FM = (1u << FB) - 1u;
+    const bool split = r >= lo && v - r >= lo;                                // :74, :84, :94
+    if (!split) {
+        pend.set(c.side ^ 1, c.tail_b++, c.box);                              // stays in invalid_box for the next pass
+    } else {
+        const uint32_t sh = (uint32_t)FB * f, p1 = f == 2u ? v - r : r, p2 = v - p1;
+        const uint32_t rest = c.box & ~(FM << sh);
+        const uint32_t c1 = rest | (p1 << sh);
+        const uint32_t c2 = (rest | (p2 << sh)) + (f == 2u ? p1 << (3 * FB) : 0u);    // :97-98: the upper part starts at high - r
+        // is_valid (:110-115): the untouched sides are within bounds iff the cut side was the only long one
+        if (nf == 1u && p1 <= hi) c.row[c.nv++] = c1;
+        else pend.set(c.side, c.tail_a++, c1);                                // appended: visited later in this pass
+        if (nf == 1u && p2 <= hi) c.row[c.nv++] = c2;
+        else pend.set(c.side, c.tail_a++, c2);
+    }
+    ++c.i;
+    if (split && c.i < c.tail_a) {                // the removal slid the next box under the iterator: not visited in this pass
+        pend.set(c.side ^ 1, c.tail_b++, pend.get(c.side, c.i));
+        ++c.i;
+    }
+    if (c.i < c.tail_a) {
+        c.box = pend.get(c.side, c.i);
+        return false;
+    }
+    const bool finished = c.tail_b == 0;          // end of the `for`: next pass over the survivors, or done
+    c.side ^= 1;
+    c.tail_a = c.tail_b;
+    c.tail_b = 0;
+    c.i = 0;
+    if (!finished) c.box = pend.get(c.side, 0);
+    return finished;
+}
 
 // The kCand output bytes that follow position `from` of the lane's ring, as two packed words (byte j of the run in bits
 // 8 j .. 8 j + 7 of lo for j < 4, of hi for j >= 4): three aligned dword reads (the repeated first bytes make the run
@@ -495,13 +688,6 @@ __device__ __forceinline__ void first_below(const uint8_t *ringb, int from, uint
     }
 }
 
-// ---- predicates as all-ones / zero words.  On this part a v_cndmask_b32 costs as much as five to nine plain vector
-// instructions (tools/ubench.hip: 9.8 ns per wave against 1.1 - 1.8 ns), so the branch-free visit below selects with
-// and / or / bit-field-insert on such masks instead.  All operands are small non-negative numbers (< 2^31).
-__device__ __forceinline__ uint32_t m_lt(uint32_t a, uint32_t b) { return (uint32_t)((int32_t)(a - b) >> 31); }   // a < b
-__device__ __forceinline__ uint32_t m_eq(uint32_t a, uint32_t b) { return m_lt(a ^ b, 1u); }
-__device__ __forceinline__ uint32_t m_sel(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }       // m ? a : b
-
 // `getrandbits(k) until below lim` on the kCand outputs that follow position `from` of the lane's ring: the first accepted
 // output wins.  Every output becomes a key -- position << 8 | value when accepted, above 0xffff when not -- and the
 // smallest key is the answer; the keys are independent of each other, which is what turns a visit's serial chain of
@@ -526,19 +712,14 @@ __device__ __forceinline__ uint32_t first_below_key(const uint8_t *ringb, int fr
 }
 __device__ __forceinline__ uint32_t bit_length(uint32_t v) { return 32u - (uint32_t)__clz((int)v); }   // v > 0
 
-// One visit for a lane whose lists are certain to stay inside LDS (tail_a + 2 <= cap, tail_b + 1 <= cap): the statement
-// of cut_visit_general below without divergent branches and without selects on condition codes.  `act` is the lane's
-// all-ones / zero activity mask; returns the mask "sequence complete".
+// The draws of one visit from the lane's ring of MT19937 outputs, or as many of them as it has outputs for, then
+// walk_apply for a visit that is decided.  `act` is the lane's all-ones / zero activity mask; returns the mask
+// "sequence complete".
 template <int FB>
 __device__ __forceinline__ uint32_t cut_visit_lds(CutLane &c, const ListCol<FB> col, int cap, const uint8_t *ringb, int filled, uint32_t act,
                                                   uint32_t lo, uint32_t hi) {
-    constexpr uint32_t FM = (1u << FB) - 1u;
-    const uint32_t dummy = 2u * (uint32_t)cap;
-    const uint32_t abase = (uint32_t)cap & (0u - (uint32_t)c.side), bbase = (uint32_t)cap - abase;
-    const uint32_t box = c.box;
-    const uint32_t bx = box & FM, by = (box >> FB) & FM, bz = (box >> (2 * FB)) & FM;
-    const uint32_t mfx = m_lt(hi, bx), mfy = m_lt(hi, by), mfz = m_lt(hi, bz);          // :60-66
-    const uint32_t nf = 0u - (mfx + mfy + mfz);
+    uint32_t mfx, mfy;
+    const uint32_t nf = long_sides_m<FB>(c.box, hi, mfx, mfy);
     const uint32_t monly = m_eq(nf, 1u);
     const uint32_t mst0 = (uint32_t)c.st - 1u;                                          // st is 0 or 1
     // random.choice(flags) (:68) -- getrandbits(1) for one long side, getrandbits(2) for two or three --, or
@@ -549,11 +730,9 @@ __device__ __forceinline__ uint32_t cut_visit_lds(CutLane &c, const ListCol<FB> 
     const uint32_t mfound1 = m_lt(first1, have1) & act;
     c.used += (int)(m_sel(mfound1, first1 + 1u, have1) & act);
     const uint32_t mchoose = mfound1 & mst0;
-    const uint32_t f0 = (2u + mfy) & ~mfx;                                              // first long side
-    const uint32_t f1 = 2u + (mfx & mfy);                                               // second long side
-    const uint32_t fnew = m_sel(m_lt(x1, 1u), f0, m_sel(m_eq(x1, 1u), f1, 2u));
+    const uint32_t fnew = chosen_side_m(mfx, mfy, x1);
     const uint32_t f = m_sel(mchoose, fnew, (uint32_t)c.f);
-    const uint32_t v = m_sel(mchoose, (box >> ((uint32_t)FB * fnew)) & FM, c.v);
+    const uint32_t v = m_sel(mchoose, side_of<FB>(c.box, fnew), c.v);
     // the cut position for a side chosen just now
     const uint32_t key2 = first_below_key(ringb, c.used, bit_length(v), v);
     const uint32_t have2 = (uint32_t)min(filled - c.used, kCand);
@@ -561,62 +740,19 @@ __device__ __forceinline__ uint32_t cut_visit_lds(CutLane &c, const ListCol<FB> 
     const uint32_t mfound2 = m_lt(first2, have2) & mchoose;
     c.used += (int)(m_sel(mfound2, first2 + 1u, have2) & mchoose);
     const uint32_t mfin = (mfound1 & ~mst0) | mfound2;                                  // the visit is decided
-    const uint32_t r = m_sel(mfound2, x2, x1) + 1u;
-    const uint32_t mgood = ~(m_lt(r, lo) | m_lt(v - r, lo));                            // :74, :84, :94
-    const uint32_t msplit = mfin & mgood, mfail = mfin & ~mgood;
-    const uint32_t mf2 = m_eq(f, 2u);
-    const uint32_t sh = (uint32_t)FB * f, p1 = m_sel(mf2, v - r, r), p2 = v - p1;
-    const uint32_t rest = box & ~(FM << sh);
-    const uint32_t c1 = rest | (p1 << sh);
-    const uint32_t c2 = (rest | (p2 << sh)) + ((p1 << (3 * FB)) & mf2);                 // :97-98: the upper part starts at high - r
-    const uint32_t me1 = msplit & monly & ~m_lt(hi, p1), me2 = msplit & monly & ~m_lt(hi, p2);   // is_valid, :110-115
-    const uint32_t mq1 = msplit & ~me1, mq2 = msplit & ~me2;
-    uint32_t nv = (uint32_t)c.nv, tail_a = (uint32_t)c.tail_a, tail_b = (uint32_t)c.tail_b, i = (uint32_t)c.i;
-    if (me1) c.row[nv] = c1;
-    nv -= me1;
-    if (me2) c.row[nv] = c2;
-    nv -= me2;
-    col.set(m_sel(mfail, bbase + tail_b, dummy), box);            // stays in invalid_box for the next pass
-    tail_b -= mfail;
-    col.set(m_sel(mq1, abase + tail_a, dummy), c1);               // appended: visited later in this pass
-    tail_a -= mq1;
-    col.set(m_sel(mq2, abase + tail_a, dummy), c2);
-    tail_a -= mq2;
     c.st = (int)(((uint32_t)c.st | (mchoose & 1u)) & ~mfin);
     c.f = (int)f;
     c.v = v;
-    i -= mfin;
-    // the two entries after the visited box (the first is skipped after a split, :124) and the head of the survivors
-    const uint32_t n1 = col.get(abase + min(i, (uint32_t)cap - 1u)), n2 = col.get(abase + min(i + 1u, (uint32_t)cap - 1u));
-    const uint32_t mskip = msplit & m_lt(i, tail_a);
-    col.set(m_sel(mskip, bbase + tail_b, dummy), n1);
-    tail_b -= mskip;
-    i -= mskip;
-    const uint32_t b0 = col.get(bbase);
-    const uint32_t mpass = mfin & ~m_lt(i, tail_a);               // end of the `for`: next pass over the survivors, or done
-    const uint32_t mdone = mpass & m_eq(tail_b, 0u);
-    c.box = m_sel(mfin, m_sel(mpass, b0, m_sel(mskip, n2, n1)), box);
-    c.side ^= (int)(mpass & 1u);
-    c.tail_a = (int)m_sel(mpass, tail_b, tail_a);
-    c.tail_b = (int)(tail_b & ~mpass);
-    c.i = (int)(i & ~mpass);
-    c.nv = (int)nv;
-    return mdone;
+    return walk_apply<FB>(c, col, cap, mfin, monly, f, v, m_sel(mfound2, x2, x1) + 1u, lo, hi, EmitToRow{c.row});
 }
 
-// One visit (mdCreator.py:59-100 benchmark_split and its bookkeeping in gen_benchmark :120-130), or the part of it the
-// lane has outputs for, in plain form: any list length (entries beyond the LDS part live in global memory).  `filled` =
-// outputs put into the ring so far.  Returns true when the sequence is complete.  This is the statement
-// cut_visit_lds above is checked against: a wave runs it whenever one of its lanes' lists may leave LDS.
-// (`f == 0 ? v <= lo : v < lo`, :71 / :81 / :91, cannot hold: the side was chosen because it exceeds hi, and bpp_stream
-// requires hi >= 2 lo - 1 >= lo; cut2_generate keeps the test.)
+// The same in plain form, with walk_apply_general: a wave runs it whenever one of its lanes' lists may leave LDS.
+// `filled` = outputs put into the ring so far.  Returns true when the sequence is complete.
 template <int FB>
 __device__ __forceinline__ bool cut_visit_general(CutLane &c, const PendLists<FB> &pend, const uint8_t *ringb, int filled, uint32_t lo,
                                                   uint32_t hi) {
-    constexpr uint32_t FM = (1u << FB) - 1u;
-    const uint32_t bx = c.box & FM, by = (c.box >> FB) & FM, bz = (c.box >> (2 * FB)) & FM;
-    const bool fx = bx > hi, fy = by > hi, fz = bz > hi;                    // :60-66
-    const uint32_t nf = (uint32_t)fx + (uint32_t)fy + (uint32_t)fz;
+    bool fx, fy;
+    const uint32_t nf = long_sides<FB>(c.box, hi, fx, fy);
     const bool st0 = c.st == 0;
     // first rejection loop of the iteration: random.choice(flags) (:68) = flags[getrandbits(bit_length(nf)) until < nf],
     // or, for a lane that chose its side earlier, random.randint(1, v) (:73 / :83 / :93) = 1 + (getrandbits(bit_length(v)) until < v)
@@ -628,8 +764,8 @@ __device__ __forceinline__ bool cut_visit_general(CutLane &c, const PendLists<FB
     c.used += found1 ? first1 + 1 : have1;
     const bool choose = found1 && st0;
     if (choose) {
-        c.f = x1 == 0u ? (fx ? 0 : (fy ? 1 : 2)) : (x1 == 1u ? ((fx && fy) ? 1 : 2) : 2);
-        c.v = c.f == 0 ? bx : (c.f == 1 ? by : bz);
+        c.f = (int)chosen_side(fx, fy, x1);
+        c.v = side_of<FB>(c.box, (uint32_t)c.f);
         c.st = 1;
     }
     // second one: the cut position for a side chosen just now
@@ -638,61 +774,59 @@ __device__ __forceinline__ bool cut_visit_general(CutLane &c, const PendLists<FB
     const bool found2 = choose && first2 < have2;
     if (choose) c.used += found2 ? first2 + 1 : have2;
     if (!((found1 && !st0) || found2)) return false;                         // the visit is not decided yet
-    const uint32_t r = (found2 ? x2 : x1) + 1u;
-    const bool split = r >= lo && c.v - r >= lo;                              // :74, :84, :94
     c.st = 0;
-    if (!split) {
-        pend.set(c.side ^ 1, c.tail_b++, c.box);                              // stays in invalid_box for the next pass
-    } else {
-        const uint32_t sh = (uint32_t)FB * (uint32_t)c.f, p1 = c.f == 2 ? c.v - r : r, p2 = c.v - p1;
-        const uint32_t rest = c.box & ~(FM << sh);
-        const uint32_t c1 = rest | (p1 << sh);
-        const uint32_t c2 = (rest | (p2 << sh)) + (c.f == 2 ? p1 << (3 * FB) : 0u);   // :97-98: the upper part starts at high - r
-        // is_valid (:110-115): the untouched sides are within bounds iff the cut side was the only long one
-        if (nf == 1u && p1 <= hi) c.row[c.nv++] = c1;
-        else pend.set(c.side, c.tail_a++, c1);                                // appended: visited later in this pass
-        if (nf == 1u && p2 <= hi) c.row[c.nv++] = c2;
-        else pend.set(c.side, c.tail_a++, c2);
-    }
-    ++c.i;
-    if (split && c.i < c.tail_a) {                // the removal slid the next box under the iterator: not visited in this pass
-        pend.set(c.side ^ 1, c.tail_b++, pend.get(c.side, c.i));
-        ++c.i;
-    }
-    if (c.i < c.tail_a) {
-        c.box = pend.get(c.side, c.i);
-        return false;
-    }
-    const bool finished = c.tail_b == 0;          // end of the `for`: next pass over the survivors, or done
-    c.side ^= 1;
-    c.tail_a = c.tail_b;
-    c.tail_b = 0;
-    c.i = 0;
-    if (!finished) c.box = pend.get(c.side, 0);
-    return finished;
+    return walk_apply_general<FB>(c, pend, nf, (uint32_t)c.f, c.v, (found2 ? x2 : x1) + 1u, lo, hi);
 }
 
-template <int FB>
-__global__ __launch_bounds__(64) void stream_cut_kernel(bpp_stream s, StreamWork w) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x;
-    const int E = s.num_envs, T = s.pool_len, D = s.depth, cap = w.cap;
-    const uint32_t lo = (uint32_t)s.bound_lo, hi = (uint32_t)s.bound_hi;
-    // This wave is one long dependency chain that uses a fraction of its SIMD's issue slots; beside the step kernel (eight
-    // waves per SIMD that want every slot) it must win the arbitration whenever it can issue, or the refill falls behind
-    // the lock-steps it runs beside.
-    __builtin_amdgcn_s_setprio(3);
-    // wave -> (bucket, position): the longest jobs are dispatched first
+// ---- the frame of the two per-bin cut kernels (one lane per job, single-wave workgroups) ----------------------------------
+struct CutJob {
+    bool job;               // the lane has a bin
+    int e, g, need;         // the bin, its next episode to generate, sequences still to cut
+};
+// wave -> (bucket, position), the longest jobs dispatched first; lane -> job.  False: the wave has nothing to do.
+__device__ __forceinline__ bool cut_job_of_lane(const bpp_stream &s, const StreamWork &w, int lane, CutJob &j) {
     const int n3 = w.hdr[2], n2 = w.hdr[1], n1 = w.hdr[0];
     const int w3 = (n3 + 63) >> 6, w2 = (n2 + 63) >> 6, w1 = (n1 + 63) >> 6;
     int b = blockIdx.x, n, bucket;
     if (b < w3) n = n3, bucket = 2;
     else if (b < w3 + w2) b -= w3, n = n2, bucket = 1;
     else if (b < w3 + w2 + w1) b -= w3 + w2, n = n1, bucket = 0;
-    else return;
-    const int j = b * 64 + lane;
-    const bool job = j < n;
-    const int e = job ? w.jobs[(size_t)bucket * E + j] : 0;
+    else return false;
+    const int q = b * 64 + lane;
+    j.job = q < n;
+    j.e = j.job ? w.jobs[(size_t)bucket * s.num_envs + q] : 0;
+    j.g = j.job ? s.gen_next[j.e] : 0;
+    j.need = j.job ? w.target[j.e] - j.g : 0;
+    return true;
+}
+// The lane's sequence is complete: its length into the row's last entry (for the sort kernel, which restores the
+// terminator), then the list re-seeded for the bin's next row.  False: the bin needs no further sequence.
+template <int FB>
+__device__ __forceinline__ bool cut_next_sequence(const bpp_stream &s, Walk &c, const PendLists<FB> &pend, CutJob &j) {
+    c.row[s.pool_len - 1 - kRowHdr] = (uint32_t)c.nv;
+    ++j.g;
+    if (--j.need <= 0) return false;
+    c.row = ring_row(s, j.g, j.e) + kRowHdr;
+    pend.set(c.side, 0, bin_box<FB>(s));
+    c.tail_a = 1;
+    c.nv = 0;
+    c.box = bin_box<FB>(s);
+    return true;
+}
+
+template <int FB>
+__global__ __launch_bounds__(64) void stream_cut_kernel(bpp_stream s, StreamWork w) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const int cap = w.cap;
+    const uint32_t lo = (uint32_t)s.bound_lo, hi = (uint32_t)s.bound_hi;
+    // This wave is one long dependency chain that uses a fraction of its SIMD's issue slots; beside the step kernel (eight
+    // waves per SIMD that want every slot) it must win the arbitration whenever it can issue, or the refill falls behind
+    // the lock-steps it runs beside.
+    __builtin_amdgcn_s_setprio(3);
+    CutJob j;
+    if (!cut_job_of_lane(s, w, lane, j)) return;
+    const int e = j.e;
     uint32_t *rec = s.mt + (size_t)e * kMtRec;
     const ListCol<FB> col{(typename ListCol<FB>::T *)smem + lane};      // entry w of this lane at index w * 64
     // outputs: byte p % 64 of this lane's run holds output p (counted from the job's start)
@@ -700,20 +834,17 @@ __global__ __launch_bounds__(64) void stream_cut_kernel(bpp_stream s, StreamWork
     uint32_t *tw = w.twist + (size_t)blockIdx.x * kTwistWords;        // twist scratch of the wave (global: the path is rare)
     const PendLists<FB> pend{col, w.spill + (size_t)blockIdx.x * 64 + lane, cap, w.nsp, (size_t)w.nslots};
 
-    int g = 0, need = 0, base = 0;                                   // base: index in the current state of the job's first output
+    int base = 0;                                                    // index in the current state of the job's first output
     uint32_t par = 0, next_ok = 0;
-    if (job) {
+    if (j.job) {
         base = (int)rec[kMtPos];
         par = rec[kMtPar];
         next_ok = rec[kMtNextOk];
-        g = s.gen_next[e];
-        need = w.target[e] - g;
     }
-    bool active = job && need > 0;
+    bool active = j.job && j.need > 0;
     const bool ran = active;
-    const uint32_t whole = (uint32_t)s.W | ((uint32_t)s.L << FB) | ((uint32_t)s.H << (2 * FB));
-    CutLane c{whole, 1u, 0, 0, 0, 1, 0, 0, 0, (uint32_t *)s.ring + ((size_t)(active ? g % D : 0) * E + e) * T + kRowHdr, 0};
-    if (active) col.set(0u, whole);
+    CutLane c{walk_begin(bin_box<FB>(s), ring_row(s, active ? j.g : 0, e) + kRowHdr), 1u, 0, 0, 0};
+    if (active) col.set(0u, c.box);
     int filled = 0;                                                  // outputs put into the ring since the job started (a multiple of 4)
 
     // The next kOutFetch output bytes after `filled`, loaded one top-up ahead as twelve packed words.  Outputs of the
@@ -766,24 +897,12 @@ __global__ __launch_bounds__(64) void stream_cut_kernel(bpp_stream s, StreamWork
             fetch();
         }
         bool finished;
-        if (__ballot(active && (c.tail_a + 2 > cap || c.tail_b + 1 > cap))) {   // wave-uniform: a list may leave LDS
+        if (__ballot(active && walk_may_spill(c, cap))) {   // wave-uniform
             finished = active ? cut_visit_general<FB>(c, pend, ringb, filled, lo, hi) : false;
         } else {
             finished = cut_visit_lds<FB>(c, col, cap, ringb, filled, active ? ~0u : 0u, lo, hi) != 0u;
         }
-        if (finished) {
-            c.row[T - 1 - kRowHdr] = (uint32_t)c.nv;  // (the row's last entry) length for the sort kernel, which restores the terminator
-            ++g;
-            if (--need > 0) {
-                c.row = (uint32_t *)s.ring + ((size_t)(g % D) * E + e) * T + kRowHdr;
-                pend.set(c.side, 0, whole);
-                c.tail_a = 1;
-                c.nv = 0;
-                c.box = whole;
-            } else {
-                active = false;
-            }
-        }
+        if (finished) active = cut_next_sequence<FB>(s, c, pend, j);
         ++it;
     }
     if (ran) {                                        // outputs in the ring that were not used are simply read again next time
@@ -796,213 +915,67 @@ __global__ __launch_bounds__(64) void stream_cut_kernel(bpp_stream s, StreamWork
         rec[kMtPos] = (uint32_t)pos;
         rec[kMtPar] = par;
         rec[kMtNextOk] = next_ok;
-        s.gen_next[e] = g;
+        s.gen_next[e] = j.g;
     }
 }
 
-// One wave per rewritten row: stable counting sort of the cut boxes by the height of their base (depart_box, :137-138),
-// sort key stripped, the rest of the row padded with the terminator.  Rows of at most 64 boxes (every 10^3 row: 47 at
-// most) never touch LDS: a lane holds one box, its place is the number of boxes with a lower base plus the number of
-// equal ones in lower lanes, counted with one ballot per distinct base height; the next row's boxes are loaded before
-// the current row is ranked.  Longer rows are staged in LDS and ranked chunk by chunk.
 // ======================================================================================================================
 // BPP_STREAM_RNG_COUNTER, fast pipeline: scan / cut / sort (no pretwist: there is no state to regenerate).  The cut kernel
 // is the list walk of stream_cut_kernel without everything the Mersenne Twister forced on it: a draw is a hash of (key,
 // draw index) -- no ring of outputs, no top-ups, no fetches --, a rejection happens once in 2^32 / lim draws -- no
-// eight-candidate min-trees, a visit is always decided in the iteration that starts it.  Same lists (ListCol / PendLists),
-// same unsorted row format, same sort kernel.
+// eight-candidate min-trees, a visit is always decided in the iteration that starts it.  Same walk (Walk, walk_apply /
+// walk_apply_general), same lists (ListCol / PendLists), same kernel frame, same unsorted row format, same sort kernel.
 // ======================================================================================================================
-struct CtrLane {
-    uint32_t box;
-    int i, tail_a, tail_b;  // position in this pass's list, its length, length of the survivors' list
-    int side;               // which LDS list is this pass's (0 / 1)
-    int nv;                 // boxes cut so far
-    uint32_t *row;
-    CtrRng rng;
-};
-
-// One visit for a lane whose lists are certain to stay inside LDS: mdCreator.py:59-100 + :120-130 without divergent
-// branches (the one that exists -- a rejected draw -- is taken by nobody in 2^32 / lim - 1 of 2^32 / lim cases).
-// Where a visit's finished boxes go: straight into the ring row, unsorted (the sort kernel ranks them later) ...
-struct EmitToRow {
-    uint32_t *row;
-    __device__ __forceinline__ void operator()(uint32_t m, uint32_t nv, uint32_t v) const {
-        if (m) row[nv] = v;
-    }
-};
-// ... or into the lane's staging column in LDS (stream_cut_rows_kernel, which ranks them itself); entry `dummy` takes the
-// stores that do not apply;
-// there it is also counted (level `nolevel` for the stores that do not apply).  Level counters of a lane: two 16-bit counters
-// per word -- a row has fewer than 2 048 boxes --, level l in half l & 1 of word (l >> 1) * 64.
-__device__ __forceinline__ uint32_t level_count(uint32_t *cnt, uint32_t level) {      // returns the level's count before
-    const uint32_t sh = (level & 1u) * 16u;
-    return (atomicAdd(&cnt[(level >> 1) * 64], 1u << sh) >> sh) & 0xffffu;
-}
-template <class Col, int FB>
-struct EmitToStage {
-    Col st;
-    uint32_t *cnt;
-    uint32_t dummy, nolevel;
-    __device__ __forceinline__ void operator()(uint32_t m, uint32_t nv, uint32_t v) const {
-        st.set(m_sel(m, nv, dummy), v);
-        const uint32_t level = m_sel(m, v >> (3 * FB), nolevel);
-        atomicAdd(&cnt[(level >> 1) * 64], 1u << ((level & 1u) * 16u));
-    }
-};
-
+// The two draws of one visit, then walk_apply: mdCreator.py:59-100 + :120-130 without divergent branches (the one that
+// exists -- a rejected draw -- is taken by nobody in 2^32 / lim - 1 of 2^32 / lim cases).
 template <int FB, class Col, class Emit>
 __device__ __forceinline__ uint32_t cut_visit_ctr(CtrLane &c, const Col col, int cap, uint32_t act, uint32_t lo, uint32_t hi, const Emit emit) {
-    constexpr uint32_t FM = (1u << FB) - 1u;
-    const uint32_t dummy = 2u * (uint32_t)cap;
-    const uint32_t abase = (uint32_t)cap & (0u - (uint32_t)c.side), bbase = (uint32_t)cap - abase;
-    const uint32_t box = c.box;
-    const uint32_t bx = box & FM, by = (box >> FB) & FM, bz = (box >> (2 * FB)) & FM;
-    const uint32_t mfx = m_lt(hi, bx), mfy = m_lt(hi, by), mfz = m_lt(hi, bz);          // :60-66
-    const uint32_t nf = max(0u - (mfx + mfy + mfz), 1u);                                // (1 for a lane without a box: no draw from 0)
-    const uint32_t monly = m_eq(nf, 1u);
-    const uint32_t x1 = c.rng.below(nf);                                                // random.choice(flags), :68
-    const uint32_t f0 = (2u + mfy) & ~mfx;                                              // first long side
-    const uint32_t f1 = 2u + (mfx & mfy);                                               // second long side
-    const uint32_t f = m_sel(m_lt(x1, 1u), f0, m_sel(m_eq(x1, 1u), f1, 2u));
-    const uint32_t v = max((box >> ((uint32_t)FB * f)) & FM, 1u);
+    uint32_t mfx, mfy;
+    const uint32_t nf = max(long_sides_m<FB>(c.box, hi, mfx, mfy), 1u);                 // (1 for a lane without a box: no draw from 0)
+    const uint32_t f = chosen_side_m(mfx, mfy, c.rng.below(nf));                        // random.choice(flags), :68
+    const uint32_t v = max(side_of<FB>(c.box, f), 1u);
     const uint32_t r = c.rng.below(v) + 1u;                                             // random.randint(1, v), :73 / :83 / :93
-    const uint32_t mgood = ~(m_lt(r, lo) | m_lt(v - r, lo));                            // :74, :84, :94
-    const uint32_t msplit = act & mgood, mfail = act & ~mgood;
-    const uint32_t mf2 = m_eq(f, 2u);
-    const uint32_t sh = (uint32_t)FB * f, p1 = m_sel(mf2, v - r, r), p2 = v - p1;
-    const uint32_t rest = box & ~(FM << sh);
-    const uint32_t c1 = rest | (p1 << sh);
-    const uint32_t c2 = (rest | (p2 << sh)) + ((p1 << (3 * FB)) & mf2);                 // :97-98: the upper part starts at high - r
-    const uint32_t me1 = msplit & monly & ~m_lt(hi, p1), me2 = msplit & monly & ~m_lt(hi, p2);   // is_valid, :110-115
-    const uint32_t mq1 = msplit & ~me1, mq2 = msplit & ~me2;
-    uint32_t nv = (uint32_t)c.nv, tail_a = (uint32_t)c.tail_a, tail_b = (uint32_t)c.tail_b, i = (uint32_t)c.i;
-    emit(me1, nv, c1);
-    nv -= me1;
-    emit(me2, nv, c2);
-    nv -= me2;
-    col.set(m_sel(mfail, bbase + tail_b, dummy), box);            // stays in invalid_box for the next pass
-    tail_b -= mfail;
-    col.set(m_sel(mq1, abase + tail_a, dummy), c1);               // appended: visited later in this pass
-    tail_a -= mq1;
-    col.set(m_sel(mq2, abase + tail_a, dummy), c2);
-    tail_a -= mq2;
-    i -= act;
-    // the two entries after the visited box (the first is skipped after a split, :124) and the head of the survivors
-    const uint32_t n1 = col.get(abase + min(i, (uint32_t)cap - 1u)), n2 = col.get(abase + min(i + 1u, (uint32_t)cap - 1u));
-    const uint32_t mskip = msplit & m_lt(i, tail_a);
-    col.set(m_sel(mskip, bbase + tail_b, dummy), n1);
-    tail_b -= mskip;
-    i -= mskip;
-    const uint32_t b0 = col.get(bbase);
-    const uint32_t mpass = act & ~m_lt(i, tail_a);                // end of the `for`: next pass over the survivors, or done
-    const uint32_t mdone = mpass & m_eq(tail_b, 0u);
-    c.box = m_sel(act, m_sel(mpass, b0, m_sel(mskip, n2, n1)), box);
-    c.side ^= (int)(mpass & 1u);
-    c.tail_a = (int)m_sel(mpass, tail_b, tail_a);
-    c.tail_b = (int)(tail_b & ~mpass);
-    c.i = (int)(i & ~mpass);
-    c.nv = (int)nv;
-    return mdone;
+    return walk_apply<FB>(c, col, cap, act, m_eq(nf, 1u), f, v, r, lo, hi, emit);
 }
-
-// The same visit in plain form for lists of any length (entries beyond the LDS part live in global memory): the
-// statement cut_visit_ctr is checked against; a wave runs it whenever one of its lanes' lists may leave LDS.
+// The same in plain form, with walk_apply_general: a wave runs it whenever one of its lanes' lists may leave LDS.
 template <int FB>
 __device__ __forceinline__ bool cut_visit_ctr_general(CtrLane &c, const PendLists<FB> &pend, uint32_t lo, uint32_t hi) {
-    constexpr uint32_t FM = (1u << FB) - 1u;
-    const uint32_t bx = c.box & FM, by = (c.box >> FB) & FM, bz = (c.box >> (2 * FB)) & FM;
-    const bool fx = bx > hi, fy = by > hi, fz = bz > hi;                    // :60-66
-    const uint32_t nf = (uint32_t)fx + (uint32_t)fy + (uint32_t)fz;
-    const uint32_t x1 = c.rng.below(nf);                                    // random.choice(flags), :68
-    const int f = x1 == 0u ? (fx ? 0 : (fy ? 1 : 2)) : (x1 == 1u ? ((fx && fy) ? 1 : 2) : 2);
-    const uint32_t v = f == 0 ? bx : (f == 1 ? by : bz);
-    const uint32_t r = c.rng.below(v) + 1u;                                 // random.randint(1, v)
-    const bool split = r >= lo && v - r >= lo;                              // :74, :84, :94
-    if (!split) {
-        pend.set(c.side ^ 1, c.tail_b++, c.box);                            // stays in invalid_box for the next pass
-    } else {
-        const uint32_t sh = (uint32_t)FB * (uint32_t)f, p1 = f == 2 ? v - r : r, p2 = v - p1;
-        const uint32_t rest = c.box & ~(FM << sh);
-        const uint32_t c1 = rest | (p1 << sh);
-        const uint32_t c2 = (rest | (p2 << sh)) + (f == 2 ? p1 << (3 * FB) : 0u);   // :97-98
-        if (nf == 1u && p1 <= hi) c.row[c.nv++] = c1;                       // is_valid (:110-115)
-        else pend.set(c.side, c.tail_a++, c1);
-        if (nf == 1u && p2 <= hi) c.row[c.nv++] = c2;
-        else pend.set(c.side, c.tail_a++, c2);
-    }
-    ++c.i;
-    if (split && c.i < c.tail_a) {                // the removal slid the next box under the iterator: not visited in this pass
-        pend.set(c.side ^ 1, c.tail_b++, pend.get(c.side, c.i));
-        ++c.i;
-    }
-    if (c.i < c.tail_a) {
-        c.box = pend.get(c.side, c.i);
-        return false;
-    }
-    const bool finished = c.tail_b == 0;          // end of the `for`: next pass over the survivors, or done
-    c.side ^= 1;
-    c.tail_a = c.tail_b;
-    c.tail_b = 0;
-    c.i = 0;
-    if (!finished) c.box = pend.get(c.side, 0);
-    return finished;
+    bool fx, fy;
+    const uint32_t nf = long_sides<FB>(c.box, hi, fx, fy);
+    const uint32_t f = chosen_side(fx, fy, c.rng.below(nf));                            // random.choice(flags), :68
+    const uint32_t v = side_of<FB>(c.box, f);
+    const uint32_t r = c.rng.below(v) + 1u;                                             // random.randint(1, v)
+    return walk_apply_general<FB>(c, pend, nf, f, v, r, lo, hi);
 }
 
 template <int FB>
 __global__ __launch_bounds__(64) void stream_cut_ctr_kernel(bpp_stream s, StreamWork w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    const int E = s.num_envs, T = s.pool_len, D = s.depth, cap = w.cap;
+    const int cap = w.cap;
     const uint32_t lo = (uint32_t)s.bound_lo, hi = (uint32_t)s.bound_hi;
-    // wave -> (bucket, position): the longest jobs are dispatched first
-    const int n3 = w.hdr[2], n2 = w.hdr[1], n1 = w.hdr[0];
-    const int w3 = (n3 + 63) >> 6, w2 = (n2 + 63) >> 6, w1 = (n1 + 63) >> 6;
-    int b = blockIdx.x, n, bucket;
-    if (b < w3) n = n3, bucket = 2;
-    else if (b < w3 + w2) b -= w3, n = n2, bucket = 1;
-    else if (b < w3 + w2 + w1) b -= w3 + w2, n = n1, bucket = 0;
-    else return;
-    const int j = b * 64 + lane;
-    const bool job = j < n;
-    const int e = job ? w.jobs[(size_t)bucket * E + j] : 0;
+    CutJob j;
+    if (!cut_job_of_lane(s, w, lane, j)) return;
     const ListCol<FB> col{(typename ListCol<FB>::T *)smem + lane};
     const PendLists<FB> pend{col, w.spill + (size_t)blockIdx.x * 64 + lane, cap, w.nsp, (size_t)w.nslots};
-    int g = 0, need = 0;
-    uint64_t sid = 0;
-    if (job) {
-        const uint32_t *rc = s.mt + (size_t)e * kCtrRec;
-        sid = (uint64_t)rc[0] | ((uint64_t)rc[1] << 32);
-        g = s.gen_next[e];
-        need = w.target[e] - g;
-    }
-    bool active = job && need > 0;
+    const uint64_t sid = j.job ? ctr_stream_id(s, j.e) : 0;
+    bool active = j.job && j.need > 0;
     const bool ran = active;
-    const uint32_t whole = (uint32_t)s.W | ((uint32_t)s.L << FB) | ((uint32_t)s.H << (2 * FB));
-    CtrLane c{whole, 0, 1, 0, 0, 0, (uint32_t *)s.ring + ((size_t)(active ? g % D : 0) * E + e) * T + kRowHdr, CtrRng::key(s.seed0, sid, (uint32_t)g)};
-    if (active) col.set(0u, whole);
+    CtrLane c{walk_begin(bin_box<FB>(s), ring_row(s, active ? j.g : 0, j.e) + kRowHdr), CtrRng::key(s.seed0, sid, (uint32_t)j.g)};
+    if (active) col.set(0u, c.box);
     while (__ballot(active)) {
         bool finished;
-        if (__ballot(active && (c.tail_a + 2 > cap || c.tail_b + 1 > cap))) {   // wave-uniform: a list may leave LDS
+        if (__ballot(active && walk_may_spill(c, cap))) {   // wave-uniform
             finished = active ? cut_visit_ctr_general<FB>(c, pend, lo, hi) : false;
         } else {
             finished = cut_visit_ctr<FB>(c, col, cap, active ? ~0u : 0u, lo, hi, EmitToRow{c.row}) != 0u;
         }
         if (finished) {
-            c.row[T - 1 - kRowHdr] = (uint32_t)c.nv;  // (the row's last entry) length for the sort kernel, which restores the terminator
-            ++g;
-            if (--need > 0) {
-                c.row = (uint32_t *)s.ring + ((size_t)(g % D) * E + e) * T + kRowHdr;
-                pend.set(c.side, 0, whole);
-                c.tail_a = 1;
-                c.nv = 0;
-                c.box = whole;
-                c.rng = CtrRng::key(s.seed0, sid, (uint32_t)g);
-            } else {
-                active = false;
-            }
+            active = cut_next_sequence<FB>(s, c, pend, j);
+            if (active) c.rng = CtrRng::key(s.seed0, sid, (uint32_t)j.g);
         }
     }
-    if (ran) s.gen_next[e] = g;
+    if (ran) s.gen_next[j.e] = j.g;
 }
 
 // An unsorted box as the cut kernel leaves it (fields of w.fb bits) -> x | y << 8 | z << 16 | base height << 24.
@@ -1042,20 +1015,19 @@ __host__ __device__ inline size_t stream_rows_lds_bytes(int cap, int stage, int 
 template <int FB, class Col>
 __device__ __forceinline__ int rows_cut_and_place(const bpp_stream &s, bool active, int bin, int ep, uint64_t sid, const Col col, const Col stage,
                                                   uint32_t *cnt, int cap, int S, bool &gave_up) {
-    const int E = s.num_envs, T = s.pool_len, D = s.depth, H = s.H;
+    const int H = s.H;
     const uint32_t lo = (uint32_t)s.bound_lo, hi = (uint32_t)s.bound_hi;
-    const uint32_t whole = (uint32_t)s.W | ((uint32_t)s.L << FB) | ((uint32_t)s.H << (2 * FB));
-    const uint32_t term = (uint32_t)s.W | ((uint32_t)s.L << 8) | ((uint32_t)s.H << 16);
-    uint32_t *row = (uint32_t *)s.ring + ((size_t)(ep % D) * E + bin) * T + kRowHdr;
-    CtrLane c{whole, 0, 1, 0, 0, 0, row, CtrRng::key(s.seed0, sid, (uint32_t)ep)};
-    if (active) col.set(0u, whole);
+    const uint32_t term = stream_terminator(s);
+    uint32_t *row = ring_row(s, ep, bin) + kRowHdr;
+    CtrLane c{walk_begin(bin_box<FB>(s), row), CtrRng::key(s.seed0, sid, (uint32_t)ep)};
+    if (active) col.set(0u, c.box);
     const int NW = (H + 2) >> 1;                      // words of level counters: levels 0 .. H - 1 and the one for nothing
     for (int l = 0; l < NW; ++l) cnt[l * 64] = 0u;
     const EmitToStage<Col, FB> emit{stage, cnt, (uint32_t)S, (uint32_t)H};
     const bool mine0 = active;
     gave_up = false;
     for (;;) {
-        const bool full = active && (c.tail_a + 2 > cap || c.tail_b + 1 > cap || c.nv + 2 > S);
+        const bool full = active && (walk_may_spill(c, cap) || c.nv + 2 > S);
         gave_up = gave_up || full;
         active = active && !full;
         if (!__ballot(active)) break;
@@ -1094,10 +1066,7 @@ __device__ __forceinline__ int rows_cut_and_place(const bpp_stream &s, bool acti
             }
         }
     }
-    if (mine) {
-        if (ep >= 1) ((uint32_t *)s.ring + ((size_t)((ep - 1) % D) * E + bin) * T)[0] = second;
-        if (ep >= 2) ((uint32_t *)s.ring + ((size_t)((ep - 2) % D) * E + bin) * T)[1] = first;
-    }
+    if (mine) place_lookahead(s, bin, ep, first, second);
     return nv;
 }
 
@@ -1106,8 +1075,8 @@ __global__ __launch_bounds__(64) void stream_cut_rows_kernel(bpp_stream s, Strea
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using LT = typename ListCol<FB>::T;
     const int lane = threadIdx.x;
-    const int E = s.num_envs, T = s.pool_len, D = s.depth, cap = w.cap, S = w.stage;
-    const int TI = T - kRowHdr;
+    const int cap = w.cap, S = w.stage;
+    const int TI = s.pool_len - kRowHdr;
     uint32_t *cnt = (uint32_t *)smem + lane;          // level counters first, then the lists and the staging columns
     LT *lists = (LT *)(smem + (size_t)((s.H + 2) / 2) * 64 * 4);
     const ListCol<FB> col{lists + lane};
@@ -1116,7 +1085,7 @@ __global__ __launch_bounds__(64) void stream_cut_rows_kernel(bpp_stream s, Strea
     const int capx = w.maxn + 2;
     const ListCol<FB, 1> colx{lists};
     const ListCol<FB, 1> stagex{lists + (size_t)(2 * capx + 1)};
-    const uint32_t term = (uint32_t)s.W | ((uint32_t)s.L << 8) | ((uint32_t)s.H << 16);
+    const uint32_t term = stream_terminator(s);
     const int nrows = w.hdr[3];
     for (int q0 = (int)blockIdx.x * 64; q0 < nrows; q0 += (int)gridDim.x * 64) {     // wave-uniform
         const int q = q0 + lane;
@@ -1125,8 +1094,7 @@ __global__ __launch_bounds__(64) void stream_cut_rows_kernel(bpp_stream s, Strea
         const int bin = (int)(uint32_t)id, ep = (int)(id >> 32);
         uint64_t sid = 0;
         if (job) {
-            const uint32_t *rc = s.mt + (size_t)bin * kCtrRec;
-            sid = (uint64_t)rc[0] | ((uint64_t)rc[1] << 32);
+            sid = ctr_stream_id(s, bin);
             if (ep + 1 == w.target[bin]) s.gen_next[bin] = ep + 1;       // the bin's newest row: its generator is now here
         }
         bool gave_up;
@@ -1142,7 +1110,7 @@ __global__ __launch_bounds__(64) void stream_cut_rows_kernel(bpp_stream s, Strea
             wave_sync();
         }
         // terminator padding: the wave, row by row
-        uint32_t *row = (uint32_t *)s.ring + ((size_t)(ep % D) * E + bin) * T + kRowHdr;
+        uint32_t *row = ring_row(s, ep, bin) + kRowHdr;
         const uint32_t plo = (uint32_t)(uintptr_t)row, phi = (uint32_t)((uint64_t)(uintptr_t)row >> 32);
         uint64_t todo = __ballot(job);
         while (todo) {
@@ -1156,22 +1124,26 @@ __global__ __launch_bounds__(64) void stream_cut_rows_kernel(bpp_stream s, Strea
     }
 }
 
+// One wave per rewritten row: stable counting sort of the cut boxes by the height of their base (depart_box, :137-138),
+// sort key stripped, the rest of the row padded with the terminator.  Rows of at most 64 boxes (every 10^3 row: 47 at
+// most) never touch LDS: a lane holds one box, its place is the number of boxes with a lower base plus the number of
+// equal ones in lower lanes, counted with one ballot per distinct base height; the next row's boxes are loaded before
+// the current row is ranked.  Longer rows are staged in LDS and ranked chunk by chunk.
 __global__ __launch_bounds__(256) void stream_sort_kernel(bpp_stream s, StreamWork w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int E = s.num_envs, T = s.pool_len, D = s.depth;
+    const int T = s.pool_len;
     const int TI = T - kRowHdr;                       // entries of a row behind its look-ahead header
     uint32_t *ent = (uint32_t *)smem + (size_t)wave * (T + 256);
     int *lvl = (int *)(ent + T);                      // per base height: count, then first free position
-    const uint32_t term = (uint32_t)s.W | ((uint32_t)s.L << 8) | ((uint32_t)s.H << 16);
+    const uint32_t term = stream_terminator(s);
     const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
     const int nrows = w.hdr[3], stride = gridDim.x * 4;
     int q = blockIdx.x * 4 + wave;                    // wave-uniform
     if (q >= nrows) return;
-    auto base_of = [&](int bin, int episode) { return (uint32_t *)s.ring + ((size_t)(episode % D) * E + bin) * T; };
     const int fb = w.fb;
     int64_t id = w.rows[q];
-    uint32_t *row = base_of((int)(uint32_t)id, (int)(id >> 32)) + kRowHdr;
+    uint32_t *row = ring_row(s, (int)(id >> 32), (int)(uint32_t)id) + kRowHdr;
     uint32_t mine = lane < TI - 1 ? cut_box_bytes(row[lane], fb) : 0u;    // this lane's box if the row is short, and the row's length
     int nv = (int)row[TI - 1];
     for (;;) {
@@ -1182,14 +1154,15 @@ __global__ __launch_bounds__(256) void stream_sort_kernel(bpp_stream s, StreamWo
         int nvn = 0;
         if (qn < nrows) {                             // next row: loads in flight while this one is ranked
             idn = w.rows[qn];
-            rown = base_of((int)(uint32_t)idn, (int)(idn >> 32)) + kRowHdr;
+            rown = ring_row(s, (int)(idn >> 32), (int)(uint32_t)idn) + kRowHdr;
             minen = lane < TI - 1 ? cut_box_bytes(rown[lane], fb) : 0u;
             nvn = (int)rown[TI - 1];
         }
-        // the look-ahead copies of this row's first two items (terminators where the row is shorter): item 1 goes into entry
-        // 0 of the row BEFORE this one, item 0 into entry 1 of the row two before -- written by the lanes that place them
+        // the look-ahead copies of this row's first two items (terminators where the row is shorter), written by the lanes
+        // that place them
         const int bin = (int)(uint32_t)id, ep = (int)(id >> 32);
-        uint32_t *hdr1 = ep >= 1 ? base_of(bin, ep - 1) : nullptr, *hdr0 = ep >= 2 ? base_of(bin, ep - 2) + 1 : nullptr;
+        uint32_t *hdr1 = has_lookahead(ep, 1) ? lookahead_slot(s, bin, ep, 1) : nullptr;
+        uint32_t *hdr0 = has_lookahead(ep, 0) ? lookahead_slot(s, bin, ep, 0) : nullptr;
         if (lane == 0) {
             if (nv < 2 && hdr1) *hdr1 = term;
             if (nv < 1 && hdr0) *hdr0 = term;
@@ -1394,14 +1367,12 @@ __global__ __launch_bounds__(256) void stream_init_kernel(bpp_stream s) {
 // The plain kernel's hand-over of one cut sequence (`n` boxes in `vals`, sorted) to ring row `g` of bin `e`: items behind
 // the two look-ahead entries, terminator padding, and this row's first two items into the headers of the two rows before.
 __device__ __forceinline__ int stream_store_row(const bpp_stream &s, int e, int g, const LdsVals &vals, int n, uint32_t term) {
-    const int E = s.num_envs, T = s.pool_len, D = s.depth, TI = T - kRowHdr;
-    uint32_t *row = (uint32_t *)s.ring + ((size_t)(g % D) * E + e) * T + kRowHdr;
+    const int TI = s.pool_len - kRowHdr;
+    uint32_t *row = ring_row(s, g, e) + kRowHdr;
     const int nw = n < TI - 1 ? n : TI - 1;
     for (int t = 0; t < nw; ++t) row[t] = vals.get(t) & 0x00ffffffu;   // drop the sort key
     for (int t = nw; t < TI; ++t) row[t] = term;                        // pad with the terminator (last entry always)
-    const uint32_t i0 = nw > 0 ? vals.get(0) & 0x00ffffffu : term, i1 = nw > 1 ? vals.get(1) & 0x00ffffffu : term;
-    if (g >= 1) ((uint32_t *)s.ring + ((size_t)((g - 1) % D) * E + e) * T)[0] = i1;
-    if (g >= 2) ((uint32_t *)s.ring + ((size_t)((g - 2) % D) * E + e) * T)[1] = i0;
+    place_lookahead(s, e, g, nw > 0 ? vals.get(0) & 0x00ffffffu : term, nw > 1 ? vals.get(1) & 0x00ffffffu : term);
     return n > TI - 1;
 }
 
@@ -1418,15 +1389,13 @@ __global__ __launch_bounds__(kStreamLanes) void stream_refill_kernel(bpp_stream 
     const int cur = s.state[e].episode;
     int g = s.gen_next[e];
     if (g >= cur + D) return;
-    const uint32_t term = (uint32_t)s.W | ((uint32_t)s.L << 8) | ((uint32_t)s.H << 16);
+    const uint32_t term = stream_terminator(s);
     LdsWork work{lds + lane, (CutBox *)s.work + e, (size_t)E};
     int over = 0;
     if (s.rng == BPP_STREAM_RNG_COUNTER) {   // every sequence a fresh generator keyed by (seed0, stream id, episode)
-        const uint32_t *rc = s.mt + (size_t)e * kCtrRec;
-        const uint64_t sid = (uint64_t)rc[0] | ((uint64_t)rc[1] << 32);
+        const uint64_t sid = ctr_stream_id(s, e);
         while (g < cur + D) {
-            uint32_t *row = (uint32_t *)s.ring + ((size_t)(g % D) * E + e) * T + kRowHdr;
-            LdsVals vals{lds + (2 * kStreamPendCap) * kStreamLanes + lane, row, T - 1 - kRowHdr};
+            LdsVals vals{lds + (2 * kStreamPendCap) * kStreamLanes + lane, ring_row(s, g, e) + kRowHdr, T - 1 - kRowHdr};
             CtrRng rng = CtrRng::key(s.seed0, sid, (uint32_t)g);
             const int n = cut2_generate(rng, work, vals, s.W, s.L, s.H, s.bound_lo, s.bound_hi);
             over += stream_store_row(s, e, g, vals, n, term);
@@ -1441,8 +1410,7 @@ __global__ __launch_bounds__(kStreamLanes) void stream_refill_kernel(bpp_stream 
     BufferedMT rng{rec, rec + kMtRaw + par0 * kMtHalf, lds + (2 * kStreamPendCap + kStreamValCap) * kStreamLanes + lane,
                    (int)rec[kMtPos], 0, 0, par0, rec[kMtNextOk]};
     while (g < cur + D) {
-        uint32_t *row = (uint32_t *)s.ring + ((size_t)(g % D) * E + e) * T + kRowHdr;
-        LdsVals vals{lds + (2 * kStreamPendCap) * kStreamLanes + lane, row, T - 1 - kRowHdr};
+        LdsVals vals{lds + (2 * kStreamPendCap) * kStreamLanes + lane, ring_row(s, g, e) + kRowHdr, T - 1 - kRowHdr};
         const int n = cut2_generate(rng, work, vals, s.W, s.L, s.H, s.bound_lo, s.bound_hi);
         over += stream_store_row(s, e, g, vals, n, term);
         ++g;
