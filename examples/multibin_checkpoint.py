@@ -9,10 +9,11 @@ pallet, choose) and one step of the live pallets per lock-step.  The pool is wha
 its pre-incremented index (pallet r plays trajectory r + 1) and the [20, 20, 10] that ends every stored trajectory (the
 [10, 10, 10] the creator appends after it is never reached: nothing fits after [20, 20, 10]).
 
-    python examples/multibin_checkpoint.py --checkpoint <reference>/pretrained_models/default_cut_2.pt [--limit N]
+    python examples/multibin_checkpoint.py --checkpoint <reference>/pretrained_models/default_cut_2.pt [--limit N] [--native]
 
 The network is the reference's CNNPro (acktr/model.py:265-323) rebuilt from plain torch layers: the actor path of
-examples/evaluate_checkpoint.py plus the critic (base.critic.*, base.critic_linear.*), which gives the value.
+examples/evaluate_checkpoint.py plus the critic (base.critic.*, base.critic_linear.*), which gives the value.  --native runs it
+as bpp_amd.NativePolicy of the window's side instead: one fused call over the 4 window rows of every pallet.
 """
 import argparse
 import os
@@ -70,8 +71,9 @@ def load_actor_critic(path, side, n_actions, device, hidden=256):
     return net.to(device).eval()
 
 
-def evaluate(checkpoint, device="cuda:0", limit=None, window=10, stride=10):
-    """-> dict(ratio float64 [n], counter int32 [n], steps int32 [n], lock_steps, seconds)."""
+def evaluate(checkpoint, device="cuda:0", limit=None, window=10, stride=10, native=False):
+    """-> dict(ratio float64 [n], counter int32 [n], steps int32 [n], lock_steps, seconds).
+    native: the network is bpp_amd.NativePolicy of side `window` (one fused call per decision) instead of torch layers."""
     dev = torch.device(device)
     size = (20, 20, 10)
     pool = bpp_amd.sequences.from_dataset(DATASET, size, terminator=(20, 20, 10))       # row r = trajectory r + 1
@@ -79,12 +81,19 @@ def evaluate(checkpoint, device="cuda:0", limit=None, window=10, stride=10):
     env = bpp_amd.BppVecEnv(n, size, pool=pool, device=dev)
     env.reset()
     mb = bpp_amd.MultiBinPacker(env, window, stride)
-    net = load_actor_critic(checkpoint, window, window * window, dev)
+    if native:
+        net = bpp_amd.NativePolicy.from_checkpoint(checkpoint, window, window * window).to(dev)
 
-    def policy(obs):
-        with torch.no_grad():
-            value, logits = net(obs)
-        return value, logits, None
+        def policy(obs):
+            value, logits, _ = net(obs, want=("value", "logits"))
+            return value, logits, None
+    else:
+        net = load_actor_critic(checkpoint, window, window * window, dev)
+
+        def policy(obs):
+            with torch.no_grad():
+                value, logits = net(obs)
+            return value, logits, None
 
     live = torch.arange(n, device=dev)
     ratio = torch.zeros(n, dtype=torch.float64, device=dev)
@@ -112,8 +121,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--limit", type=int)
+    ap.add_argument("--native", action="store_true", help="run the network as bpp_amd.NativePolicy (one fused call per decision)")
     args = ap.parse_args()
-    r = evaluate(args.checkpoint, limit=args.limit)
+    r = evaluate(args.checkpoint, limit=args.limit, native=args.native)
     print("%d trajectories of 20x20x10 in one batch, %d lock-steps, %.2f s: average ratio %.4f, average item number %.4f" % (
         len(r["ratio"]), r["lock_steps"], r["seconds"], r["ratio"].mean(), r["counter"].mean()))
 
