@@ -131,6 +131,17 @@ def hipcc():
     return "hipcc"
 
 
+def bind_branch(L, batch=None, step_out=None, stream=None):
+    """Argument types of the BRANCH_SYMBOLS on library handle L (`batch`, `step_out`, `stream`: the ctypes classes of struct
+    bpp_batch, bpp_step_out and bpp_stream)."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_step_subset.argtypes = [ctypes.POINTER(batch or Batch), vp, i32, vp, ctypes.POINTER(step_out or StepOut), vp, vp]
+    L.bpp_copy_bins.argtypes = [ctypes.POINTER(batch or Batch), ctypes.POINTER(stream or Stream), vp, vp, i32, vp]
+    for name in BRANCH_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
 class Reorder(ctypes.Structure):
     """struct bpp_reorder"""
     _fields_ = [("n", ctypes.c_int32), ("k", ctypes.c_int32), ("times", ctypes.c_int32), ("max_nodes", ctypes.c_int32),
@@ -347,17 +358,12 @@ def lib():
         L.bpp_launch_info.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]
         L.bpp_get_knobs.argtypes = [ctypes.POINTER(Knobs)]
         L.bpp_set_knobs.argtypes = [ctypes.POINTER(Knobs)]
-        L.bpp_step_subset.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(StepOut),
-                                      ctypes.c_void_p, ctypes.c_void_p]
-        L.bpp_step_subset.restype = ctypes.c_int
-        L.bpp_copy_bins.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Stream), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                    ctypes.c_void_p]
-        L.bpp_copy_bins.restype = ctypes.c_int
         L.bpp_pipeline_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]
         L.bpp_pipeline_destroy.argtypes = [ctypes.c_void_p]
         L.bpp_pipeline_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         L.bpp_rollout_uniform_sets_pipelined.argtypes = L.bpp_rollout_uniform_sets.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int32,
                                                                                                     ctypes.c_void_p]
+        bind_branch(L)
         bind_reorder(L)
         bind_multibin(L)
         bind_mcts(L)
@@ -371,9 +377,10 @@ def lib():
     return _lib
 
 
-def check(rc):
+def check(rc, L=None):
+    """RuntimeError with bpp_last_error of library handle L (default: libbpp_hip.so) unless rc is 0."""
     if rc != 0:
-        raise RuntimeError("libbpp_hip error %d: %s" % (rc, lib().bpp_last_error().decode()))
+        raise RuntimeError("libbpp_hip error %d: %s" % (rc, (L or lib()).bpp_last_error().decode()))
 
 
 def get_knobs():

@@ -90,7 +90,7 @@ class MCTSearch(object):
         self.env, self.k, self.sim_times, self.max_depth, self.rollout_length = env, k, int(sim_times), max_depth, r
         self.credit, self.zeta = float(credit), float(zeta)
         sizes = (ctypes.c_int64 * 4)()
-        _lib.check(env.lib.bpp_mcts_sizes(env.E, k, self.sim_times, max_depth, r, env.W, env.L, sizes))
+        _lib.check(env.lib.bpp_mcts_sizes(env.E, k, self.sim_times, max_depth, r, env.W, env.L, sizes), env.lib)
         self.nbytes, self.cap, self.bin_bytes, self.rollout_levels = (int(v) for v in sizes)
         dev = env.device
         self.state = torch.zeros(((self.nbytes + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
@@ -131,7 +131,7 @@ class MCTSearch(object):
             raise ValueError("seeds must lie in [0, 2**32)")
         s = torch.where(s > 0x7FFFFFFF, s - (1 << 32), s).to(torch.int32).contiguous()     # the uint32 bit pattern
         m = self._desc(0)
-        _lib.check(env.lib.bpp_mcts_seed(env._batch_ref, ctypes.byref(m), ids.data_ptr(), s.data_ptr(), ids.numel(), env._stream_ptr()))
+        _lib.check(env.lib.bpp_mcts_seed(env._batch_ref, ctypes.byref(m), ids.data_ptr(), s.data_ptr(), ids.numel(), env._stream_ptr()), env.lib)
 
     def reset(self, ids=None):
         """Drop the trees of bins ids (None: every bin); the random streams continue."""
@@ -139,7 +139,7 @@ class MCTSearch(object):
         ids_t = None if ids is None else env._ids(ids)
         m = self._desc(0)
         _lib.check(env.lib.bpp_mcts_clear(env._batch_ref, ctypes.byref(m), None if ids_t is None else ids_t.data_ptr(),
-                                          0 if ids_t is None else ids_t.numel(), env._stream_ptr()))
+                                          0 if ids_t is None else ids_t.numel(), env._stream_ptr()), env.lib)
         self._pending = None
 
     def decide(self, policy, ids, scratch, check=True):
@@ -158,26 +158,26 @@ class MCTSearch(object):
         obs, actions, A = st["obs"], st["actions"], env.A
         env._on_device()
         stream = env._stream_ptr()
-        _lib.check(L.bpp_mcts_begin(b, mr, stream))
+        _lib.check(L.bpp_mcts_begin(b, mr, stream), L)
         for _ in range(self.sim_times):
             env.clone_bins(ids, scratch, check=False)                 # select()'s copy.deepcopy(sim_env)
             done = None
             for level in range(self.max_depth):
-                _lib.check(L.bpp_mcts_select(b, mr, level, done, actions.data_ptr(), stream))
+                _lib.check(L.bpp_mcts_select(b, mr, level, done, actions.data_ptr(), stream), L)
                 done = env.step_bins(scratch, actions, check=False).done.data_ptr()
-            _lib.check(L.bpp_mcts_emit(b, mr, 0, done, obs.data_ptr(), stream))
+            _lib.check(L.bpp_mcts_emit(b, mr, 0, done, obs.data_ptr(), stream), L)
             value, logits, _ = check_policy_output(policy(obs), n, A)
-            _lib.check(L.bpp_mcts_expand(b, mr, value.data_ptr(), logits.data_ptr(), actions.data_ptr(), stream))
+            _lib.check(L.bpp_mcts_expand(b, mr, value.data_ptr(), logits.data_ptr(), actions.data_ptr(), stream), L)
             done = None
             for level in range(1, self.rollout_levels):
                 done = env.step_bins(scratch, actions, check=False).done.data_ptr()
-                _lib.check(L.bpp_mcts_emit(b, mr, level, done, obs.data_ptr(), stream))
+                _lib.check(L.bpp_mcts_emit(b, mr, level, done, obs.data_ptr(), stream), L)
                 value, logits, _ = check_policy_output(policy(obs), n, A)
-                _lib.check(L.bpp_mcts_rollout(b, mr, value.data_ptr(), logits.data_ptr(), actions.data_ptr(), stream))
+                _lib.check(L.bpp_mcts_rollout(b, mr, value.data_ptr(), logits.data_ptr(), actions.data_ptr(), stream), L)
             if self.rollout_levels > 0:
                 done = env.step_bins(scratch, actions, check=False).done.data_ptr()
-            _lib.check(L.bpp_mcts_backup(b, mr, done, stream))
-        _lib.check(L.bpp_mcts_finish(b, mr, st["action"].data_ptr(), st["visits"].data_ptr(), stream))
+            _lib.check(L.bpp_mcts_backup(b, mr, done, stream), L)
+        _lib.check(L.bpp_mcts_finish(b, mr, st["action"].data_ptr(), st["visits"].data_ptr(), stream), L)
         self._pending = (ids, scratch)
         return st["action"].clone(), st["visits"].clone()
 
@@ -192,7 +192,7 @@ class MCTSearch(object):
             raise ValueError("done must have one entry per slot of the last decide")
         d = d.to(torch.uint8).contiguous()
         m = self._desc(ids.numel(), ids, scratch)
-        _lib.check(env.lib.bpp_mcts_advance(env._batch_ref, ctypes.byref(m), d.data_ptr(), env._stream_ptr()))
+        _lib.check(env.lib.bpp_mcts_advance(env._batch_ref, ctypes.byref(m), d.data_ptr(), env._stream_ptr()), env.lib)
         self._pending = None
 
     def root_stats(self, ids):

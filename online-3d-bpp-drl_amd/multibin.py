@@ -49,7 +49,7 @@ class MultiBinPacker(object):
             raise ValueError("%d windows: more than the %d one pallet may have" % (K, _lib.MULTIBIN_MAX_K))
         self.env, self.w, self.s, self.K = env, w, s, K
         sizes = (ctypes.c_int64 * 3)()
-        _lib.check(env.lib.bpp_multibin_sizes(env.W, env.L, w, s, 0, env.E, sizes))
+        _lib.check(env.lib.bpp_multibin_sizes(env.W, env.L, w, s, 0, env.E, sizes), env.lib)
         assert int(sizes[0]) == K
         self.state = torch.zeros((max(int(sizes[1]), 8) + 7) // 8, dtype=torch.float64, device=env.device)
         self._sets = {}
@@ -67,7 +67,7 @@ class MultiBinPacker(object):
         if ent is None:
             env, dev = self.env, self.env.device
             sizes = (ctypes.c_int64 * 3)()
-            _lib.check(env.lib.bpp_multibin_sizes(env.W, env.L, self.w, self.s, n, env.E, sizes))
+            _lib.check(env.lib.bpp_multibin_sizes(env.W, env.L, self.w, self.s, n, env.E, sizes), env.lib)
             ent = dict(work=torch.empty((max(int(sizes[2]), 16) + 15) // 16 * 16, dtype=torch.uint8, device=dev),
                        obs=torch.zeros((n * self.K, 4 * self.w * self.w), dtype=torch.float32, device=dev),
                        action=torch.zeros((n,), dtype=torch.int64, device=dev), adv=torch.zeros((n,), dtype=torch.float64, device=dev),
@@ -101,10 +101,10 @@ class MultiBinPacker(object):
         env._on_device()
         stream = env._stream_ptr()
         obs = st["obs"]
-        _lib.check(L.bpp_multibin_emit(b, mm, obs.data_ptr(), stream))
+        _lib.check(L.bpp_multibin_emit(b, mm, obs.data_ptr(), stream), L)
         value, logits, _ = check_policy_output(policy(obs), n * self.K, self.w * self.w)
         _lib.check(L.bpp_multibin_choose(b, mm, value.data_ptr(), logits.data_ptr(), st["action"].data_ptr(), st["adv"].data_ptr(),
-                                         st["window"].data_ptr(), stream))
+                                         st["window"].data_ptr(), stream), L)
         self._pending = (ids, st)
         return st["action"].clone(), st["adv"].clone(), st["window"].clone()
 
@@ -121,7 +121,7 @@ class MultiBinPacker(object):
         env = self.env
         m = self._desc(ids, st)
         env._on_device()
-        _lib.check(env.lib.bpp_multibin_commit(env._batch_ref, ctypes.byref(m), d.data_ptr(), env._stream_ptr()))
+        _lib.check(env.lib.bpp_multibin_commit(env._batch_ref, ctypes.byref(m), d.data_ptr(), env._stream_ptr()), env.lib)
         self._pending = None
 
     def reset(self, ids=None):
@@ -131,4 +131,4 @@ class MultiBinPacker(object):
         m = _lib.MultiBin(0, self.w, self.s, self.K, None, self.state.data_ptr(), st["work"].data_ptr())
         env._on_device()
         _lib.check(env.lib.bpp_multibin_clear(env._batch_ref, ctypes.byref(m), None if ids_t is None else ids_t.data_ptr(),
-                                              0 if ids_t is None else ids_t.numel(), env._stream_ptr()))
+                                              0 if ids_t is None else ids_t.numel(), env._stream_ptr()), env.lib)

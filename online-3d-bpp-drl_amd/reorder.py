@@ -126,7 +126,7 @@ class ReorderSearch(object):
         if ent is None:
             env = self.env
             sizes = (ctypes.c_int64 * 3)()
-            _lib.check(env.lib.bpp_reorder_sizes(n, self.k, self.times, env.W, env.L, sizes))
+            _lib.check(env.lib.bpp_reorder_sizes(n, self.k, self.times, env.W, env.L, sizes), env.lib)
             assert int(sizes[1]) == self.times
             dev = env.device
             if self.overflow is None:
@@ -155,17 +155,17 @@ class ReorderSearch(object):
         obs, actions = st["obs"], st["actions"]
         env._on_device()
         stream = env._stream_ptr()
-        _lib.check(L.bpp_reorder_begin(b, rr, stream))
+        _lib.check(L.bpp_reorder_begin(b, rr, stream), L)
         done = None
         for it in range(-1, self.times):
             env.clone_bins(ids, scratch, check=False)                 # copy.deepcopy(self.env)
             for level in range(self.k):
-                _lib.check(L.bpp_reorder_emit(b, rr, it, level, done, obs.data_ptr(), stream))
+                _lib.check(L.bpp_reorder_emit(b, rr, it, level, done, obs.data_ptr(), stream), L)
                 value, logits, pred = check_policy_output(policy(obs), n, env.A)
                 _lib.check(L.bpp_reorder_choose(b, rr, value.data_ptr(), logits.data_ptr(),
-                                                None if pred is None else pred.data_ptr(), actions.data_ptr(), stream))
+                                                None if pred is None else pred.data_ptr(), actions.data_ptr(), stream), L)
                 res = env.step_bins(scratch, actions, check=False)
                 done = res.done.data_ptr()
-        _lib.check(L.bpp_reorder_commit(b, rr, done, stream))
-        _lib.check(L.bpp_reorder_finish(b, rr, st["action"].data_ptr(), st["value"].data_ptr(), st["default"].data_ptr(), stream))
+        _lib.check(L.bpp_reorder_commit(b, rr, done, stream), L)
+        _lib.check(L.bpp_reorder_finish(b, rr, st["action"].data_ptr(), st["value"].data_ptr(), st["default"].data_ptr(), stream), L)
         return st["action"].clone(), st["value"].clone(), st["default"].clone().to(torch.bool)

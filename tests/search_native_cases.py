@@ -12,7 +12,7 @@ inside a decision is judged given its own input, and a replay proves that the se
              int64 numpy forward; float32 is exact on it in any summation order (the bound is asserted on the judged rows).
   judge_exact / judge_real / judge_alone   the three judges.
 
-Both tiers run the same code: the emulated one hands numpy arrays round, the device one torch tensors."""
+Both tiers run the same code on torch tensors: the emulated one's live on the host, the device one's on the device."""
 import numpy as np
 import torch
 
@@ -93,11 +93,6 @@ def host_policy(L, geom, blob):
         got = run(obs, geom, blob)
         return tuple(got[h] for h in HEADS)
     return policy
-
-
-def two_heads(policy):
-    """EmuMcts takes (value, logits)."""
-    return lambda obs: policy(obs)[:2]
 
 
 # ----------------------------------------------------------------------------------------------------------- the exact network

@@ -1,46 +1,32 @@
 """Native branch stepping (include/bpp_branch.h): bpp_step_subset / bpp_copy_bins and BppVecEnv.step_bins / observe_bins /
 clone_bins, checked against the paths they replace -- bpp_step with BPP_ACTION_NOOP for every other bin (step_subset) and
-copy_bin_records (copy_bins / clone_into) -- on twin envs over the same items.  CPU: the product kernels in the host SIMT
-emulator (tests/emu); `-m gpu`: BppVecEnv on the device at the headline sizes."""
+copy_bin_records (copy_bins / clone_into) -- on twin envs over the same items.  CPU: the product's step_bins / clone_bins on an
+EmuVecEnv (tests/emu_env.py) over the product kernels in the host SIMT emulator (tests/emu), and the per-n lifetime of
+step_bins' results; `-m gpu`: BppVecEnv on the device at the headline sizes."""
 import ctypes
 
 import numpy as np
 import pytest
 
 from conftest import load_golden
+from emu_env import KEYS, EmuVecEnv, bind
 from test_lookahead import NOOP, replay_branches
-
-KEYS = ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len")
 
 
 # ---------------------------------------------------------------------------------------------------- CPU (emulator)
-def _bind(emu):
-    L = emu.lib()
-    if not hasattr(L, "bpp_step_subset") or not hasattr(L, "bpp_copy_bins"):
-        raise RuntimeError("the emulated library lacks the branch entry points: rebuild tests/emu/libbpp_emu.so")
-    L.bpp_step_subset.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                  ctypes.POINTER(emu.StepOut), ctypes.c_void_p, ctypes.c_void_p]
-    L.bpp_copy_bins.argtypes = [ctypes.POINTER(emu.Batch), ctypes.POINTER(emu.Stream), ctypes.c_void_p, ctypes.c_void_p,
-                                ctypes.c_int32, ctypes.c_void_p]
-    return L
-
-
 def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 class Twins(object):
     """Two emulated envs over the same items: `full` is stepped the old way (bpp_step over all bins, BPP_ACTION_NOOP for the
-    unlisted ones; copies by copy_bin_records), `sub` by the native branch calls."""
+    unlisted ones; copies by copy_bin_records), `sub`, an EmuVecEnv, by the product's step_bins / clone_bins."""
 
     def __init__(self, emu, size, rot, E, pool=None, stream=None):
         self.emu, self.E, self.size = emu, E, size
-        self.lib = _bind(emu)
         self.full = emu.OracleEnv(pool, size, rot, E, stream=stream)
-        self.sub = emu.OracleEnv(pool, size, rot, E, stream=stream)
-        self.bad = np.zeros(1, np.int32)
+        self.sub = EmuVecEnv(emu, size, E, pool=pool, stream=stream, rotation=rot)
         self.mask = self.full.reset()[1]
-        self.sub.reset()
 
     def step_full(self, ids, a, sample=None):
         full = np.full(self.E, NOOP, np.int64)
@@ -59,22 +45,19 @@ class Twins(object):
             r["next_action"] = nxt
         return r
 
-    def step_sub(self, ids, a, sample=None, env=None):
+    def step_sub(self, ids, a, sample=None, env=None, check=True):
+        """env.step_bins as a dict of arrays (reward [n]); the cached output set of this n is filled with a sentinel byte
+        first, so that a row the launch did not write cannot pass for one it wrote."""
+        import torch
         env = env or self.sub
-        ids = np.ascontiguousarray(ids, np.int64)
-        a = np.ascontiguousarray(a, np.int64)
-        n = ids.shape[0]
-        A, M = env.A, env.M
-        r = dict(obs=np.full((n, 4 * A), -1, np.float32), mask=np.full((n, M), -1, np.float32), reward=np.full(n, -1, np.float32),
-                 done=np.full(n, 7, np.uint8), counter=np.full(n, -1, np.int32), ratio=np.full(n, -1.0), ep_ret=np.full(n, -1.0),
-                 ep_len=np.full(n, -1, np.int32))
-        out = self.emu.StepOut(*[_p(r[k]).value for k in KEYS])
-        if sample is not None:
-            r["next_action"] = np.full(n, -7, np.int64)
-            out.next_action, out.sample_seed, out.sample_step = _p(r["next_action"]).value, sample[0], sample[1]
-        rc = self.lib.bpp_step_subset(ctypes.byref(env._b), _p(ids), n, _p(a), ctypes.byref(out), _p(self.bad), None)
-        assert rc == 0, self.lib.bpp_last_error()
-        env._after_steps(1)
+        n = len(ids)
+        env._branch_out(n)[0]._flat.fill_(0xA5)
+        nxt = None if sample is None else torch.full((n,), -7, dtype=torch.int64)
+        res = env.step_bins(np.asarray(ids, np.int64), np.asarray(a, np.int64), check=check,
+                            sample=None if sample is None else (sample[0], sample[1], nxt))
+        r = {k: getattr(res, k).numpy().reshape(-1).copy() if k == "reward" else getattr(res, k).numpy().copy() for k in KEYS}
+        if nxt is not None:
+            r["next_action"] = nxt.numpy()
         return r
 
     def clone_full(self, src, dst):
@@ -92,14 +75,10 @@ class Twins(object):
             env.reset_seq_cache()
 
     def clone_sub(self, src, dst):
-        env = self.sub
-        src, dst = np.ascontiguousarray(src, np.int64), np.ascontiguousarray(dst, np.int64)
-        rc = self.lib.bpp_copy_bins(ctypes.byref(env._b), ctypes.byref(env.stream) if env.stream is not None else None,
-                                    _p(src), _p(dst), src.shape[0], None)
-        assert rc == 0, self.lib.bpp_last_error()
+        self.sub.clone_bins(np.asarray(src, np.int64), np.asarray(dst, np.int64))
 
     def assert_same_state(self, what=""):
-        a, b = self.full, self.sub
+        a, b = self.full, self.sub.oracle
         np.testing.assert_array_equal(a.hmap, b.hmap, err_msg="hmap " + what)
         np.testing.assert_array_equal(a.state.view(np.int32), b.state.view(np.int32), err_msg="state " + what)
         np.testing.assert_array_equal(a.ep_acc, b.ep_acc, err_msg="ep_acc " + what)
@@ -154,7 +133,7 @@ def test_emulated_step_bins_equals_step_subset(emu, size, E, rot):
         tw.assert_same_state("t=%d" % t)
         done += int(rs["done"].sum())
     assert done >= 5
-    assert tw.bad[0] == 0
+    assert int(tw.sub.bad_ids[0]) == 0
 
 
 @pytest.mark.parametrize("rng_kind", ["mt19937", "counter"])
@@ -163,7 +142,7 @@ def test_emulated_step_bins_streaming_with_row_cache(emu, rng_kind):
     step kernel); results and the ring stay those of the full path across refills."""
     size, E = (10, 10, 10), 24
     tw = Twins(emu, size, True, E, stream=dict(bound=(2, 5), seed=7, depth=8, rng=rng_kind))
-    assert tw.sub.seq_cache is not None
+    assert tw.sub.oracle.seq_cache is not None
     rng = np.random.RandomState(5)
     for t in range(24):
         ids = _ids(rng, E, t)
@@ -193,7 +172,7 @@ def test_emulated_clone_bins_equals_copy_bin_records(emu, mode):
     tw.clone_full(src, dst)
     tw.clone_sub(src, dst)
     tw.assert_same_state("after the clone")
-    np.testing.assert_array_equal(tw.sub.hmap[dst], tw.sub.hmap[src])
+    np.testing.assert_array_equal(tw.sub.oracle.hmap[dst], tw.sub.oracle.hmap[src])
     for t in range(6, 26):                                 # refill_every = 4: several refills
         ids = _ids(rng, E, t)
         a = _actions(rng, emu, tw.mask, ids, t, tw.full.M)
@@ -209,8 +188,7 @@ def test_emulated_bad_ids_are_noop_rows(emu, size):
     E = 20
     pool = sequences.cut2_pool(size, 8, seed=2, native=False)
     tw = Twins(emu, size, True, E, pool=pool)
-    ref = emu.OracleEnv(pool, size, True, E)
-    ref.reset()
+    ref = EmuVecEnv(emu, size, E, pool=pool, rotation=True)
     rng = np.random.RandomState(3)
     for t in range(6):
         good = rng.permutation(E)[:9]
@@ -218,34 +196,53 @@ def test_emulated_bad_ids_are_noop_rows(emu, size):
         bad_ids = np.array([-1, E, E + 100, 2 ** 40, -2 ** 62])
         ids = np.concatenate([good[:4], bad_ids[:2], good[4:], bad_ids[2:]])
         acts = np.concatenate([a[:4], [0, NOOP], a[4:], [1, 2, 3]])
-        before = int(tw.bad[0])
+        before = int(tw.sub.bad_ids[0])
         want = tw.step_sub(good, a, (4, t), env=ref)
-        got = tw.step_sub(ids, acts, (4, t))
+        got = tw.step_sub(ids, acts, (4, t), check=False)
         isbad = (ids < 0) | (ids >= E)
-        assert int(tw.bad[0]) - before == int(isbad.sum())
+        assert int(tw.sub.bad_ids[0]) - before == int(isbad.sum())
         for k in KEYS + ("next_action",):
             np.testing.assert_array_equal(got[k][~isbad], want[k], err_msg=k)
             assert not got[k][isbad].any(), k
-        np.testing.assert_array_equal(tw.sub.hmap, ref.hmap)
-        np.testing.assert_array_equal(tw.sub.state.view(np.int32), ref.state.view(np.int32))
-        tw.mask = ref.step(np.full(E, NOOP, np.int64))["mask"]           # (re-emits only: ref's bins stay as they are)
+        np.testing.assert_array_equal(tw.sub.oracle.hmap, ref.oracle.hmap)
+        np.testing.assert_array_equal(tw.sub.oracle.state.view(np.int32), ref.oracle.state.view(np.int32))
+        tw.mask = ref.oracle.step(np.full(E, NOOP, np.int64))["mask"]    # (re-emits only: ref's bins stay as they are)
 
 
 def test_emulated_argument_checks(emu):
     from bpp_amd import sequences
     size, E = (10, 10, 10), 8
     tw = Twins(emu, size, False, E, pool=sequences.cut2_pool(size, 4, seed=1, native=False))
-    L, env = tw.lib, tw.sub
+    from bpp_amd import _lib
+    L, env = bind(emu), tw.sub.oracle
     ids = np.arange(2, dtype=np.int64)
-    r = tw.step_sub(np.zeros(0, np.int64), np.zeros(0, np.int64))          # n == 0: a valid no-op
-    assert r["obs"].shape == (0, 400)
-    out = emu.StepOut(*[_p(np.zeros((2, 400), np.float32)).value] + [None] * 7)
+    none = [np.zeros(0, np.int64) for _ in range(10)]                      # n == 0: a valid no-op
+    out = _lib.StepOut(*[_p(x).value for x in none[2:]])
+    assert L.bpp_step_subset(ctypes.byref(env._b), _p(none[0]), 0, _p(none[1]), ctypes.byref(out), None, None) == 0
+    out = _lib.StepOut(*[_p(np.zeros((2, 400), np.float32)).value] + [None] * 7)
     assert L.bpp_step_subset(ctypes.byref(env._b), _p(ids), 2, _p(ids), ctypes.byref(out), None, None) != 0      # NULL outputs
     assert L.bpp_step_subset(ctypes.byref(env._b), None, 2, _p(ids), ctypes.byref(out), None, None) != 0
     assert L.bpp_step_subset(ctypes.byref(env._b), _p(ids), -1, _p(ids), ctypes.byref(out), None, None) != 0
     assert L.bpp_copy_bins(ctypes.byref(env._b), None, _p(ids), _p(ids), -1, None) != 0
     assert L.bpp_copy_bins(ctypes.byref(env._b), None, None, _p(ids), 1, None) != 0
     assert L.bpp_copy_bins(ctypes.byref(env._b), None, _p(ids), _p(ids), 0, None) == 0
+
+
+def test_emulated_step_bins_results_live_per_n(emu):
+    """step_bins' promise that mcts.py and reorder.py rely on when they keep `.done.data_ptr()` across launches: the
+    compact output set of a given n is made once -- two calls with the same n hand back the same buffers -- and a call
+    with another n in between neither moves nor overwrites it."""
+    g = load_golden("mcts_fake_5x5x3")
+    env = EmuVecEnv(emu, (5, 5, 3), 6, pool=g["pool"][:6])
+    first = env.step_bins([0, 1, 2], [0, 0, 0])
+    ptr, kept = first.done.data_ptr(), {k: getattr(first, k).clone() for k in KEYS}
+    other = env.step_bins([3, 4], [1, 1])
+    assert other.done.data_ptr() != ptr and other.obs.shape[0] == 2
+    for k in KEYS:
+        assert getattr(first, k).equal(kept[k]), k
+    again = env.step_bins([2, 1, 0], [env.NOOP] * 3)
+    assert again is first and again.done.data_ptr() == ptr
+    assert again.obs[0].equal(kept["obs"][2]) and not again.done.any()
 
 
 class NativeHost(object):
@@ -257,7 +254,7 @@ class NativeHost(object):
         self.last = None
 
     def reset(self):
-        env = self.tw.sub
+        env = self.tw.sub.oracle
         self.last = {k: np.array(v) for k, v in env.out.items()}
         return self.last["obs"].copy(), self.last["mask"].copy()
 

@@ -10,8 +10,9 @@ launch is checked given identical inputs:
            u <= cdf64[a] + CDF_TOL, and the host adopts it;
   backup   n and w of every node on the path bit for bit;  finish: play()'s action and the root record equal.
 HostTree is first pinned: on its own (its own float32 priors and draws) under flat_policy it reproduces the committed
-mcts_fake_* fixtures bit for bit.  The driver runs MCTSearch.decide's schedule on the emulator or on the device
-(`-m gpu`, through bpp_amd._lib.bind_mcts on torch buffers)."""
+mcts_fake_* fixtures bit for bit.  The driver below restates MCTSearch.decide's schedule launch by launch, on the buffers
+of an MCTSearch over an EmuVecEnv or (`-m gpu`) over a BppVecEnv.  It is the one deliberate second statement of a
+schedule under tests/: it compares a host tree between every two launches, which MCTSearch.decide cannot offer."""
 import ctypes
 import math
 
@@ -20,7 +21,8 @@ import pytest
 
 import search_inputs as si
 from conftest import load_golden
-from test_mcts_search import NOOP, RUNS, EmuMcts, _p, case_params, expected
+from test_mcts_search import NOOP, RUNS, case_params, expected
+from test_reorder_search import make_env
 from test_policy_head_f64 import CDF_TOL
 
 TINY = 2.0 ** -126
@@ -200,8 +202,35 @@ def softmax64(x):
 
 # ------------------------------------------------------------------------------------------------- the two backends
 class Backend(object):
-    """MCTSearch.decide's launches one at a time.  Subclasses provide buffers (`new`, `ptr`, `host`), the env calls and the
-    state bytes; `done` handles stay backend buffers, everything returned for checking is numpy."""
+    """MCTSearch.decide's launches one at a time, on the buffers of an MCTSearch over make_env's env (emu: the emulated
+    library, None: the device); `done` handles stay tensors of the env's device, everything returned for checking is numpy.
+    Subclasses provide `gather`: the state bytes at an array of offsets."""
+
+    def __init__(self, emu, pool, size, n, k, S, rollout, credit, seeds, depth=None):
+        import torch
+        from bpp_amd import MCTSearch
+        env = make_env(emu, pool, size, 2 * n)
+        if emu is None:                            # the device's scratch bins are judged by the oracle's "space" rule
+            from oracle import oracle as emu
+        self.torch, self.mask_from_hmap = torch, emu.mask_from_hmap
+        ms = MCTSearch(env, k, sim_times=S, search_depth=depth, rollout_length=rollout, credit=credit)
+        self.env, self.ms, self.L, self.b = env, ms, env.lib, env._batch_ref
+        self.n, self.k, self.S, self.max_depth, self.rollout, self.cap, self.credit = n, k, S, ms.max_depth, ms.rollout_length, ms.cap, ms.credit
+        self.E, self.A, self.size, self.levels = env.E, env.A, tuple(int(v) for v in size), ms.rollout_levels
+        self.real = np.arange(n)
+        dev = env.device
+        self.ids, self.scratch = torch.arange(n, device=dev), torch.arange(n, 2 * n, device=dev)
+        self.state, self.overflow = ms.state, ms.overflow
+        self.acts, self.act = torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
+        self.vis = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.obs = torch.zeros((n, 4 * self.A), dtype=torch.float32, device=dev)
+        ms.seed(self.ids, torch.as_tensor(np.asarray(seeds)))
+
+    ptr = staticmethod(lambda a: None if a is None else a.data_ptr())
+    host = staticmethod(lambda a: a.cpu().numpy().copy())       # (a host tensor's numpy() is a view of it)
+
+    def new(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.env.device)
 
     def desc(self):
         from bpp_amd import _lib
@@ -210,12 +239,12 @@ class Backend(object):
 
     def call(self, name, *args):
         m = self.desc()
-        rc = getattr(self.L, name)(self.b, ctypes.byref(m), *(list(args) + [self.stream()]))
+        rc = getattr(self.L, name)(self.b, ctypes.byref(m), *(list(args) + [self.env._stream_ptr()]))
         assert rc == 0, (name, self.L.bpp_last_error())
 
     def launch_acts(self, name, *args):
         self.call(name, *(list(args) + [self.ptr(self.acts)]))
-        return self.host(self.acts).copy()
+        return self.host(self.acts)
 
     def select(self, level, done):
         return self.launch_acts("bpp_mcts_select", level, None if done is None else self.ptr(done))
@@ -232,7 +261,7 @@ class Backend(object):
 
     def finish(self):
         self.call("bpp_mcts_finish", self.ptr(self.act), self.ptr(self.vis))
-        return self.host(self.act).copy(), self.host(self.vis).copy()
+        return self.host(self.act), self.host(self.vis)
 
     def bins(self):
         """int32 [n, 48]: the MBin records of the real bins."""
@@ -244,90 +273,6 @@ class Backend(object):
         base = self.E * 192 + self.E * 640 * 4 + (self.real * 2 + half) * self.cap * 32
         off = base[:, None, None] + idx[:, :, None] * 32 + np.arange(32)[None, None]
         return self.gather(off.reshape(self.n, -1)).reshape(self.n, idx.shape[1], 32)
-
-
-class EmuBackend(Backend):
-    def __init__(self, emu, pool, size, n, k, S, rollout, credit, seeds, depth=None):
-        em = EmuMcts(emu, pool, size, n, k, S, depth, rollout, credit)
-        self.em, self.emu, self.L, self.b = em, emu, em.L, ctypes.byref(em.env._b)
-        self.n, self.k, self.S, self.max_depth, self.rollout, self.cap, self.credit = n, k, S, em.max_depth, em.rollout, em.cap, em.credit
-        self.E, self.A, self.size, self.levels = em.E, em.A, em.size, em.levels
-        self.real = np.arange(n)
-        self.ids, self.scratch = np.arange(n, dtype=np.int64), np.arange(n, 2 * n, dtype=np.int64)
-        self.state, self.overflow = em.state, em.overflow
-        self.acts, self.act, self.vis = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
-        self.obs = np.zeros((n, 4 * self.A), np.float32)
-        em.seed(self.ids, seeds)
-
-    ptr = staticmethod(lambda a: None if a is None else _p(a).value)
-    host = staticmethod(lambda a: a)
-    new = staticmethod(lambda a: np.ascontiguousarray(a))
-    stream = staticmethod(lambda: None)
-
-    def gather(self, off):
-        return self.state[off]
-
-    def warm(self, steps):
-        env = self.em.env
-        for t in range(steps):
-            env.step(self.emu.sample_feasible(env.out["mask"], 3, t))
-
-    def begin(self):
-        self.call("bpp_mcts_begin")
-
-    def clone(self):
-        assert self.L.bpp_copy_bins(self.b, None, _p(self.ids), _p(self.scratch), self.n, None) == 0
-
-    def scratch_bins(self):
-        env = self.em.env
-        it = env.state["item_cur"][self.n:]
-        return env.hmap[self.n:].copy(), np.stack([(it >> (8 * j)) & 255 for j in range(3)], 1).astype(np.int64)
-
-    def step(self, acts):
-        return self.em._step(self.scratch, acts)["done"]
-
-    def step_real(self, act):
-        return self.em._step(self.ids, act)["done"]
-
-    def advance(self, done):
-        self.call("bpp_mcts_advance", _p(np.ascontiguousarray(done, np.uint8)).value)
-
-    def mask(self, hmap, items):
-        return self.emu.mask_from_hmap(hmap, items, self.size, False) > 0.5
-
-
-class GpuBackend(Backend):
-    def __init__(self, pool, size, n, k, S, rollout, credit, seeds):
-        import torch
-        from bpp_amd import BppVecEnv, MCTSearch, _lib
-        from oracle import oracle as orc
-        self.torch, self.orc = torch, orc
-        env = BppVecEnv(2 * n, container_size=size, pool=np.ascontiguousarray(pool), device="cuda", compute_mask=True)
-        env.reset()
-        ms = MCTSearch(env, k, sim_times=S, rollout_length=rollout, credit=credit)
-        self.env, self.ms, self.L, self.b = env, ms, _lib.bind_mcts(env.lib), env._batch_ref
-        self.n, self.k, self.S, self.max_depth, self.rollout, self.cap, self.credit = n, k, S, ms.max_depth, ms.rollout_length, ms.cap, ms.credit
-        self.E, self.A, self.size, self.levels = env.E, env.A, tuple(size), ms.rollout_levels
-        self.real = np.arange(n)
-        dev = env.device
-        self.ids, self.scratch = torch.arange(n, device=dev), torch.arange(n, 2 * n, device=dev)
-        self.state, self.overflow = ms.state, ms.overflow
-        self.acts, self.act = torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
-        self.vis = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.obs = torch.zeros((n, 4 * self.A), dtype=torch.float32, device=dev)
-        ms.seed(self.ids, torch.as_tensor(np.asarray(seeds)))
-
-    ptr = staticmethod(lambda a: None if a is None else a.data_ptr())
-    host = staticmethod(lambda a: a.cpu().numpy())
-
-    def new(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def stream(self):
-        return self.env._stream_ptr()
-
-    def gather(self, off):
-        return self.state[self.torch.from_numpy(off).cuda()].cpu().numpy()
 
     def warm(self, steps):
         for t in range(steps):
@@ -341,8 +286,8 @@ class GpuBackend(Backend):
         self.env.clone_bins(self.ids, self.scratch, check=False)
 
     def scratch_bins(self):
-        it = self.env.state_numpy()["item_cur"][self.n:]
-        return self.env.hmap[self.n:].cpu().numpy(), np.stack([(it >> (8 * j)) & 255 for j in range(3)], 1).astype(np.int64)
+        it = self.host(self.env.state[self.n:, 8]).view(np.uint32)                   # bpp_env_state.item_cur
+        return self.host(self.env.hmap[self.n:]), np.stack([(it >> (8 * j)) & 255 for j in range(3)], 1).astype(np.int64)
 
     def step(self, acts):
         return self.env.step_bins(self.scratch, self.new(acts), check=False).done
@@ -351,10 +296,25 @@ class GpuBackend(Backend):
         return self.env.step_bins(self.ids, self.new(act)).done
 
     def advance(self, done):
-        self.call("bpp_mcts_advance", done.to(self.torch.uint8).contiguous().data_ptr())
+        d = self.torch.as_tensor(done).to(device=self.env.device, dtype=self.torch.uint8).contiguous()
+        self.call("bpp_mcts_advance", d.data_ptr())
 
     def mask(self, hmap, items):
-        return self.orc.mask_from_hmap(hmap, items, self.size, False) > 0.5
+        return self.mask_from_hmap(hmap, items, self.size, False) > 0.5
+
+
+class EmuBackend(Backend):
+    def gather(self, off):
+        """State bytes at offsets `off`, indexed as the host array they are."""
+        return self.state.numpy()[off]
+
+
+class GpuBackend(Backend):
+    def __init__(self, pool, size, n, k, S, rollout, credit, seeds):
+        Backend.__init__(self, None, pool, size, n, k, S, rollout, credit, seeds)
+
+    def gather(self, off):
+        return self.host(self.state[self.new(off)])
 
 
 # ------------------------------------------------------------------------------------------------- the checked schedule
@@ -555,14 +515,16 @@ def pool_of(A, n):
 def test_host_tree_reproduces_the_fixtures(emu, name, case):
     """HostTree on its own -- its own float32 priors, its own draws and choices; the emulated env only steps the bins --
     under flat_policy: action, root n, root w, child count and stream position of every decision of the fixture."""
-    from test_mcts_search import flat_policy_np
+    import torch
+    from bpp_amd.mcts import flat_policy
     g = load_golden(name)
     size = tuple(int(v) for v in g["size"])
     S, k, depth, rollout, credit, episodes = case_params(g, case)
     N = min(len(g[case + "_seeds"]), 1 if case == "default" else 3)     # trajectories: bounded for the suite's wall time
     exp = expected(g, case)[:N]
     be = EmuBackend(emu, g["pool"][:N], size, N, k, S, rollout, credit, g[case + "_seeds"][:N], depth=depth)
-    pol = flat_policy_np(size)
+    tpol = flat_policy(size)
+    pol = lambda obs: tuple(t.numpy() for t in tpol(torch.from_numpy(obs))[:2])          # noqa: E731
     trees = [HostTree(k, be.max_depth, be.rollout, be.credit, float(np.prod(size)), s) for s in g[case + "_seeds"][:N]]
     ep, t = np.zeros(N, int), np.zeros(N, int)
     checked = 0

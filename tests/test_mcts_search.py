@@ -1,8 +1,9 @@
 """Batched MCTS (include/bpp_mcts.h, online-3d-bpp-drl_amd/mcts.py) against MCTS/monteCarlo.py's MCTree driven as
 mcts_test.py:14-65 drives it (fixtures: tests/golden/make_mcts_golden.py).
 
-CPU: the product kernels in the host SIMT emulator (tests/emu), the fixtures' flat policy between the launches; the sizes
-bound; argument checks.  `-m gpu`: BppVecEnv + MCTSearch on the device, the same policy in torch; subsets, invalid ids,
+One replay serves both tiers: MCTSearch on make_env's env with the fixtures' flat policy.  CPU: an EmuVecEnv
+(tests/emu_env.py) over the product kernels in the host SIMT emulator (tests/emu); the sizes bound; argument checks;
+subsets and invalid ids at 5x5x3.  `-m gpu`: a BppVecEnv on the device; subsets, invalid ids,
 the sync-free path, seed ranges, stream supply against pool supply, 2 048 slots against a host restatement over
 oracle/ref_port.py; the toolchain's float64 sqrt against numpy.
 
@@ -11,18 +12,18 @@ trajectories match bit for bit.  Under real logits the priors agree with float64
 what follows them (UCB choice, backup, play()) is exact given the priors' bits: tests/test_mcts_real_policy.py checks
 that launch by launch."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
+from emu_env import bind
+from test_reorder_search import make_env
 
 NOOP = np.iinfo(np.int64).min
 FILES = {"mcts_fake_10": ["default", "k2", "depth1", "depth0", "roll0", "roll2", "credit", "ep2"],
          "mcts_fake_8x12x9": ["wide"], "mcts_fake_5x5x3": ["small"], "mcts_fake_20x20x10": ["big"]}
 RUNS = [(f, c) for f, cs in FILES.items() for c in cs]
-MCTS_SRC = [os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_mcts.inl"), os.path.join(ROOT, "include", "bpp_mcts.h")]
 
 
 def _p(a):
@@ -44,142 +45,6 @@ def expected(g, c):
     return [[tuple(a[st[p * episodes + e]:st[p * episodes + e + 1]] for a in f) for e in range(episodes)] for p in range(N)]
 
 
-def flat_policy_np(size):
-    import torch
-    from bpp_amd.mcts import flat_policy
-    pol = flat_policy(size)
-
-    def policy(obs):
-        v, lg, _ = pol(torch.from_numpy(obs))
-        return np.ascontiguousarray(v.numpy()), np.ascontiguousarray(lg.numpy())
-    return policy
-
-
-def parse_roots(raw, E, cap, ids):
-    """(n, w, children, mt position) of the roots of bins ids from the raw state bytes (csrc/bpp_mcts.inl layout)."""
-    raw = np.asarray(raw).view(np.uint8)
-    bins = raw[:E * 192].view(np.int32).reshape(E, 48)
-    pool0 = E * 192 + E * 640 * 4
-    out = []
-    for e in ids:
-        half, pos = int(bins[e, 1]), int(bins[e, 3])
-        base = pool0 + (e * 2 + half) * cap * 32
-        rec = raw[base:base + 32]
-        w = float(rec[:8].view(np.float64)[0])
-        n, blk = (int(v) for v in rec[16:24].view(np.int32))
-        ch = int(raw[base + blk * 32 + 16:base + blk * 32 + 20].view(np.int32)[0]) if blk >= 0 else 0
-        out.append((n, w, ch, pos))
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------- CPU (emulator)
-def emu_mcts_lib(emu):
-    """The emulated library with the MCTS entry points of the current source (tests/emu's own staleness check does not
-    know bpp_mcts.inl / bpp_mcts.h): rebuilt and reloaded under a name of its own when older than them."""
-    from bpp_amd import _lib
-    L = emu.lib()
-    stale = any(os.path.getmtime(f) > os.path.getmtime(emu.LIB) for f in MCTS_SRC)
-    if stale or not all(hasattr(L, s) for s in _lib.MCTS_SYMBOLS):
-        import shutil
-        emu.build(force=True)
-        fresh = "%s.mcts.%d" % (emu.LIB, os.getpid())
-        shutil.copyfile(emu.LIB, fresh)
-        emu.LIB, emu._lib = fresh, None
-        L = emu.lib()
-        assert all(hasattr(L, s) for s in _lib.MCTS_SYMBOLS)
-    return L
-
-
-class EmuMcts(object):
-    """The schedule of MCTSearch.decide over the emulated library: real bins [0, n), scratch bins [n, 2n)."""
-
-    def __init__(self, emu, pool, size, n, k, S, depth=None, rollout=-1, credit=1, zeta=1e-5):
-        from bpp_amd import _lib
-        self._lib = _lib
-        self.emu, self.size, self.n, self.k, self.S = emu, tuple(int(v) for v in size), n, k, S
-        L = emu_mcts_lib(emu)
-        self.L = _lib.bind_mcts(L, emu.Batch)
-        L.bpp_step_subset.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                      ctypes.POINTER(emu.StepOut), ctypes.c_void_p, ctypes.c_void_p]
-        L.bpp_copy_bins.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                    ctypes.c_void_p]
-        self.env = emu.OracleEnv(pool, self.size, False, 2 * n)
-        self.env.reset()
-        self.A, self.E = self.env.A, 2 * n
-        self.max_depth = k - 1 if depth is None else min(depth, k - 1)
-        self.rollout = 0 if rollout is None else rollout
-        self.credit, self.zeta = float(credit), zeta
-        sizes = (ctypes.c_int64 * 4)()
-        assert self.L.bpp_mcts_sizes(self.E, k, S, self.max_depth, self.rollout, self.env.W, self.env.L, sizes) == 0
-        self.nbytes, self.cap, _, self.levels = (int(v) for v in sizes)
-        buf = np.zeros(self.nbytes + 16, np.uint8)
-        off = (-buf.ctypes.data) % 16
-        self.state = buf[off:off + self.nbytes]
-        self.overflow = np.zeros(1, np.int32)
-        self.policy = flat_policy_np(self.size)
-        self._last = None
-
-    def desc(self, ids, scratch):
-        return self._lib.Mcts(0 if ids is None else ids.shape[0], self.k, self.S, self.max_depth, self.rollout, self.cap, self.credit,
-                              self.zeta, None if ids is None else _p(ids).value, None if scratch is None else _p(scratch).value,
-                              _p(self.state).value, _p(self.overflow).value, 0)
-
-    def seed(self, ids, seeds):
-        ids, seeds = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(seeds, np.int64).astype(np.uint32)
-        m = self.desc(None, None)
-        assert self.L.bpp_mcts_seed(ctypes.byref(self.env._b), ctypes.byref(m), _p(ids), _p(seeds), ids.shape[0], None) == 0
-
-    def _step(self, ids, a):
-        n, env = ids.shape[0], self.env
-        r = dict(obs=np.zeros((n, 4 * self.A), np.float32), mask=np.zeros((n, self.A), np.float32), reward=np.zeros(n, np.float32),
-                 done=np.zeros(n, np.uint8), counter=np.zeros(n, np.int32), ratio=np.zeros(n), ep_ret=np.zeros(n),
-                 ep_len=np.zeros(n, np.int32))
-        out = self.emu.StepOut(*[_p(r[f]).value for f in ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len")])
-        a = np.ascontiguousarray(a, np.int64)
-        assert self.L.bpp_step_subset(ctypes.byref(env._b), _p(ids), n, _p(a), ctypes.byref(out), None, None) == 0
-        return r
-
-    def decide(self, ids, scratch=None):
-        ids = np.ascontiguousarray(ids, np.int64)
-        scratch = ids + self.n if scratch is None else np.ascontiguousarray(scratch, np.int64)
-        n, L, b = ids.shape[0], self.L, ctypes.byref(self.env._b)
-        m = self.desc(ids, scratch)
-        mr = ctypes.byref(m)
-        obs, acts = np.zeros((n, 4 * self.A), np.float32), np.zeros(n, np.int64)
-        assert L.bpp_mcts_begin(b, mr, None) == 0, L.bpp_last_error()
-        for _ in range(self.S):
-            assert L.bpp_copy_bins(b, None, _p(ids), _p(scratch), n, None) == 0
-            done = None
-            for level in range(self.max_depth):
-                assert L.bpp_mcts_select(b, mr, level, _p(done), _p(acts), None) == 0, L.bpp_last_error()
-                done = self._step(scratch, acts)["done"]
-            assert L.bpp_mcts_emit(b, mr, 0, _p(done), _p(obs), None) == 0, L.bpp_last_error()
-            value, logits = self.policy(obs)
-            assert L.bpp_mcts_expand(b, mr, _p(value), _p(logits), _p(acts), None) == 0
-            done = None
-            for level in range(1, self.levels):
-                done = self._step(scratch, acts)["done"]
-                assert L.bpp_mcts_emit(b, mr, level, _p(done), _p(obs), None) == 0
-                value, logits = self.policy(obs)
-                assert L.bpp_mcts_rollout(b, mr, _p(value), _p(logits), _p(acts), None) == 0
-            if self.levels > 0:
-                done = self._step(scratch, acts)["done"]
-            assert L.bpp_mcts_backup(b, mr, _p(done), None) == 0
-        act, vis = np.zeros(n, np.int64), np.zeros(n, np.int32)
-        assert L.bpp_mcts_finish(b, mr, _p(act), _p(vis), None) == 0
-        self._last = (ids, scratch)
-        return act, vis
-
-    def advance(self, done):
-        ids, scratch = self._last
-        m = self.desc(ids, scratch)
-        d = np.ascontiguousarray(done, np.uint8)
-        assert self.L.bpp_mcts_advance(ctypes.byref(self.env._b), ctypes.byref(m), _p(d), None) == 0
-
-    def roots(self, ids):
-        return parse_roots(self.state, self.E, self.cap, ids)
-
-
 def check_decisions(exp, ep, t, slots, traj, act, roots, bad):
     """Compare the decisions of live slots with the fixture; records (trajectory, slot) pairs that diverge in `bad`."""
     for j, s in enumerate(slots):
@@ -196,149 +61,11 @@ def check_decisions(exp, ep, t, slots, traj, act, roots, bad):
                 k, ep[s], (int(act[j]), n, w, ch, pos), tuple(x[k] for x in e))))
 
 
-def replay_emulated(emu, g, c, N):
-    size = tuple(int(v) for v in g["size"])
-    S, k, depth, rollout, credit, episodes = case_params(g, c)
-    exp = expected(g, c)[:N]
-    em = EmuMcts(emu, g["pool"][:N], size, N, k, S, depth, rollout, credit)
-    em.seed(np.arange(N), g[c + "_seeds"][:N])
-    ep, t, traj = np.zeros(N, int), np.zeros(N, int), np.arange(N)
-    live = np.arange(N)
-    bad = set()
-    ratios = np.zeros((N, episodes))
-    while live.size:
-        act, vis = em.decide(live)
-        check_decisions(exp, ep, t, live, traj, act, em.roots(live), bad)
-        assert not bad, sorted(bad)[:5]
-        r = em._step(live, act)
-        em.advance(r["done"])
-        t[live] += 1
-        for j, s in enumerate(live):
-            if r["done"][j]:
-                assert t[s] == len(exp[s][ep[s]][0]), "trajectory %d episode %d ends early" % (s, ep[s])
-                ratios[s, ep[s]] = r["ratio"][j]
-                ep[s] += 1
-                t[s] = 0
-        live = live[ep[live] < episodes]
-    np.testing.assert_array_equal(ratios.reshape(-1), g[c + "_ratio"][:N * episodes])
-    assert em.overflow[0] == 0
-
-
-# the emulator runs every fixture case; the S = 100 default case on its first 3 trajectories (the device runs all of them)
-EMU_TRAJ = {"default": 3}
-
-
-@pytest.mark.parametrize("name,case", RUNS)
-def test_emulated_mcts_matches_reference(emu, name, case):
-    g = load_golden(name)
-    N = len(g[case + "_seeds"])
-    replay_emulated(emu, g, case, min(N, EMU_TRAJ.get(case, N)))
-
-
-@pytest.mark.parametrize("name,case", RUNS)
-def test_fixture_is_meaningful(name, case):
-    """Every case plays whole episodes with more than one decision, its roots have children and visits, the stream is
-    consumed (ties broken, rollouts sampled), and the cases differ from each other."""
-    g = load_golden(name)
-    S, k, depth, rollout, credit, episodes = case_params(g, case)
-    st = g[case + "_start"]
-    assert (np.diff(st) >= 2).all()
-    assert (g[case + "_nch"] >= 1).all()
-    assert (g[case + "_n"] >= S).all()
-    assert len(set(g[case + "_pos"].tolist())) > 1
-
-
-def test_sizes_bound(emu):
-    from bpp_amd import _lib
-    L = _lib.bind_mcts(emu_mcts_lib(emu), emu.Batch)
-    out = (ctypes.c_int64 * 4)()
-    assert L.bpp_mcts_sizes(10, 4, 100, 3, -1, 10, 10, out) == 0
-    assert out[1] == 1 + 4 * 100 * 101 and out[3] == 4
-    assert out[2] == 192 + 640 * 4 + 2 * out[1] * 32 and out[0] == 10 * out[2]
-    assert L.bpp_mcts_sizes(1, 5, 40, 4, 2, 10, 10, out) == 0 and out[3] == 3
-    assert L.bpp_mcts_sizes(1, 4, 40, 3, 0, 10, 10, out) == 0 and out[3] == 0
-    assert L.bpp_mcts_sizes(1, 3, 40, 2, 5, 10, 10, out) == 0 and out[3] == 0     # k - d >= r + 1 never holds
-    assert L.bpp_mcts_sizes(1, 4, 40, 0, -1, 10, 10, out) == 0 and out[1] == 1 + 40 * 101
-    for args in ((1, 1, 10, 0, -1, 10, 10), (1, 17, 10, 3, -1, 10, 10), (1, 4, 0, 3, -1, 10, 10), (1, 4, 10, 4, -1, 10, 10),
-                 (1, 4, 10, 3, -2, 10, 10), (1, 4, 10, 3, -1, 40, 40)):
-        assert L.bpp_mcts_sizes(*args, out) != 0, args
-
-
-def test_emulated_argument_checks(emu):
-    from bpp_amd import _lib
-    L = _lib.bind_mcts(emu_mcts_lib(emu), emu.Batch)
-    pool = load_golden("mcts_fake_10")["pool"][:4]
-    ids, scratch = np.arange(2, dtype=np.int64), np.arange(2, 4, dtype=np.int64)
-    state, ovf = np.zeros(1 << 16, np.uint8), np.zeros(1, np.int32)
-    cap = 1 + 2 * 4 * 101
-    for rot, k, depth, cap_, credit, want in ((True, 3, 1, cap, 1.0, "rotation"), (False, 1, 0, cap, 1.0, "k must"),
-                                              (False, 3, 3, cap, 1.0, "max_depth"), (False, 3, 1, cap + 1, 1.0, "cap"),
-                                              (False, 3, 1, cap, 1.5, "credit")):
-        env = emu.OracleEnv(pool, (10, 10, 10), rot, 4)
-        m = _lib.Mcts(2, k, 4, depth, -1, cap_, credit, 1e-5, _p(ids).value, _p(scratch).value, _p(state).value, _p(ovf).value, 0)
-        assert L.bpp_mcts_begin(ctypes.byref(env._b), ctypes.byref(m), None) != 0
-        assert want in L.bpp_last_error().decode(), L.bpp_last_error()
-
-
-def test_emulated_invalid_ids_touch_nothing(emu):
-    """A slot whose real or scratch id lies outside [0, E) searches nothing and touches no state: the other slots decide
-    what they decide without it, and it gets BPP_ACTION_NOOP with 0 visits."""
-    g = load_golden("mcts_fake_10")
-    S, k, depth, rollout, credit, _ = case_params(g, "k2")
-    n = 4
-    a = EmuMcts(emu, g["pool"][:n], (10, 10, 10), n, k, S, depth, rollout, credit)
-    b = EmuMcts(emu, g["pool"][:n], (10, 10, 10), n, k, S, depth, rollout, credit)
-    for em in (a, b):
-        em.seed(np.arange(2 * n), np.arange(2 * n) + 5)
-    want = b.decide(np.arange(n))
-    ids, scratch = np.arange(n), np.arange(n) + n
-    ids[1] = -2
-    scratch[3] = 99
-    before = a.state.copy()
-    act, vis = a.decide(ids, scratch)
-    for j in (0, 2):
-        assert (act[j], vis[j]) == (want[0][j], want[1][j])
-    for j in (1, 3):
-        assert (act[j], vis[j]) == (NOOP, 0)
-    # bin 3's state (its slot's scratch id is bad) is as before
-    st = parse_roots(before, a.E, a.cap, [3]), parse_roots(a.state, a.E, a.cap, [3])
-    assert st[0] == st[1]
-    assert a.overflow[0] == 0
-
-
-def test_python_argument_checks():
-    from types import SimpleNamespace
-    from bpp_amd.mcts import MCTSearch
-    env = SimpleNamespace(can_rotate=False)
-    with pytest.raises(ValueError, match="rotation"):
-        MCTSearch(SimpleNamespace(can_rotate=True), 3)
-    for k in (1, 17):
-        with pytest.raises(ValueError, match="k must"):
-            MCTSearch(env, k)
-    with pytest.raises(ValueError, match="sim_times"):
-        MCTSearch(env, 3, sim_times=0)
-    with pytest.raises(ValueError, match="rollout_length"):
-        MCTSearch(env, 3, rollout_length=-2)
-    with pytest.raises(ValueError, match="credit"):
-        MCTSearch(env, 3, credit=1.5)
-    with pytest.raises(ValueError, match="zeta"):
-        MCTSearch(env, 3, zeta=0.0)
-
-
-# ---------------------------------------------------------------------------------------------------- GPU
-def _gpu_env(pool, size, E):
-    import torch
-    from bpp_amd import BppVecEnv
-    env = BppVecEnv(E, container_size=size, pool=np.ascontiguousarray(pool), device="cuda", compute_mask=True)
-    env.reset()
-    torch.cuda.synchronize()
-    return env
-
-
-def replay_gpu(g, c, N, reps=1, check=True):
-    """Play the first N trajectories of case c, each replicated `reps` times, with BppVecEnv + MCTSearch (real bins [0, M),
-    scratch [M, 2M), M = N * reps; bin b plays trajectory b mod N).  Returns the diverging (trajectory, bin, what) and the
-    overflow counter."""
+def replay(emu, g, c, N, reps=1, check=True):
+    """Play the first N trajectories of case c, each replicated `reps` times, with MCTSearch on make_env's env (real bins
+    [0, M), scratch [M, 2M), M = N * reps; bin b plays trajectory b mod N): the action and the root's n, w, child count
+    and stream position of every decision, every episode's length and final ratio.  Returns the diverging (trajectory,
+    bin, what) and the overflow counter."""
     import torch
     from bpp_amd import MCTSearch
     from bpp_amd.mcts import flat_policy
@@ -346,7 +73,7 @@ def replay_gpu(g, c, N, reps=1, check=True):
     S, k, depth, rollout, credit, episodes = case_params(g, c)
     exp = expected(g, c)[:N]
     M = N * reps
-    env = _gpu_env(g["pool"][:N], size, 2 * M)
+    env = make_env(emu, g["pool"][:N], size, 2 * M)
     ms = MCTSearch(env, k, sim_times=S, search_depth=depth, rollout_length=rollout, credit=credit)
     ms.seed(torch.arange(M), torch.as_tensor(np.tile(g[c + "_seeds"][:N], reps)))
     policy = flat_policy(size)
@@ -376,11 +103,123 @@ def replay_gpu(g, c, N, reps=1, check=True):
     return sorted(bad), int(ms.overflow.item())
 
 
+# ---------------------------------------------------------------------------------------------------- CPU (emulator)
+# the emulator runs every fixture case; the S = 100 default case on its first 3 trajectories (the device runs all of them)
+EMU_TRAJ = {"default": 3}
+
+
+@pytest.mark.parametrize("name,case", RUNS)
+def test_emulated_mcts_matches_reference(emu, name, case):
+    g = load_golden(name)
+    N = len(g[case + "_seeds"])
+    bad, ovf = replay(emu, g, case, min(N, EMU_TRAJ.get(case, N)))
+    assert not bad, bad[:5]
+    assert ovf == 0
+
+
+@pytest.mark.parametrize("name,case", RUNS)
+def test_fixture_is_meaningful(name, case):
+    """Every case plays whole episodes with more than one decision, its roots have children and visits, the stream is
+    consumed (ties broken, rollouts sampled), and the cases differ from each other."""
+    g = load_golden(name)
+    S, k, depth, rollout, credit, episodes = case_params(g, case)
+    st = g[case + "_start"]
+    assert (np.diff(st) >= 2).all()
+    assert (g[case + "_nch"] >= 1).all()
+    assert (g[case + "_n"] >= S).all()
+    assert len(set(g[case + "_pos"].tolist())) > 1
+
+
+def test_sizes_bound(emu):
+    from bpp_amd import _lib
+    L = bind(emu)
+    out = (ctypes.c_int64 * 4)()
+    assert L.bpp_mcts_sizes(10, 4, 100, 3, -1, 10, 10, out) == 0
+    assert out[1] == 1 + 4 * 100 * 101 and out[3] == 4
+    assert out[2] == 192 + 640 * 4 + 2 * out[1] * 32 and out[0] == 10 * out[2]
+    assert L.bpp_mcts_sizes(1, 5, 40, 4, 2, 10, 10, out) == 0 and out[3] == 3
+    assert L.bpp_mcts_sizes(1, 4, 40, 3, 0, 10, 10, out) == 0 and out[3] == 0
+    assert L.bpp_mcts_sizes(1, 3, 40, 2, 5, 10, 10, out) == 0 and out[3] == 0     # k - d >= r + 1 never holds
+    assert L.bpp_mcts_sizes(1, 4, 40, 0, -1, 10, 10, out) == 0 and out[1] == 1 + 40 * 101
+    for args in ((1, 1, 10, 0, -1, 10, 10), (1, 17, 10, 3, -1, 10, 10), (1, 4, 0, 3, -1, 10, 10), (1, 4, 10, 4, -1, 10, 10),
+                 (1, 4, 10, 3, -2, 10, 10), (1, 4, 10, 3, -1, 40, 40)):
+        assert L.bpp_mcts_sizes(*args, out) != 0, args
+
+
+def test_emulated_argument_checks(emu):
+    from bpp_amd import _lib
+    L = bind(emu)
+    pool = load_golden("mcts_fake_10")["pool"][:4]
+    ids, scratch = np.arange(2, dtype=np.int64), np.arange(2, 4, dtype=np.int64)
+    state, ovf = np.zeros(1 << 16, np.uint8), np.zeros(1, np.int32)
+    cap = 1 + 2 * 4 * 101
+    for rot, k, depth, cap_, credit, want in ((True, 3, 1, cap, 1.0, "rotation"), (False, 1, 0, cap, 1.0, "k must"),
+                                              (False, 3, 3, cap, 1.0, "max_depth"), (False, 3, 1, cap + 1, 1.0, "cap"),
+                                              (False, 3, 1, cap, 1.5, "credit")):
+        env = emu.OracleEnv(pool, (10, 10, 10), rot, 4)
+        m = _lib.Mcts(2, k, 4, depth, -1, cap_, credit, 1e-5, _p(ids).value, _p(scratch).value, _p(state).value, _p(ovf).value, 0)
+        assert L.bpp_mcts_begin(ctypes.byref(env._b), ctypes.byref(m), None) != 0
+        assert want in L.bpp_last_error().decode(), L.bpp_last_error()
+
+
+def test_emulated_invalid_ids_touch_nothing(emu):
+    """A slot whose real or scratch id lies outside [0, E) searches nothing and touches no state: the other slots decide
+    what they decide without it, and it gets BPP_ACTION_NOOP with 0 visits."""
+    import torch
+    from bpp_amd import MCTSearch
+    from bpp_amd.mcts import flat_policy
+    g = load_golden("mcts_fake_10")
+    S, k, depth, rollout, credit, _ = case_params(g, "k2")
+    n, size = 4, (10, 10, 10)
+    pol = flat_policy(size)
+    a, b = (MCTSearch(make_env(emu, g["pool"][:n], size, 2 * n), k, sim_times=S, search_depth=depth, rollout_length=rollout,
+                      credit=credit) for _ in range(2))
+    for ms in (a, b):
+        ms.seed(torch.arange(2 * n), torch.arange(2 * n) + 5)
+    want = b.decide(pol, torch.arange(n), torch.arange(n) + n)
+    ids, scratch = torch.arange(n), torch.arange(n) + n
+    ids[1] = -2
+    scratch[3] = 99
+    before = a.root_stats([3])
+    act, vis = a.decide(pol, ids, scratch, check=False)
+    for j in (0, 2):
+        assert (act[j], vis[j]) == (want[0][j], want[1][j])
+    for j in (1, 3):
+        assert (act[j], vis[j]) == (NOOP, 0)
+    # bin 3's state (its slot's scratch id is bad) is as before
+    assert [x.tobytes() for x in before] == [x.tobytes() for x in a.root_stats([3])]
+    assert int(a.overflow[0]) == 0
+
+
+def test_python_argument_checks():
+    from types import SimpleNamespace
+    from bpp_amd.mcts import MCTSearch
+    env = SimpleNamespace(can_rotate=False)
+    with pytest.raises(ValueError, match="rotation"):
+        MCTSearch(SimpleNamespace(can_rotate=True), 3)
+    for k in (1, 17):
+        with pytest.raises(ValueError, match="k must"):
+            MCTSearch(env, k)
+    with pytest.raises(ValueError, match="sim_times"):
+        MCTSearch(env, 3, sim_times=0)
+    with pytest.raises(ValueError, match="rollout_length"):
+        MCTSearch(env, 3, rollout_length=-2)
+    with pytest.raises(ValueError, match="credit"):
+        MCTSearch(env, 3, credit=1.5)
+    with pytest.raises(ValueError, match="zeta"):
+        MCTSearch(env, 3, zeta=0.0)
+
+
+# ---------------------------------------------------------------------------------------------------- GPU
+def _gpu_env(pool, size, E):
+    return make_env(None, pool, size, E)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,case", RUNS)
 def test_gpu_mcts_matches_reference(name, case):
     g = load_golden(name)
-    bad, ovf = replay_gpu(g, case, len(g[case + "_seeds"]))
+    bad, ovf = replay(None, g, case, len(g[case + "_seeds"]))
     assert not bad, bad[:10]
     assert ovf == 0
 
@@ -391,7 +230,7 @@ def test_gpu_mcts_matches_reference(name, case):
 def test_gpu_mcts_replicated(name, case):
     """Every trajectory 256 times (up to 2 048 slots, 4 096 bins): every replica equals the fixture."""
     g = load_golden(name)
-    bad, ovf = replay_gpu(g, case, len(g[case + "_seeds"]), reps=256)
+    bad, ovf = replay(None, g, case, len(g[case + "_seeds"]), reps=256)
     assert not bad, bad[:10]
     assert ovf == 0
 
@@ -399,39 +238,56 @@ def test_gpu_mcts_replicated(name, case):
 @pytest.mark.gpu
 def test_gpu_check_false_is_the_same():
     g = load_golden("mcts_fake_10")
-    bad, ovf = replay_gpu(g, "k2", 8, reps=4, check=False)
+    bad, ovf = replay(None, g, "k2", 8, reps=4, check=False)
     assert not bad and ovf == 0
 
 
-@pytest.mark.gpu
-def test_gpu_subsets_and_invalid_ids():
+def test_emulated_check_false_is_the_same(emu):
+    """The same on the emulator at the smallest fixture: 5x5x3, every trajectory twice."""
+    g = load_golden("mcts_fake_5x5x3")
+    bad, ovf = replay(emu, g, "small", len(g["small_seeds"]), reps=2, check=False)
+    assert not bad and ovf == 0
+
+
+def subsets_and_invalid_ids(emu, name, case, N, sub):
     """A decision for a subset of the bins, in any order, equals the decision of the full batch for those bins; ids out of
     range give BPP_ACTION_NOOP and touch nothing; check=True rejects duplicates and overlapping scratch bins."""
     import torch
     from bpp_amd import MCTSearch
     from bpp_amd.mcts import flat_policy
-    g = load_golden("mcts_fake_10")
-    S, k, depth, rollout, credit, _ = case_params(g, "k2")
-    N = 8
-    pol = flat_policy((10, 10, 10))
-    full_env = _gpu_env(g["pool"][:N], (10, 10, 10), 2 * N)
+    g = load_golden(name)
+    size = tuple(int(v) for v in g["size"])
+    S, k, depth, rollout, credit, _ = case_params(g, case)
+    pol = flat_policy(size)
+    full_env = make_env(emu, g["pool"][:N], size, 2 * N)
+    dev = full_env.device
     full = MCTSearch(full_env, k, sim_times=S, search_depth=depth, rollout_length=rollout, credit=credit)
-    ids = torch.arange(N, device="cuda")
+    ids = torch.arange(N, device=dev)
     want_a, want_v = full.decide(pol, ids, ids + N)
-    env = _gpu_env(g["pool"][:N], (10, 10, 10), 2 * N)
+    env = make_env(emu, g["pool"][:N], size, 2 * N)
     ms = MCTSearch(env, k, sim_times=S, search_depth=depth, rollout_length=rollout, credit=credit)
-    sub = torch.tensor([6, 1, 3], device="cuda")
+    sub = torch.tensor(sub, device=dev)
     a, v = ms.decide(pol, sub, sub + N)
     assert torch.equal(a, want_a[sub]) and torch.equal(v, want_v[sub])
-    bad_ids = torch.tensor([0, -1, 2, 40], device="cuda")
-    a, v = ms.decide(pol, bad_ids, torch.tensor([8, 9, 10, 11], device="cuda"), check=False)
+    bad_ids = torch.tensor([0, -1, 2, 40], device=dev)
+    a, v = ms.decide(pol, bad_ids, torch.arange(N, N + 4, device=dev), check=False)
     assert int(a[1]) == NOOP and int(a[3]) == NOOP and int(v[1]) == 0 and int(v[3]) == 0
     assert int(a[0]) == int(want_a[0]) and int(a[2]) == int(want_a[2])
     with pytest.raises(ValueError):
-        ms.decide(pol, torch.tensor([0, 0], device="cuda"), torch.tensor([8, 9], device="cuda"))
+        ms.decide(pol, torch.tensor([0, 0], device=dev), torch.tensor([N, N + 1], device=dev))
     with pytest.raises(ValueError):
-        ms.decide(pol, torch.tensor([0, 1], device="cuda"), torch.tensor([1, 9], device="cuda"))
+        ms.decide(pol, torch.tensor([0, 1], device=dev), torch.tensor([1, N + 1], device=dev))
     assert int(ms.overflow.item()) == 0
+
+
+@pytest.mark.gpu
+def test_gpu_subsets_and_invalid_ids():
+    subsets_and_invalid_ids(None, "mcts_fake_10", "k2", 8, [6, 1, 3])
+
+
+def test_emulated_subsets_and_invalid_ids(emu):
+    """The same on the emulator: 5x5x3, k = 4, sim_times = 30, 8 slots."""
+    subsets_and_invalid_ids(emu, "mcts_fake_5x5x3", "small", 8, [6, 1, 3])
 
 
 @pytest.mark.gpu

@@ -1,20 +1,21 @@
 """Multi-bin packing (include/bpp_multibin.h, online-3d-bpp-drl_amd/multibin.py) against the unmodified
 multi_bin/multi_bin.py, driven by its own test() (fixtures: tests/golden/make_multibin_golden.py).
 
-CPU: the product kernels in the host SIMT emulator (tests/emu), the fixtures' fake policy between emit and choose; argument
-checks.  `-m gpu`: BppVecEnv + MultiBinPacker on the device with bpp_amd.reorder.int_policy, and a float64 host
-restatement of the decision rule over the oracle env."""
+One replay serves both tiers: MultiBinPacker on make_env's env with bpp_amd.reorder.int_policy.  CPU: an EmuVecEnv
+(tests/emu_env.py) over the product kernels in the host SIMT emulator (tests/emu); argument checks.  `-m gpu`: a BppVecEnv
+on the device, and a float64 host restatement of the decision rule over the oracle env."""
 import ctypes
 import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
+from emu_env import bind
+from test_reorder_search import make_env
 
 NOOP = np.iinfo(np.int64).min
 CASES = ["multibin_fake_20x20x10", "multibin_fake_20x20x10_s5", "multibin_fake_30x30x10"]
-MULTIBIN_SRC = [os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_multibin.inl"), os.path.join(ROOT, "include", "bpp_multibin.h")]
 COV_NAMES = ("skipped_window", "tie_at_max", "no_window", "chosen_again", "failed_placement", "keyerror")
 
 
@@ -40,103 +41,51 @@ def window_policy(w, H):
     return int_policy((w, w, H), mask_fn=lambda obs: torch.zeros((obs.shape[0], w * w), dtype=torch.float32, device=obs.device))
 
 
-# ---------------------------------------------------------------------------------------------------- CPU (emulator)
-def emu_multibin_lib(emu):
-    """The emulated library with the multi-bin entry points of the current source (tests/emu's own staleness check does not
-    know bpp_multibin.inl / bpp_multibin.h): rebuilt and reloaded under a name of its own when older than them."""
-    from bpp_amd import _lib
-    L = emu.lib()
-    stale = any(os.path.getmtime(f) > os.path.getmtime(emu.LIB) for f in MULTIBIN_SRC)
-    if stale or not all(hasattr(L, s) for s in _lib.MULTIBIN_SYMBOLS):
-        import shutil
-        emu.build(force=True)
-        fresh = "%s.multibin.%d" % (emu.LIB, os.getpid())
-        shutil.copyfile(emu.LIB, fresh)
-        emu.LIB, emu._lib = fresh, None
-        L = emu.lib()
-        assert all(hasattr(L, s) for s in _lib.MULTIBIN_SYMBOLS)
-    return _lib.bind_multibin(L, emu.Batch)
-
-
-class EmuMultiBin(object):
-    """MultiBinPacker's schedule over the emulated library: E pallets, slots = the listed pallets."""
-
-    def __init__(self, emu, pool, size, w, s, E):
-        import torch
-        from bpp_amd import _lib
-        self.emu, self.size, self.w, self.s = emu, size, w, s
-        self.L = emu_multibin_lib(emu)
-        self.L.bpp_step_subset.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.POINTER(emu.StepOut), ctypes.c_void_p, ctypes.c_void_p]
-        self.env = emu.OracleEnv(pool, size, False, E)
-        self.env.reset()
-        sizes = (ctypes.c_int64 * 3)()
-        assert self.L.bpp_multibin_sizes(size[0], size[1], w, s, 0, E, sizes) == 0
-        self.K = int(sizes[0])
-        self.state = np.zeros(int(sizes[1]) // 8, np.float64)
-        pol = window_policy(w, size[2])
-        self.policy = lambda obs: tuple(np.ascontiguousarray(t.numpy()) for t in pol(torch.from_numpy(obs)))
-        self._lib = _lib
-
-    def _step(self, ids, a):
-        n, A = ids.shape[0], self.env.A
-        r = dict(obs=np.zeros((n, 4 * A), np.float32), mask=np.zeros((n, A), np.float32), reward=np.zeros(n, np.float32),
-                 done=np.zeros(n, np.uint8), counter=np.zeros(n, np.int32), ratio=np.zeros(n), ep_ret=np.zeros(n),
-                 ep_len=np.zeros(n, np.int32))
-        out = self.emu.StepOut(*[_p(r[f]).value for f in ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len")])
-        a = np.ascontiguousarray(a, np.int64)
-        assert self.L.bpp_step_subset(ctypes.byref(self.env._b), _p(ids), n, _p(a), ctypes.byref(out), None, None) == 0
-        return r
-
-    def decide_step(self, ids):
-        """decide, step, commit for pallets ids; returns (action, adv, window, step outputs)."""
-        ids = np.ascontiguousarray(ids, np.int64)
-        n, L, b, w = ids.shape[0], self.L, ctypes.byref(self.env._b), self.w
-        sizes = (ctypes.c_int64 * 3)()
-        assert L.bpp_multibin_sizes(self.size[0], self.size[1], w, self.s, n, self.env.E, sizes) == 0
-        work = np.zeros(int(sizes[2]) + 16, np.uint8)
-        off = (-work.ctypes.data) % 16
-        work = work[off:off + int(sizes[2])]
-        m = self._lib.MultiBin(n, w, self.s, self.K, _p(ids).value, _p(self.state).value, _p(work).value)
-        obs = np.zeros((n * self.K, 4 * w * w), np.float32)
-        assert L.bpp_multibin_emit(b, ctypes.byref(m), _p(obs), None) == 0, L.bpp_last_error()
-        value, logits, _ = self.policy(obs)
-        act, adv, win = np.zeros(n, np.int64), np.zeros(n), np.zeros(n, np.int32)
-        assert L.bpp_multibin_choose(b, ctypes.byref(m), _p(value), _p(logits), _p(act), _p(adv), _p(win), None) == 0
-        r = self._step(ids, act)
-        assert L.bpp_multibin_commit(b, ctypes.byref(m), _p(r["done"]), None) == 0
-        return act, adv, win, r
-
-
-def replay_emulated(emu, g):
+def replay(emu, g, reps=1):
+    """Play fixture g's trajectories, each replicated `reps` times (pallet b plays trajectory b mod n), with MultiBinPacker
+    on make_env's env: action, window and adv (bit for bit) of every decision, the episode's length, counter and ratio;
+    returns the (trajectory, replica) pairs that diverge."""
+    import torch
+    from bpp_amd import MultiBinPacker
     size, w, s = _geometry(g)
     recs = _records(g)
     n = len(recs)
-    em = EmuMultiBin(emu, g["pool"], size, w, s, n)
-    live = np.arange(n)
+    N = n * reps
+    env = make_env(emu, g["pool"], size, N)
+    mb = MultiBinPacker(env, w, s)
+    policy = window_policy(w, size[2])
+    live = torch.arange(N, device=env.device)
+    bad = set()
     t = 0
-    while live.size:
-        act, adv, win, r = em.decide_step(live)
-        for j, p in enumerate(live):
+    while live.numel():
+        act, adv, win = mb.decide(policy, live)
+        r = env.step_bins(live, act)
+        mb.commit(r.done)
+        a, v, wn, lv = act.cpu().numpy(), adv.cpu().numpy(), win.cpu().numpy(), live.cpu().numpy()
+        done, cnt, rat = r.done.cpu().numpy(), r.counter.cpu().numpy(), r.ratio.cpu().numpy()
+        keep = np.ones(lv.size, bool)
+        for j, b in enumerate(lv):
+            p = b % n
             ra, re, rw = recs[p]
-            assert t < len(ra), "trajectory %d plays longer than the reference" % p
-            assert (act[j], win[j]) == (ra[t], rw[t]), "traj %d decision %d: action %d window %d, reference %d / %d" % (
-                p, t, act[j], win[j], ra[t], rw[t])
-            assert adv[j].tobytes() == np.float64(re[t]).tobytes(), "traj %d decision %d: adv %r != %r" % (p, t, adv[j], re[t])
-        keep = np.ones(live.size, bool)
-        for j, p in enumerate(live):
-            if r["done"][j] or (g["keyerror"][p] and t == len(recs[p][0]) - 1):
-                assert t == len(recs[p][0]) - 1, "trajectory %d ends early" % p
-                if r["done"][j]:
-                    assert (r["counter"][j], r["ratio"][j]) == (g["counter"][p], g["ratio"][p]), p
+            last = t == len(ra) - 1
+            if t >= len(ra) or not (a[j] == ra[t] and wn[j] == rw[t] and v[j].tobytes() == np.float64(re[t]).tobytes()):
+                bad.add((int(p), int(b // n)))
                 keep[j] = False
-        live = live[keep]
+                continue
+            if done[j] and not (last and cnt[j] == g["counter"][p] and rat[j] == g["ratio"][p]):
+                bad.add((int(p), int(b // n)))
+            if done[j] or (last and g["keyerror"][p]):
+                keep[j] = False
+        live = live[torch.from_numpy(keep).to(env.device)]
         t += 1
+    return sorted(bad)
 
 
+# ---------------------------------------------------------------------------------------------------- CPU (emulator)
 @pytest.mark.parametrize("case", CASES)
 def test_emulated_multibin_matches_reference(emu, case):
-    replay_emulated(emu, load_golden(case))
+    bad = replay(emu, load_golden(case))
+    assert not bad, "diverging trajectories: %r" % bad[:20]
 
 
 def test_fixture_coverage():
@@ -156,7 +105,7 @@ def test_fixture_coverage():
 
 def test_emulated_argument_checks(emu):
     from bpp_amd import _lib
-    L = emu_multibin_lib(emu)
+    L = bind(emu)
     out = (ctypes.c_int64 * 3)()
     assert L.bpp_multibin_sizes(20, 20, 10, 10, 4, 8, out) == 0 and out[0] == 4 and out[1] == 8 * 4 * 24
     assert L.bpp_multibin_sizes(20, 20, 10, 5, 4, 8, out) == 0 and out[0] == 9
@@ -179,21 +128,29 @@ def test_emulated_argument_checks(emu):
 def test_emulated_invalid_ids_touch_nothing(emu):
     """A slot whose id lies outside [0, E) emits nothing, gets BPP_ACTION_NOOP and touches no pallet and no record; the other
     slots decide as in a run without it."""
+    import torch
+    from bpp_amd import MultiBinPacker
     g = load_golden("multibin_fake_20x20x10")
     size, w, s = _geometry(g)
-    a = EmuMultiBin(emu, g["pool"][:6], size, w, s, 6)
-    b = EmuMultiBin(emu, g["pool"][:6], size, w, s, 6)
+    policy = window_policy(w, size[2])
+    env_a, env_b = (make_env(emu, g["pool"][:6], size, 6) for _ in range(2))
+    a, b = MultiBinPacker(env_a, w, s), MultiBinPacker(env_b, w, s)
+
+    def decide_step(mb, ids):
+        dec = mb.decide(policy, torch.tensor(ids), check=False)
+        mb.commit(mb.env.step_bins(ids, dec[0], check=False).done)
+        return [t.numpy() for t in dec]
     for _ in range(3):
-        want = b.decide_step(np.arange(6))
-        got = a.decide_step(np.array([0, 1, -3, 3, 4, 5, 6 + 7]))
+        want = decide_step(b, list(range(6)))
+        got = decide_step(a, [0, 1, -3, 3, 4, 5, 6 + 7])
         for j, jj in ((0, 0), (1, 1), (3, 3), (4, 4), (5, 5)):
             assert (got[0][jj], got[1][jj], got[2][jj]) == (want[0][j], want[1][j], want[2][j])
         for jj in (2, 6):
             assert (got[0][jj], got[1][jj], got[2][jj]) == (NOOP, 0.0, -1)
-        late = a.decide_step(np.array([2]))                  # pallet 2 was left out above: it decides on its own
+        late = decide_step(a, [2])                            # pallet 2 was left out above: it decides on its own
         assert (late[0][0], late[1][0], late[2][0]) == (want[0][2], want[1][2], want[2][2])
-    np.testing.assert_array_equal(a.env.hmap, b.env.hmap)
-    np.testing.assert_array_equal(a.state.view(np.int64), b.state.view(np.int64))
+    np.testing.assert_array_equal(env_a.oracle.hmap, env_b.oracle.hmap)
+    assert torch.equal(a.state.view(torch.int64), b.state.view(torch.int64))
 
 
 def test_python_argument_checks():
@@ -226,57 +183,13 @@ def test_python_argument_checks():
 
 # ---------------------------------------------------------------------------------------------------- GPU
 def _gpu_env(pool, size, E):
-    import torch
-    from bpp_amd import BppVecEnv
-    env = BppVecEnv(E, container_size=size, pool=np.ascontiguousarray(pool), device="cuda", compute_mask=True)
-    env.reset()
-    torch.cuda.synchronize()
-    return env
-
-
-def replay_gpu(g, reps=1):
-    """Play fixture g's trajectories, each replicated `reps` times (pallet b plays trajectory b mod n), with BppVecEnv +
-    MultiBinPacker; returns the (trajectory, replica) pairs that diverge."""
-    import torch
-    from bpp_amd import MultiBinPacker
-    size, w, s = _geometry(g)
-    recs = _records(g)
-    n = len(recs)
-    N = n * reps
-    env = _gpu_env(g["pool"], size, N)
-    mb = MultiBinPacker(env, w, s)
-    policy = window_policy(w, size[2])
-    live = torch.arange(N, device=env.device)
-    bad = set()
-    t = 0
-    while live.numel():
-        act, adv, win = mb.decide(policy, live)
-        r = env.step_bins(live, act)
-        mb.commit(r.done)
-        a, v, wn, lv = act.cpu().numpy(), adv.cpu().numpy(), win.cpu().numpy(), live.cpu().numpy()
-        done, cnt, rat = r.done.cpu().numpy(), r.counter.cpu().numpy(), r.ratio.cpu().numpy()
-        keep = np.ones(lv.size, bool)
-        for j, b in enumerate(lv):
-            p = b % n
-            ra, re, rw = recs[p]
-            last = t == len(ra) - 1
-            if t >= len(ra) or not (a[j] == ra[t] and wn[j] == rw[t] and v[j].tobytes() == np.float64(re[t]).tobytes()):
-                bad.add((int(p), int(b // n)))
-                keep[j] = False
-                continue
-            if done[j] and not (last and cnt[j] == g["counter"][p] and rat[j] == g["ratio"][p]):
-                bad.add((int(p), int(b // n)))
-            if done[j] or (last and g["keyerror"][p]):
-                keep[j] = False
-        live = live[torch.from_numpy(keep).to(env.device)]
-        t += 1
-    return sorted(bad)
+    return make_env(None, pool, size, E)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES)
 def test_gpu_multibin_matches_reference(case):
-    bad = replay_gpu(load_golden(case))
+    bad = replay(None, load_golden(case))
     assert not bad, "diverging trajectories: %r" % bad[:20]
 
 
@@ -284,23 +197,30 @@ def test_gpu_multibin_matches_reference(case):
 @pytest.mark.parametrize("case", CASES)
 def test_gpu_multibin_replicated(case):
     """Every trajectory x 256 replicas; every replica equals the fixture."""
-    bad = replay_gpu(load_golden(case), reps=256)
+    bad = replay(None, load_golden(case), reps=256)
     assert not bad, "diverging (trajectory, replica) pairs: %r" % bad[:20]
 
 
 def _snapshot(env, mb):
+    """Heightmaps, bpp_env_state records (as int32 words) and the packer's records, copied to the host."""
     import torch
-    torch.cuda.synchronize()
-    return env.hmap.cpu().numpy().copy(), env.state_numpy().copy(), mb.state.view(torch.int64).cpu().numpy().copy()
+    return env.hmap.cpu().numpy().copy(), env.state.cpu().numpy().copy(), mb.state.view(torch.int64).cpu().numpy().copy()
 
 
 @pytest.mark.gpu
 def test_gpu_subset_leaves_other_pallets_alone():
+    subset_leaves_other_pallets_alone(None, 64)
+
+
+def test_emulated_subset_leaves_other_pallets_alone(emu):
+    subset_leaves_other_pallets_alone(emu, 10)
+
+
+def subset_leaves_other_pallets_alone(emu, E):
     import torch
     from bpp_amd import MultiBinPacker
     g = load_golden("multibin_fake_20x20x10")
-    E = 64
-    env = _gpu_env(g["pool"], (20, 20, 10), E)
+    env = make_env(emu, g["pool"], (20, 20, 10), E)
     mb = MultiBinPacker(env)
     policy = window_policy(10, 10)
     for _ in range(3):                                   # every pallet with some history
@@ -323,11 +243,19 @@ def test_gpu_subset_leaves_other_pallets_alone():
 
 @pytest.mark.gpu
 def test_gpu_invalid_ids_give_noop():
+    invalid_ids_give_noop(None)
+
+
+def test_emulated_invalid_ids_give_noop(emu):
+    invalid_ids_give_noop(emu)
+
+
+def invalid_ids_give_noop(emu):
     import torch
     from bpp_amd import MultiBinPacker
     g = load_golden("multibin_fake_20x20x10")
     E = 16
-    envs = [_gpu_env(g["pool"], (20, 20, 10), E) for _ in range(2)]
+    envs = [make_env(emu, g["pool"], (20, 20, 10), E) for _ in range(2)]
     mbs = [MultiBinPacker(e) for e in envs]
     policy = window_policy(10, 10)
     dev = envs[0].device

@@ -9,14 +9,12 @@ geometries give bin_num = 9, 6.25, 4 and 2.25, so bin_num * reward + (v - last) 
 multiply-add would round once.  Every launch feeds one family to every window of every pallet; a pallet set plays six
 decide / step / commit rounds, so windows are chosen again with history.
 
-Two tiers: the product kernels on the host SIMT emulator, and `-m gpu` on the MI355X through MultiBinPacker."""
-import ctypes
-
+Two tiers, one body: MultiBinPacker on an EmuVecEnv over the host SIMT emulator, and `-m gpu` on a BppVecEnv on the MI355X."""
 import numpy as np
 import pytest
 
 import search_inputs as si
-from test_multibin import EmuMultiBin, _p
+from test_reorder_search import make_env
 
 # (pallet, window side, stride): w^2 = 100, 64, 25, 400
 GEOMETRIES = {"30x30_w10": ((30, 30, 10), 10, 10), "20x20_w8_s4": ((20, 20, 10), 8, 4), "10x10_w5": ((10, 10, 10), 5, 5),
@@ -128,73 +126,37 @@ def check_launch(host, label, value, x, masks, action, adv, win, items, what):
     return share, want_w
 
 
-class EmuTier(object):
-    pallets = 21
+class Tier(object):
+    """emu: the emulated library (21 pallets), or None for the device (1 024 pallets)."""
 
-    def __init__(self, emu):
-        self.emu = emu
-
-    def start(self, geometry):
-        size, w, s = GEOMETRIES[geometry]
-        E = self.pallets
-        self.em = EmuMultiBin(self.emu, small_items(size, E), size, w, s, E)
-        env = self.em.env
-        for t in range(WARM_STEPS):
-            env.step(self.emu.sample_feasible(env.out["mask"], 5, t))
-        return Host(size, w, s, E)
-
-    def round(self, host, label, seed):
-        """emit, the family's rows, choose, step, commit.  Returns what check_launch and Host.update need."""
-        em, E, K, w = self.em, host.E, host.K, host.w
-        ids = np.arange(E, dtype=np.int64)
-        L, b = em.L, ctypes.byref(em.env._b)
-        sizes = (ctypes.c_int64 * 3)()
-        assert L.bpp_multibin_sizes(host.size[0], host.size[1], w, host.s, E, E, sizes) == 0
-        buf = np.zeros(int(sizes[2]) + 16, np.uint8)
-        off = (-buf.ctypes.data) % 16
-        work = buf[off:off + int(sizes[2])]
-        m = em._lib.MultiBin(E, w, host.s, K, _p(ids).value, _p(em.state).value, _p(work).value)
-        obs = np.zeros((E * K, 4 * w * w), np.float32)
-        assert L.bpp_multibin_emit(b, ctypes.byref(m), _p(obs), None) == 0, L.bpp_last_error()
-        masks = masks_of(work, E, K, w * w)
-        check_masks(masks, obs, self.emu.mask_from_obs, w, host.size[2])
-        value, x = family_rows(label, masks, seed)
-        act, adv, win = np.zeros(E, np.int64), np.zeros(E), np.zeros(E, np.int32)
-        assert L.bpp_multibin_choose(b, ctypes.byref(m), _p(value), _p(x), _p(act), _p(adv), _p(win), None) == 0
-        r = em._step(ids, act)
-        assert L.bpp_multibin_commit(b, ctypes.byref(m), _p(r["done"]), None) == 0
-        items = obs.reshape(E, K, 4, w * w)[:, 0, 1:, 0].astype(np.int64)
-        return value, x, masks, act, adv, win, items, r["done"]
-
-
-class GpuTier(object):
-    pallets = 1024
+    def __init__(self, emu=None):
+        self.emu, self.pallets = emu, 1024 if emu is None else 21
+        if emu is None:
+            from oracle import oracle as emu
+        self.mask_from_obs = emu.mask_from_obs
 
     def start(self, geometry):
-        import torch
-        from bpp_amd import BppVecEnv, MultiBinPacker
+        from bpp_amd import MultiBinPacker
         size, w, s = GEOMETRIES[geometry]
         E = self.pallets
-        self.env = BppVecEnv(E, container_size=size, pool=small_items(size, E), device="cuda", compute_mask=True)
-        self.env.reset()
+        self.env = make_env(self.emu, small_items(size, E), size, E)
         for t in range(WARM_STEPS):
             self.env.step_tensors(self.env.sample_feasible(seed=5, step=t))
         self.mb = MultiBinPacker(self.env, w, s)
-        torch.cuda.synchronize()
         return Host(size, w, s, E)
 
     def round(self, host, label, seed):
+        """decide under the family's rows, step, commit.  Returns what check_launch and Host.update need."""
         import torch
         env, mb, E, K, w = self.env, self.mb, host.E, host.K, host.w
         got = {}
 
         def policy(obs):
-            from oracle import oracle as orc
             masks = masks_of(mb._sets[E]["work"].cpu().numpy(), E, K, w * w)
-            check_masks(masks, obs.cpu().numpy(), orc.mask_from_obs, w, host.size[2])
+            check_masks(masks, obs.cpu().numpy(), self.mask_from_obs, w, host.size[2])
             value, x = family_rows(label, masks, seed)
             got.update(value=value, x=x, masks=masks, items=obs.cpu().numpy().reshape(E, K, 4, w * w)[:, 0, 1:, 0].astype(np.int64))
-            return torch.from_numpy(value).cuda(), torch.from_numpy(x).cuda(), None
+            return torch.from_numpy(value).to(env.device), torch.from_numpy(x).to(env.device), None
         act, adv, win = mb.decide(policy)
         r = env.step_tensors(act)
         mb.commit(r.done)
@@ -207,8 +169,8 @@ def tier(request):
     if request.param == "gpu":
         import torch
         assert torch.cuda.is_available()
-        return GpuTier()
-    return EmuTier(request.getfixturevalue("emu"))
+        return Tier()
+    return Tier(request.getfixturevalue("emu"))
 
 
 @pytest.mark.parametrize("geometry", sorted(GEOMETRIES))

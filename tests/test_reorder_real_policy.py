@@ -10,13 +10,13 @@ family rows get the feasibility mask of the emitted observation (the env's own r
 uniform-feasible steps) joined with 30 % random cells -- the env's masks alone leave rows with one or two feasible cells,
 too few for the wide families to be decidable in float64 -- and adapted where a family needs a mask of its own.
 
-Two tiers: the product kernel on the host SIMT emulator, and `-m gpu` on the MI355X through ReorderSearch."""
+Two tiers, one body: ReorderSearch on an EmuVecEnv over the host SIMT emulator, and `-m gpu` on a BppVecEnv on the MI355X."""
 import numpy as np
 import pytest
 
 import search_inputs as si
 from conftest import load_golden
-from test_reorder_search import NOOP, EmuReorder
+from test_reorder_search import NOOP, make_env
 
 SIZES = {25: ("reorder_fake_5x5x3", (5, 5, 3)), 96: ("reorder_fake_8x12x9", (8, 12, 9)), 100: ("reorder_fake_10", (10, 10, 10)),
          400: ("mcts_fake_20x20x10", (20, 20, 10))}
@@ -54,47 +54,32 @@ class Recorder(object):
         return np.full(n, 0.5, np.float32), np.ascontiguousarray(x), feas.astype(np.float32)
 
 
-class EmuTier(object):
-    rows = 21
+class Tier(object):
+    """emu: the emulated library (21 slots), or None for the device (259 slots)."""
 
-    def __init__(self, emu):
-        self.emu = emu
+    def __init__(self, emu=None):
+        self.emu, self.rows = emu, 259 if emu is None else 21
+
+    def mask_fn(self, size):
+        import torch
+        if self.emu is not None:
+            return lambda obs: self.emu.mask_from_obs(obs, size, False)
+        from bpp_amd.masks import batched_mask_from_obs
+        return lambda obs: batched_mask_from_obs(torch.from_numpy(obs).cuda(), size).cpu().numpy()
 
     def run(self, A, label, family_call, seed):
         """One k = 2 decision; returns (x, m, actions of the family's launch)."""
-        emu = self.emu
-        pool, size = pool_rows(A, self.rows)
-        er = EmuReorder(emu, pool, size, self.rows, 2)
-        for t in range(WARM_STEPS):
-            er.env.step(emu.sample_feasible(er.env.out["mask"], 7, t))
-        rec = Recorder(size, lambda obs: emu.mask_from_obs(obs, size, False), family_call, label, seed)
-        er.policy = rec
-        acts = []
-        step = er._step
-        er._step = lambda ids, a: (acts.append(np.array(a)), step(ids, a))[1]
-        er.decide(np.arange(self.rows))
-        assert er.overflow[0] == 0 and rec.calls == 4
-        return rec.x, rec.m, acts[family_call]
-
-
-class GpuTier(object):
-    rows = 259
-
-    def run(self, A, label, family_call, seed):
         import torch
-        from bpp_amd import BppVecEnv, ReorderSearch
-        from bpp_amd.masks import batched_mask_from_obs
+        from bpp_amd import ReorderSearch
         n = self.rows
         pool, size = pool_rows(A, n)
-        env = BppVecEnv(2 * n, container_size=size, pool=pool, device="cuda", compute_mask=True)
-        env.reset()
+        env = make_env(self.emu, pool, size, 2 * n)
         for t in range(WARM_STEPS):
             env.step_tensors(env.sample_feasible(seed=7, step=t))
-        rec = Recorder(size, lambda obs: batched_mask_from_obs(torch.from_numpy(obs).cuda(), size).cpu().numpy(), family_call,
-                       label, seed)
+        rec = Recorder(size, self.mask_fn(size), family_call, label, seed)
 
         def policy(obs):
-            return tuple(torch.from_numpy(np.ascontiguousarray(t)).cuda() for t in rec(obs.cpu().numpy()))
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(env.device) for t in rec(obs.cpu().numpy()))
         acts = []
         step = env.step_bins
         env.step_bins = lambda ids, a, **kw: (acts.append(a.cpu().numpy().copy()), step(ids, a, **kw))[1]
@@ -110,8 +95,8 @@ def tier(request):
     if request.param == "gpu":
         import torch
         assert torch.cuda.is_available()
-        return GpuTier()
-    return EmuTier(request.getfixturevalue("emu"))
+        return Tier()
+    return Tier(request.getfixturevalue("emu"))
 
 
 @pytest.mark.parametrize("A", sorted(SIZES))

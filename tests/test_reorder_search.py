@@ -1,21 +1,21 @@
 """BPP-k reorder search (include/bpp_reorder.h, online-3d-bpp-drl_amd/reorder.py) against acktr/reorder.py's ReorderTree
 driven as unified_test.py:9-27 drives it (fixtures: tests/golden/make_reorder_golden.py).
 
-CPU: the product kernels in the host SIMT emulator (tests/emu), the fixtures' fake policy in numpy between the levels;
-argument checks.  `-m gpu`: BppVecEnv + ReorderSearch on the device, the same fake policy in torch."""
+One replay serves both tiers: ReorderSearch on make_env's env with the fixtures' fake policy in torch.  CPU: an EmuVecEnv
+(tests/emu_env.py) over the product kernels in the host SIMT emulator (tests/emu); argument checks.  `-m gpu`: a BppVecEnv
+on the device."""
 import ctypes
-import math
 import os
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_golden
+from emu_env import EmuVecEnv, bind
 
 NOOP = np.iinfo(np.int64).min
 FAKE_CASES = ["reorder_fake_10", "reorder_fake_8x12x9", "reorder_fake_5x5x3"]
 FAKE_RUNS = [("reorder_fake_10", k) for k in (1, 2, 3, 4, 5)] + [("reorder_fake_8x12x9", 3)] + [("reorder_fake_5x5x3", k) for k in (2, 3, 4)]
-REORDER_SRC = [os.path.join(ROOT, "online-3d-bpp-drl_amd", "csrc", "bpp_reorder.inl"), os.path.join(ROOT, "include", "bpp_reorder.h")]
 COV_NAMES = ("disable", "will_terminate", "conservative", "default_true", "default_false")
 
 
@@ -23,22 +23,27 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-# ---------------------------------------------------------------------------------------------------- the fake policy
-def fake_policy_np(emu, size):
-    """bpp_amd.reorder.int_policy (make_reorder_golden.fake_policy) on host rows, its feasibility mask from the emulated
-    bpp_mask_from_obs: obs numpy [n, 4A] -> (value f32 [n], logits f32 [n, A], pred f32 [n, A]) as numpy."""
+# ---------------------------------------------------------------------------------------------------- the two tiers
+def fake_policy(size, emu=None):
+    """bpp_amd.reorder.int_policy (make_reorder_golden.fake_policy); emu: its feasibility mask from the emulated
+    bpp_mask_from_obs on host rows instead of the device's."""
     import torch
     from bpp_amd.reorder import int_policy
-    pol = int_policy(size, mask_fn=lambda obs: torch.from_numpy(emu.mask_from_obs(obs.numpy(), size, False)))
-
-    def policy(obs):
-        return tuple(np.ascontiguousarray(t.numpy()) for t in pol(torch.from_numpy(obs)))
-    return policy
+    if emu is None:
+        return int_policy(size)
+    return int_policy(size, mask_fn=lambda obs: torch.from_numpy(emu.mask_from_obs(obs.numpy(), size, False)))
 
 
-def fake_policy_torch(size):
-    from bpp_amd.reorder import int_policy
-    return int_policy(size)
+def make_env(emu, pool, size, E):
+    """E bins over `pool` after their first reset: an EmuVecEnv on the emulator, a BppVecEnv on the device for emu = None."""
+    if emu is not None:
+        return EmuVecEnv(emu, size, E, pool=np.ascontiguousarray(pool))
+    import torch
+    from bpp_amd import BppVecEnv
+    env = BppVecEnv(E, container_size=size, pool=np.ascontiguousarray(pool), device="cuda", compute_mask=True)
+    env.reset()
+    torch.cuda.synchronize()
+    return env
 
 
 def _records(g, k):
@@ -47,122 +52,52 @@ def _records(g, k):
     return [tuple(g["k%d_%s" % (k, f)][st[p]:st[p + 1]] for f in ("items", "act", "exp", "default")) for p in range(len(st) - 1)]
 
 
-# ---------------------------------------------------------------------------------------------------- CPU (emulator)
-def emu_reorder_lib(emu):
-    """The emulated library with the reorder entry points of the current source: tests/emu's own staleness check does not
-    know bpp_reorder.inl / bpp_reorder.h, so a library older than them (or without the symbols) is rebuilt and reloaded."""
-    from bpp_amd import _lib
-    L = emu.lib()
-    stale = any(os.path.getmtime(f) > os.path.getmtime(emu.LIB) for f in REORDER_SRC)
-    if stale or not all(hasattr(L, s) for s in _lib.REORDER_SYMBOLS):
-        import shutil
-        emu.build(force=True)
-        # dlopen hands back the library already loaded under the same name: load the new build under a name of its own
-        fresh = "%s.reorder.%d" % (emu.LIB, os.getpid())
-        shutil.copyfile(emu.LIB, fresh)
-        emu.LIB, emu._lib = fresh, None
-        L = emu.lib()
-        assert all(hasattr(L, s) for s in _lib.REORDER_SYMBOLS)
-    return L
-
-
-class EmuReorder(object):
-    """The schedule of ReorderSearch.decide over the emulated library: real bins [0, n), scratch bins [n, 2n)."""
-
-    def __init__(self, emu, pool, size, n, k, times=100, v_bound=0.1):
-        from bpp_amd import _lib
-        self.emu, self.size, self.n, self.k = emu, tuple(int(v) for v in size), n, k
-        L = emu_reorder_lib(emu)
-        self.L = _lib.bind_reorder(L, emu.Batch)
-        L.bpp_step_subset.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                      ctypes.POINTER(emu.StepOut), ctypes.c_void_p, ctypes.c_void_p]
-        L.bpp_copy_bins.argtypes = [ctypes.POINTER(emu.Batch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                    ctypes.c_void_p]
-        self.env = emu.OracleEnv(pool, self.size, False, 2 * n)
-        self.env.reset()
-        self.A = self.env.A
-        self.times = min(times, math.factorial(k - 1))
-        self.v_bound = v_bound
-        self.overflow = np.zeros(1, np.int32)
-        self.policy = fake_policy_np(emu, self.size)
-
-    def _step(self, ids, a):
-        n, env = ids.shape[0], self.env
-        r = dict(obs=np.zeros((n, 4 * self.A), np.float32), mask=np.zeros((n, self.A), np.float32), reward=np.zeros(n, np.float32),
-                 done=np.zeros(n, np.uint8), counter=np.zeros(n, np.int32), ratio=np.zeros(n), ep_ret=np.zeros(n),
-                 ep_len=np.zeros(n, np.int32))
-        out = self.emu.StepOut(*[_p(r[f]).value for f in ("obs", "mask", "reward", "done", "counter", "ratio", "ep_ret", "ep_len")])
-        a = np.ascontiguousarray(a, np.int64)
-        assert self.L.bpp_step_subset(ctypes.byref(env._b), _p(ids), n, _p(a), ctypes.byref(out), None, None) == 0
-        return r
-
-    def decide(self, ids, scratch=None):
-        ids = np.ascontiguousarray(ids, np.int64)
-        scratch = ids + self.n if scratch is None else np.ascontiguousarray(scratch, np.int64)
-        n, k, L, b = ids.shape[0], self.k, self.L, ctypes.byref(self.env._b)
-        sizes = (ctypes.c_int64 * 3)()
-        assert L.bpp_reorder_sizes(n, k, self.times, self.env.W, self.env.L, sizes) == 0
-        work = np.zeros(int(sizes[0]) + 16, np.uint8)
-        off = (-work.ctypes.data) % 16
-        work = work[off:off + int(sizes[0])]
-        r = self.emu_r = __import__("bpp_amd")._lib.Reorder(n, k, self.times, int(sizes[2]), self.v_bound, _p(ids).value,
-                                                             _p(scratch).value, _p(work).value, _p(self.overflow).value, 0)
-        rr = ctypes.byref(r)
-        obs, acts = np.zeros((n, 4 * self.A), np.float32), np.zeros(n, np.int64)
-        assert L.bpp_reorder_begin(b, rr, None) == 0
-        done = None
-        for it in range(-1, self.times):
-            assert L.bpp_copy_bins(b, None, _p(ids), _p(scratch), n, None) == 0
-            for level in range(k):
-                assert L.bpp_reorder_emit(b, rr, it, level, _p(done), _p(obs), None) == 0, L.bpp_last_error()
-                value, logits, pred = self.policy(obs)
-                assert L.bpp_reorder_choose(b, rr, _p(value), _p(logits), _p(pred), _p(acts), None) == 0
-                done = self._step(scratch, acts)["done"]
-        assert L.bpp_reorder_commit(b, rr, _p(done), None) == 0
-        act, val, dflt = np.zeros(n, np.int64), np.zeros(n), np.zeros(n, np.uint8)
-        assert L.bpp_reorder_finish(b, rr, _p(act), _p(val), _p(dflt), None) == 0
-        return act, val, dflt.astype(bool)
-
-    def preview(self, ids):
-        st = self.env.state[ids]
-        pool = self.env.pool
-        T = pool.shape[1]
-        return np.stack([pool[st["seq"][i], np.minimum(st["cursor"][i] + np.arange(self.k), T - 1), :3] for i in range(len(ids))]).astype(np.int32)
-
-
-def replay_emulated(emu, g, k, n):
-    """Play the first n trajectories of fixture g with the emulated search; compare every decision."""
+def replay(emu, g, k, n, reps=1):
+    """Play the first n trajectories of g, each replicated `reps` times, with ReorderSearch on make_env's env (real bins
+    [0, N), scratch [N, 2N), N = n * reps; bin b plays trajectory b mod n): items, action, default and max_exp (bit for
+    bit) of every decision, the episode's length and its final ratio.  Returns the list of (trajectory, replica) pairs
+    that diverge and the overflow counter."""
+    import torch
+    from bpp_amd import ReorderSearch
     size = tuple(int(v) for v in g["size"])
     recs = _records(g, k)[:n]
-    er = EmuReorder(emu, g["pool"][:n], size, n, k)
-    live = np.arange(n)
+    N = n * reps
+    env = make_env(emu, g["pool"][:n], size, 2 * N)
+    rs = ReorderSearch(env, k)
+    policy = fake_policy(size, emu)
+    dev = env.device
+    live = torch.arange(N, device=dev)
     t = 0
-    ratios = np.zeros(n)
-    while live.size:
-        act, val, dflt = er.decide(live)
-        items = er.preview(live)
-        for j, p in enumerate(live):
+    bad = set()
+    ratio = torch.zeros(N, dtype=torch.float64, device=dev)
+    while live.numel():
+        items = env.preview(k)[live].cpu().numpy()
+        act, val, dflt = rs.decide(policy, live, live + N)
+        a, v, d, lv = act.cpu().numpy(), val.cpu().numpy(), dflt.cpu().numpy(), live.cpu().numpy()
+        r = env.step_bins(live, act)
+        done = r.done.bool()
+        for j, (b, fin) in enumerate(zip(lv, done.cpu().numpy())):
+            p = b % n
             it, ra, re, rd = recs[p]
-            assert t < len(ra), "trajectory %d plays longer than the reference" % p
-            np.testing.assert_array_equal(items[j], it[t], err_msg="items traj %d decision %d" % (p, t))
-            assert (act[j], rd[t]) == (ra[t], dflt[j]), "traj %d decision %d: action %d / default %s, reference %d / %s" % (
-                p, t, act[j], dflt[j], ra[t], rd[t])
-            assert val[j].tobytes() == np.float64(re[t]).tobytes(), "traj %d decision %d: max_exp %r != %r" % (p, t, val[j], re[t])
-        r = er._step(live, act)
-        for j, p in enumerate(live):
-            if r["done"][j]:
-                assert t == len(recs[p][1]) - 1, "trajectory %d ends early" % p
-                ratios[p] = r["ratio"][j]
-        live = live[r["done"] == 0]
+            if t >= len(ra) or not (np.array_equal(items[j], it[t]) and a[j] == ra[t] and d[j] == rd[t]
+                                    and v[j].tobytes() == np.float64(re[t]).tobytes()) or (fin and t != len(ra) - 1):
+                bad.add((int(p), int(b // n)))
+        ratio[live[done]] = r.ratio[done]
+        live = live[~done]
         t += 1
-    np.testing.assert_array_equal(ratios, g["k%d_ratio" % k][:n])
-    assert er.overflow[0] == 0
+    want = np.tile(g["k%d_ratio" % k][:n], reps)
+    got = ratio.cpu().numpy()
+    bad |= {(int(b % n), int(b // n)) for b in np.flatnonzero(got != want)}
+    return sorted(bad), int(rs.overflow.item())
 
 
+# ---------------------------------------------------------------------------------------------------- CPU (emulator)
 @pytest.mark.parametrize("case,k", FAKE_RUNS)
 def test_emulated_reorder_matches_reference(emu, case, k):
     g = load_golden(case)
-    replay_emulated(emu, g, k, len(g["k%d_ratio" % k]))
+    bad, ovf = replay(emu, g, k, len(g["k%d_ratio" % k]))
+    assert not bad, "diverging trajectories: %r" % bad[:20]
+    assert ovf == 0
 
 
 @pytest.mark.parametrize("case", FAKE_CASES)
@@ -194,34 +129,38 @@ def terminator_previews(g):
 def test_emulated_invalid_ids_touch_nothing(emu):
     """A slot whose scratch (or real) bin lies outside [0, E) searches nothing and writes no bin: the other slots' decisions
     are those of a run without it, no bin other than the valid scratch bins changes, and finish reports BPP_ACTION_NOOP."""
+    import torch
+    from bpp_amd import ReorderSearch
     g = load_golden("reorder_fake_10")
-    n, k = 6, 3
-    a = EmuReorder(emu, g["pool"][:n], (10, 10, 10), n, k)
-    b = EmuReorder(emu, g["pool"][:n], (10, 10, 10), n, k)
-    ids = np.arange(n)
-    want = b.decide(ids)
-    real_h, real_s = a.env.hmap[:n].copy(), a.env.state[:n].copy()
+    n, k, size = 6, 3, (10, 10, 10)
+    policy = fake_policy(size, emu)
+    env_a, env_b = (make_env(emu, g["pool"][:n], size, 2 * n) for _ in range(2))
+    a, b = ReorderSearch(env_a, k), ReorderSearch(env_b, k)
+    ids = torch.arange(n)
+    want = [t.numpy() for t in b.decide(policy, ids, ids + n)]
+    hmap, state = env_a.oracle.hmap, env_a.oracle.state
+    real_h, real_s = hmap[:n].copy(), state[:n].copy()
     scratch = ids + n
     scratch[2] = 2 * n + 7                       # outside [0, E)
-    ids2 = ids.copy()
+    ids2 = ids.clone()
     ids2[4] = -3                                 # a real id outside [0, E) (its scratch bin stays valid)
-    hm_before, st_before = a.env.hmap.copy(), a.env.state.copy()
-    act, val, dflt = a.decide(ids2, scratch)
+    hm_before, st_before = hmap.copy(), state.copy()
+    act, val, dflt = (t.numpy() for t in a.decide(policy, ids2, scratch, check=False))
     for j in (0, 1, 3, 5):
         assert (act[j], val[j], dflt[j]) == (want[0][j], want[1][j], want[2][j]), j
     for j in (2, 4):
         assert (act[j], val[j], dflt[j]) == (NOOP, 0.0, False), j
-    np.testing.assert_array_equal(a.env.hmap[:n], real_h)
-    np.testing.assert_array_equal(a.env.state[:n].view(np.int32), real_s.view(np.int32))
+    np.testing.assert_array_equal(hmap[:n], real_h)
+    np.testing.assert_array_equal(state[:n].view(np.int32), real_s.view(np.int32))
     untouched = [n + 4]                          # the valid scratch bin of the slot whose real id is bad
-    np.testing.assert_array_equal(a.env.hmap[untouched], hm_before[untouched])
-    np.testing.assert_array_equal(a.env.state[untouched].view(np.int32), st_before[untouched].view(np.int32))
-    assert a.overflow[0] == 0
+    np.testing.assert_array_equal(hmap[untouched], hm_before[untouched])
+    np.testing.assert_array_equal(state[untouched].view(np.int32), st_before[untouched].view(np.int32))
+    assert int(a.overflow[0]) == 0
 
 
 def test_emulated_argument_checks(emu):
     from bpp_amd import _lib
-    L = _lib.bind_reorder(emu_reorder_lib(emu), emu.Batch)
+    L = bind(emu)
     sizes = (ctypes.c_int64 * 3)()
     for k in (0, 9):
         assert L.bpp_reorder_sizes(4, k, 100, 10, 10, sizes) != 0
@@ -291,57 +230,14 @@ def test_live_reference_rerecord():
 
 # ---------------------------------------------------------------------------------------------------- GPU
 def _gpu_env(pool, size, E):
-    import torch
-    from bpp_amd import BppVecEnv
-    env = BppVecEnv(E, container_size=size, pool=np.ascontiguousarray(pool), device="cuda", compute_mask=True)
-    env.reset()
-    torch.cuda.synchronize()
-    return env
-
-
-def replay_gpu(g, k, n, reps=1):
-    """Play the first n trajectories of g, each replicated `reps` times, with BppVecEnv + ReorderSearch (real bins [0, N),
-    scratch [N, 2N), N = n * reps; bin b plays trajectory b mod n).  Returns the list of (trajectory, replica) pairs
-    that diverge and the overflow counter."""
-    import torch
-    from bpp_amd import ReorderSearch
-    size = tuple(int(v) for v in g["size"])
-    recs = _records(g, k)[:n]
-    N = n * reps
-    env = _gpu_env(g["pool"][:n], size, 2 * N)
-    rs = ReorderSearch(env, k)
-    policy = fake_policy_torch(size)
-    dev = env.device
-    live = torch.arange(N, device=dev)
-    t = 0
-    bad = set()
-    ratio = torch.zeros(N, dtype=torch.float64, device=dev)
-    while live.numel():
-        items = env.preview(k)[live].cpu().numpy()
-        act, val, dflt = rs.decide(policy, live, live + N)
-        a, v, d, lv = act.cpu().numpy(), val.cpu().numpy(), dflt.cpu().numpy(), live.cpu().numpy()
-        for j, b in enumerate(lv):
-            p = b % n
-            it, ra, re, rd = recs[p]
-            if t >= len(ra) or not (np.array_equal(items[j], it[t]) and a[j] == ra[t] and d[j] == rd[t]
-                                    and v[j].tobytes() == np.float64(re[t]).tobytes()):
-                bad.add((int(p), int(b // n)))
-        r = env.step_bins(live, act)
-        done = r.done.bool()
-        ratio[live[done]] = r.ratio[done]
-        live = live[~done]
-        t += 1
-    want = np.tile(g["k%d_ratio" % k][:n], reps)
-    got = ratio.cpu().numpy()
-    bad |= {(int(b % n), int(b // n)) for b in np.flatnonzero(got != want)}
-    return sorted(bad), int(rs.overflow.item())
+    return make_env(None, pool, size, E)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case,k", FAKE_RUNS)
 def test_gpu_reorder_matches_reference(case, k):
     g = load_golden(case)
-    bad, ovf = replay_gpu(g, k, len(g["k%d_ratio" % k]))
+    bad, ovf = replay(None, g, k, len(g["k%d_ratio" % k]))
     assert not bad, "diverging trajectories: %r" % bad[:20]
     assert ovf == 0
 
@@ -351,7 +247,7 @@ def test_gpu_reorder_matches_reference(case, k):
 def test_gpu_reorder_replicated(k):
     """64 trajectories x 256 replicas: 16 384 slots, 32 768 bins; every replica equals the fixture."""
     g = load_golden("reorder_fake_10")
-    bad, ovf = replay_gpu(g, k, 64, reps=256)
+    bad, ovf = replay(None, g, k, 64, reps=256)
     assert not bad, "diverging (trajectory, replica) pairs: %r" % bad[:20]
     assert ovf == 0
 
@@ -367,7 +263,7 @@ def test_gpu_k1_is_masked_argmax():
     pool = cut2_pool(size, 4096, seed=11)
     env = _gpu_env(pool, size, 2 * N)
     rs = ReorderSearch(env, 1)
-    policy = fake_policy_torch(size)
+    policy = fake_policy(size)
     ids = torch.arange(N, device=env.device)
     for step in range(3):
         obs = env.observe_bins(ids).obs.clone()
@@ -394,7 +290,7 @@ def test_gpu_decide_does_not_synchronise():
     g = load_golden("reorder_fake_10")
     env = _gpu_env(g["pool"][:64], (10, 10, 10), 128)
     rs = ReorderSearch(env, 3)
-    policy = fake_policy_torch((10, 10, 10))
+    policy = fake_policy((10, 10, 10))
     ids = torch.arange(64, device=env.device)
     rs.decide(policy, ids, ids + 64)           # buffers are made on first use
     torch.cuda.synchronize()

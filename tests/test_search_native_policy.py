@@ -4,9 +4,8 @@ by forward (tests/search_native_cases.py): every forward inside a decision again
 tape replay on an identically built second env, which proves that the search kernels consumed exactly the outputs the forward
 wrote (and that the next emit did not overwrite an obs the forward had still to read).
 
-Emulated half (no marker): the product kernels on the host SIMT emulator, EmuReorder / EmuMcts / EmuMultiBin of the search
-tests with pc.host_runner on a packed blob as their policy, geometry (5, 32, 25), P + 1 slots so that one trunk workgroup is
-partial.  Side 5 with H = 32 is judged exactly only: the float32 torch yardstick is unstable on tiny networks (policy_cases).
+Emulated half (no marker): the product kernels on the host SIMT emulator, the three search classes on an EmuVecEnv with
+pc.host_runner on a packed blob as their policy, geometry (5, 32, 25), P + 1 slots so that one trunk workgroup is partial.  Side 5 with H = 32 is judged exactly only: the float32 torch yardstick is unstable on tiny networks (policy_cases).
 
 Device half (`-m gpu`): BppVecEnv and the three search classes with NativePolicy, geometry (10, 256, 100), T + 3 slots (odd against
 P = 2, a head tile of 3): the exact network (a), its tape replay (b), the live policy on a side stream, which is another workspace
@@ -25,11 +24,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import policy_cases as pc  # noqa: E402
 import search_native_cases as sn  # noqa: E402
 from conftest import load_golden  # noqa: E402
+from emu_env import torch_policy  # noqa: E402
 from test_gpu_policy_forward import _checkpoint  # noqa: E402
-from test_mcts_search import EmuMcts  # noqa: E402
-from test_multibin import EmuMultiBin  # noqa: E402
 from test_policy_forward import emu_lib  # noqa: E402,F401  (the module's fixture: the emulated library bound with bind_policy)
-from test_reorder_search import EmuReorder  # noqa: E402
+from test_reorder_search import make_env  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -79,51 +77,15 @@ def pool_of(name, size, rows, wide=None):
 # A game is one env with one search object; play(policy, rounds) runs the schedule of the examples -- decide, step the real bins,
 # advance / commit -- and returns the decision outputs per round, the real bins' heightmaps after the last step, and what the
 # conditions need.  Two games made with the same arguments are identical.
-class EmuGame(object):
+class Game(object):
+    """emu: the emulated library, or None for the device."""
+
     def __init__(self, emu, search, size, pool, n, **kw):
-        self.search, self.n, self.kw = search, n, kw
-        if search == "reorder":
-            self.s = EmuReorder(emu, pool_of(pool, size, n), size, n, kw["k"])
-        elif search == "mcts":
-            self.s = EmuMcts(emu, pool_of(pool, size, n), size, n, kw["k"], kw["sims"])
-            self.s.seed(np.arange(n), np.arange(n) + 5)
-        else:
-            self.s = EmuMultiBin(emu, pool_of(pool, size, n, wide=kw["w"]), size, kw["w"], kw["s"], n)
-            self.K = self.s.K
-
-    def play(self, policy, rounds):
-        s, ids = self.s, np.arange(self.n, dtype=np.int64)
-        out, info = [], dict(done=[], children=[], windows=[])
-        for _ in range(rounds):
-            if self.search == "reorder":
-                s.policy = policy
-                dec = s.decide(ids)
-                r = s._step(ids, dec[0])
-            elif self.search == "mcts":
-                s.policy = sn.two_heads(policy)
-                dec = s.decide(ids)
-                info["children"].append(np.array([c for _, _, c, _ in s.roots(ids)]))
-                r = s._step(ids, dec[0])
-                s.advance(r["done"])
-            else:
-                s.policy = policy
-                act, adv, win, r = s.decide_step(ids)
-                dec = (act, adv, win)
-                info["windows"].append(win.copy())
-            out.append(tuple(np.array(d) for d in dec))
-            info["done"].append(r["done"].astype(bool))
-        info["overflow"] = int(getattr(s, "overflow", np.zeros(1))[0])
-        return out, s.env.hmap[:self.n].copy(), info
-
-
-class GpuGame(object):
-    def __init__(self, search, size, pool, n, **kw):
         import bpp_amd
         self.search, self.n = search, n
         E = n if search == "multibin" else 2 * n
         wide = kw["w"] if search == "multibin" else None
-        self.env = bpp_amd.BppVecEnv(E, container_size=size, pool=pool_of(pool, size, n, wide), device=DEV, compute_mask=True)
-        self.env.reset()
+        self.env = make_env(emu, pool_of(pool, size, n, wide), size, E)
         self.ids = torch.arange(n, device=self.env.device)
         if search == "reorder":
             self.s = bpp_amd.ReorderSearch(self.env, kw["k"])
@@ -156,7 +118,8 @@ class GpuGame(object):
             out.append(dec)
             info["done"].append(res.done.reshape(-1).clone())
         final = env.heightmaps()[:n].clone()
-        torch.cuda.synchronize()
+        if env.device.type == "cuda":
+            torch.cuda.synchronize()
         info["done"] = [sn.to_numpy(d).astype(bool) for d in info["done"]]
         info["windows"] = [sn.to_numpy(w) for w in info["windows"]]
         info["overflow"] = int(s.overflow.item()) if getattr(s, "overflow", None) is not None else 0
@@ -203,7 +166,7 @@ def check_conditions(search, decisions, info, K=None):
 def emu_game(emu, emu_lib, search):
     size, pool, kw, rounds = EMU_SHAPES[search]
     n = pc.info(emu_lib, G5, 1)["bins_per_trunk_group"] + 1
-    return EmuGame(emu, search, size, pool, n, **kw), rounds
+    return Game(emu, search, size, pool, n, **kw), rounds
 
 
 @pytest.mark.parametrize("search", SEARCHES)
@@ -213,20 +176,20 @@ def test_emulated_search_under_the_exact_network(emu, emu_lib, search):
     i = pc.info(emu_lib, G5, 1)
     P, T = i["bins_per_trunk_group"], i["bins_per_head_tile"]
     net = sn.exact_net(G5)
-    policy = sn.host_policy(emu_lib, G5, net.blob)
+    policy = torch_policy(sn.host_policy(emu_lib, G5, net.blob))
     a, rounds = emu_game(emu, emu_lib, search)
     rec = sn.Recorder(policy)
     dec_a, hmap_a, info = a.play(rec, rounds)
     assert info["overflow"] == 0
     check_wide_rows(search, a, rec.calls)
-    rows = sn.judge_exact(net, rec.calls, P, T, all_rows=True)
+    rows = sn.judge_exact(net, sn.host_calls(rec.calls), P, T, all_rows=True)
     alone = sn.judge_alone(policy, rec.calls, P, T)
     b, _ = emu_game(emu, emu_lib, search)
     tape = sn.Tape(rec.calls)
     dec_b, hmap_b, _ = b.play(tape, rounds)
     assert not tape.mismatch()
     sn.same_decisions(dec_a, dec_b, search + " replay")
-    assert np.array_equal(hmap_a, hmap_b)
+    assert torch.equal(hmap_a, hmap_b)
     print("%s: %d calls, %d rows exact, %d alone, %.1f s" % (search, len(rec.calls), rows, alone, time.perf_counter() - t0))
 
 
@@ -238,7 +201,7 @@ def test_emulated_search_under_real_weights(emu, emu_lib, search):
     i = pc.info(emu_lib, G5, 1)
     P, T = i["bins_per_trunk_group"], i["bins_per_head_tile"]
     blob = pc.pol.pack_weights(pc.real_weights(*G5, REAL_SEED), *G5).numpy()
-    policy = sn.host_policy(emu_lib, G5, blob)
+    policy = torch_policy(sn.host_policy(emu_lib, G5, blob))
     a, rounds = emu_game(emu, emu_lib, search)
     rec = sn.Recorder(policy)
     dec_a, hmap_a, info = a.play(rec, rounds)
@@ -250,7 +213,7 @@ def test_emulated_search_under_real_weights(emu, emu_lib, search):
     dec_b, hmap_b, _ = b.play(tape, rounds)
     assert not tape.mismatch()
     sn.same_decisions(dec_a, dec_b, search + " replay")
-    assert np.array_equal(hmap_a, hmap_b)
+    assert torch.equal(hmap_a, hmap_b)
     print("%s: %d calls, %d alone, %.1f s" % (search, len(rec.calls), alone, time.perf_counter() - t0))
 
 
@@ -260,8 +223,8 @@ def test_conditions_hold_for_the_int64_forward_alone(emu, search):
     forward, no policy kernel involved.  What test (a) on the device then asserts of the kernels is a property of the reference."""
     size, pool, kw = DEV_SHAPES[search]
     net = sn.exact_net(G10)
-    game = EmuGame(emu, search, size, pool, 8, **kw)
-    decisions, _, info = game.play(net.policy_np(), ROUNDS)
+    game = Game(emu, search, size, pool, 8, **kw)
+    decisions, _, info = game.play(torch_policy(net.policy_np()), ROUNDS, stats=True)
     assert info["overflow"] == 0
     check_conditions(search, decisions, info, getattr(game, "K", None))
 
@@ -327,7 +290,7 @@ def tiles(bpp):
 def gpu_game(search, tiles):
     size, pool, kw = DEV_SHAPES[search]
     n = MULTIBIN_PALLETS if search == "multibin" else tiles[1] + 3
-    return GpuGame(search, size, pool, n, **kw)
+    return Game(None, search, size, pool, n, **kw)
 
 
 def native(bpp, plain):
