@@ -68,14 +68,17 @@ def main():
     ap.add_argument("--stream", action="store_true",
                     help="endless item supply generated on the device (every bin its own random.Random, nothing replayed) "
                          "instead of a pool of 4096 sequences")
+    ap.add_argument("--item-seq", choices=("cut2", "cut1", "rs"), default="cut2",
+                    help="with --stream: the item generator of the supply (the reference's --item-seq; cut1 and rs on the counter generator)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     size = (10, 10, 10)
     if args.graph and args.stream:
         raise SystemExit("--graph replays ONE captured lock-step; the stream supply's refills are scheduled by host code between lock-steps")
     if args.stream:
+        spec = dict(bound=(2, 5)) if args.item_seq == "cut2" else dict(kind=args.item_seq)
         envs = bpp_amd.BppVecEnv(args.envs, size, enable_rotation=args.rotation, device=dev,
-                                 stream=dict(bound=(2, 5), seed=0, depth=16, refill_every=8))
+                                 stream=dict(spec, seed=0, depth=16, refill_every=8))
     else:
         pool = bpp_amd.sequences.cut2_pool(size, 4096, seed=0)
         envs = bpp_amd.BppVecEnv(args.envs, size, enable_rotation=args.rotation, pool=pool, device=dev)

@@ -25,6 +25,7 @@ ROLLOUT_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_rollout.h")
 UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
 KFAC_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_kfac.h")
 POLICY_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy.h")
+STREAM_KINDS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_stream_kinds.h")
 # everything a rebuild depends on, by glob: a new .inl or header counts from the moment it exists
 DEPS = sorted(f for d, pats in ((CSRC, ("*.hip", "*.inl")), (os.path.dirname(HDR), ("*.h", "*.inl")))
               for pat in pats for f in glob.glob(os.path.join(d, pat)))
@@ -68,6 +69,11 @@ KFAC_INFO = ("D", "R", "tile", "rows_per_split", "splits", "chain")
 # include/bpp_policy.h: the same, for the CNNPro policy forward
 POLICY_SYMBOLS = ["bpp_policy_forward", "bpp_policy_forward_workspace", "bpp_policy_weights_floats", "bpp_policy_forward_info"]
 POLICY_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "bins_per_head_tile", "head_groups", "tile", "padded_rows", "path")
+# include/bpp_stream_kinds.h: the same, for the CUT-1 and RS ring refills
+STREAM_KIND_SYMBOLS = ["bpp_stream_refill_cut1", "bpp_stream_refill_rs", "bpp_stream_kinds_info", "bpp_rollout_uniform_stream_kind"]
+STREAM_KINDS = {"cut1": 1, "rs": 2}                  # BPP_STREAM_KIND_*
+CUT1_MAX_PIECES, RS_MAX_SET = 128, 4096
+STREAM_KINDS_INFO = ("lanes", "lds_bytes", "pieces", "threads")
 
 
 class Batch(ctypes.Structure):
@@ -266,6 +272,34 @@ def bind_policy(L):
     return L
 
 
+def bind_stream_kinds(L, batch=None, step_out=None, stream=None):
+    """Argument types of the STREAM_KIND_SYMBOLS on library handle L (`batch`, `step_out`, `stream`: the ctypes classes of struct
+    bpp_batch, bpp_step_out and bpp_stream)."""
+    vp, i32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64
+    S, rg = ctypes.POINTER(stream or Stream), ctypes.POINTER(i32)
+    L.bpp_stream_refill_cut1.argtypes = [S, rg, i32, vp]
+    L.bpp_stream_refill_rs.argtypes = [S, vp, i32, vp]
+    L.bpp_stream_kinds_info.argtypes = [S, i32, rg, rg]
+    L.bpp_rollout_uniform_stream_kind.argtypes = [ctypes.POINTER(batch or Batch), ctypes.POINTER(step_out or StepOut), vp, u64, u64, i32, S, i32,
+                                                  i32, rg, i32, vp, i32, vp]
+    for name in STREAM_KIND_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
+def box_range_arg(box_range):
+    """The box_range[6] argument of the STREAM_KIND_SYMBOLS."""
+    return (ctypes.c_int32 * 6)(*[int(v) for v in box_range])
+
+
+def stream_kinds_info(stream, kind, box_range=None, L=None):
+    """bpp_stream_kinds_info: the form a refill of `kind` ("cut1" / "rs") takes for struct bpp_stream `stream`, as a dict."""
+    out = (ctypes.c_int32 * 4)()
+    check((L or lib()).bpp_stream_kinds_info(ctypes.byref(stream), STREAM_KINDS[kind], box_range_arg(box_range) if box_range is not None else None,
+                                             out), L)
+    return dict(zip(STREAM_KINDS_INFO, (int(v) for v in out)))
+
+
 def kfac_geom(values):
     """A geom[] argument of the KFAC_SYMBOLS."""
     return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
@@ -371,6 +405,7 @@ def lib():
         bind_update(L)
         bind_kfac(L)
         bind_policy(L)
+        bind_stream_kinds(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

@@ -43,6 +43,7 @@
 #include "../../include/bpp_update.h"
 #include "../../include/bpp_kfac.h"
 #include "../../include/bpp_policy.h"
+#include "../../include/bpp_stream_kinds.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1628,6 +1629,7 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 }  // extern "C"
 
 #include "bpp_drivers.inl"
+#include "bpp_stream_kinds.inl"
 #include "bpp_search_common.inl"
 #include "bpp_reorder.inl"
 #include "bpp_multibin.inl"

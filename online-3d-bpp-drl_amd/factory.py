@@ -2,7 +2,9 @@
 
     envs = make_vec_envs(env_name, seed, num_processes, gamma, log_dir, device, allow_early_resets, args=args)
 
-Pass `stream=dict(bound=(lo, hi), seed=s, depth=D)` instead of a pool for the endless device-generated CUT-2 supply.
+Pass `stream=dict(bound=(lo, hi), seed=s, depth=D)` instead of a pool for the endless device-generated CUT-2 supply,
+`stream=dict(kind="cut1", box_range=...)` or `stream=dict(kind="rs", box_set=...)` for the other two generators: the dict is handed
+to BppVecEnv as it is, so the kind is what the dict says (`args.data_type` only chooses the pool when there is no stream).
 `args` is the reference's argparse namespace (acktr/arguments.py): `container_size`, `enable_rotation`,
 `data_type` ('cut1' | 'cut2' | 'rs', bin3D.py:21-32) and `box_size_set` are honoured; `gamma`,
 `allow_early_resets`, `num_frame_stack` are accepted for signature compatibility (the reference disables

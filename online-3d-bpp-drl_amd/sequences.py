@@ -333,3 +333,55 @@ def _pool_native(kind, container_size, n, seed, T, threads, box_range=None, rota
     if T is None:
         pool = np.ascontiguousarray(pool[:, :int(lengths.max()) + 1])
     return pool
+
+
+# ---- the endless device-generated supply of CUT-1 and RS (include/bpp_stream_kinds.h): normative statements ------------------
+class _CounterCoin(object):
+    """The rotation coin of a CUT-1 stream: rand() = 0.5 * R.below(2), drawn from the sequence's own CounterRandom at the
+    place the reference draws np.random.rand() -- the x / y swap happens exactly when the draw is 1."""
+
+    def __init__(self, rng):
+        self.rng = rng
+
+    def rand(self):
+        return 0.5 * self.rng.below(2)
+
+
+def cut1_stream_sequence(container_size, box_range, seed0, sid, episode, rotation=False):
+    """Episode `episode` of stream id `sid` (initially the bin's global id) of a CUT-1 stream under `seed0`: what
+    bpp_stream_refill_cut1 writes into the ring, item for item.  Every choice / randint is one CounterRandom.below (also
+    choice over a single axis), the coin one more when `rotation` is on."""
+    rng = CounterRandom(int(seed0), int(sid), int(episode))
+    return cut1_sequence(container_size, box_range, rng, rotation, _CounterCoin(rng))
+
+
+def rs_stream_sequence(container_size, box_set, seed0, sid, episode, length):
+    """The first `length` items of episode `episode` of stream id `sid` of an RS stream under `seed0` (a ring row holds
+    pool_len - 3 of them, then the terminator): item j = box_set[R.below(len(box_set))]."""
+    rng = CounterRandom(int(seed0), int(sid), int(episode))
+    if box_set is None:
+        box_set = DEFAULT_BOX_SET
+    return [tuple(int(v) for v in box_set[rng.below(len(box_set))]) for _ in range(int(length))]
+
+
+def rs_stream_pool_len(container_size, box_set=None):
+    """Shortest ring row (pool_len) of an RS stream: a bin is full before W*L*H / (smallest box volume) items are in it, so
+    the terminator that ends the row stands in for the reference's endless draw."""
+    W, L, H = (int(v) for v in container_size)
+    vmin = min(int(b[0]) * int(b[1]) * int(b[2]) for b in (box_set if box_set is not None else DEFAULT_BOX_SET))
+    return W * L * H // max(1, vmin) + 3
+
+
+def check_box_set(container_size, box_set):
+    """uint8 [n][4] = (x, y, z, 0) of an RS stream's box set; ValueError for an empty or oversized set, a zero side or a box
+    that fits the bin in neither orientation."""
+    W, L, H = (int(v) for v in container_size)
+    bs = np.asarray(box_set if box_set is not None else DEFAULT_BOX_SET, dtype=np.int64).reshape(-1, 3)
+    if not 1 <= bs.shape[0] <= 4096:
+        raise ValueError("box_set needs 1 .. 4096 boxes, got %d" % bs.shape[0])
+    for x, y, z in bs:
+        if min(x, y, z) < 1 or z > H or not ((x <= W and y <= L) or (x <= L and y <= W)):
+            raise ValueError("box_set: box %r does not fit the bin %r" % ((int(x), int(y), int(z)), (W, L, H)))
+    out = np.zeros((bs.shape[0], 4), np.uint8)
+    out[:, :3] = bs
+    return out

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .branch import BranchOps
-from .sequences import check_pool
+from .sequences import check_box_set, check_pool, rs_stream_pool_len
 from .spaces import Box, Discrete
 
 
@@ -329,6 +329,11 @@ class BppVecEnv(BranchOps):
                     overrides --, R = 5 for every other geometry); `rollout_uniform` runs the refills beside the
                     lock-steps when D >= 2 R + 3 (+ 4 with the cache; e.g. D = 32, R = 14).  Costs 6.6 KB of
                     generator state per bin (16 bytes with rng="counter") plus D rows of W*L*H / lo^3 + 3 entries.
+                    kind="cut1", box_range=(low_x, low_y, low_z, high_x, high_y, high_z) / kind="rs", box_set=[(x, y, z), ...]
+                    (default sequences.DEFAULT_BOX_SET): the reference's other two generators as endless supplies
+                    (include/bpp_stream_kinds.h; episode k of a bin = sequences.cut1_stream_sequence / rs_stream_sequence for
+                    (seed, global bin id, k)); counter generator only (rng defaults to "counter", "mt19937" is refused),
+                    `bound` is not used; CUT-1 follows enable_rotation; refills run between the lock-steps.  No `kind`: CUT-2.
     """
 
     def __init__(self, num_envs, container_size=(10, 10, 10), enable_rotation=False, pool=None, device="cuda",
@@ -372,8 +377,36 @@ class BppVecEnv(BranchOps):
                 self.pool = torch.from_numpy(self.pool_host).to(dev)
                 pool_rows, pool_len, pool_mode = self.pool_host.shape[0], self.pool_host.shape[1], _lib.POOL_STATIC
             else:
-                lo, hi = (int(v) for v in stream.get("bound", (2, 5)))
+                kind = stream.get("kind", "cut2")
+                if kind not in ("cut2", "cut1", "rs"):
+                    raise ValueError("stream kind must be 'cut2', 'cut1' or 'rs', got %r" % (kind,))
                 depth = int(stream.get("depth", 8))
+                kind_spec = {}
+                if kind == "cut2":
+                    lo, hi = (int(v) for v in stream.get("bound", (2, 5)))
+                    rng_name = stream.get("rng", "mt19937")
+                    default_len = self.W * self.L * self.H // lo ** 3 + 3
+                else:       # include/bpp_stream_kinds.h: counter generator only; `bound` merely sizes the scratch of the scan
+                    rng_name = stream.get("rng", "counter")
+                    if rng_name != "counter":
+                        raise ValueError("stream kind %r is generated by the counter generator only (rng='counter'), got rng=%r" % (kind, rng_name))
+                    lo = max(1, min(self.bin_size) // 2)
+                    hi = 2 * lo - 1
+                    if kind == "cut1":
+                        box_range = tuple(int(v) for v in stream.get("box_range", (2, 2, 2, 5, 5, 5)))
+                        if len(box_range) != 6 or min(box_range[:3]) < 1 or any(box_range[k] > box_range[3 + k] for k in range(3)):
+                            raise ValueError("box_range must be (low_x, low_y, low_z, high_x, high_y, high_z) with 1 <= low <= high, got %r"
+                                             % (box_range,))
+                        default_len = self.W * self.L * self.H // (box_range[0] * box_range[1] * box_range[2]) + 3
+                        kind_spec = dict(box_range=box_range)
+                    else:
+                        box_set = check_box_set(self.bin_size, stream.get("box_set"))
+                        default_len = rs_stream_pool_len(self.bin_size, box_set[:, :3])
+                        if int(stream.get("pool_len", default_len)) < default_len:
+                            raise ValueError("an RS stream needs pool_len >= %d (W*L*H / smallest box volume + 3): a bin must be full "
+                                             "before its row ends" % default_len)
+                        kind_spec = dict(box_set=tuple(tuple(int(v) for v in b[:3]) for b in box_set))
+                        self._box_set = torch.from_numpy(box_set).to(dev)
                 # bpp_batch.seq_cache: the row cache (include/bpp_abi.h) -- no step workgroup waits for a read of the ring;
                 # its lines refer to the row after next, which costs one row of look-ahead.  Default: wherever the refill
                 # schedule leaves that row
@@ -381,21 +414,26 @@ class BppVecEnv(BranchOps):
                     cache = bool(stream["cache"])
                 else:       # only the tile step kernel keeps the cache: any other geometry would pay a row of look-ahead for nothing
                     cache = depth >= 5 and depth - int(stream.get("refill_every", 1)) >= 4 and \
-                        int(stream.get("pool_len", self.W * self.L * self.H // lo ** 3 + 3)) < 8192 and \
+                        int(stream.get("pool_len", default_len)) < 8192 and \
                         _lib.launch_info(self.E, self.bin_size, self.can_rotate)["kernel"] == 2      # BPP_KERNEL_TILE
                 behind = 4 if cache else 3
                 if depth < behind + 1:
                     raise ValueError("stream depth must be >= %d" % (behind + 1))
                 # entries per ring row: two look-ahead entries (include/bpp_abi.h), the longest possible sequence, the terminator
-                pool_len = int(stream.get("pool_len", self.W * self.L * self.H // lo ** 3 + 3))
+                pool_len = int(stream.get("pool_len", default_len))
                 self.refill_every = int(stream.get("refill_every", depth - behind))
                 if not 1 <= self.refill_every <= depth - behind:
                     raise ValueError("refill_every must be in 1 .. depth - %d" % behind)
                 self.pool = torch.zeros((depth * self.E, pool_len, 4), dtype=torch.uint8, device=dev)   # the ring
                 sizes = (ctypes.c_int64 * 2)()      # the two opaque buffers of a bpp_stream: generator records, scratch
-                rng = {"mt19937": _lib.STREAM_RNG_MT19937, "counter": _lib.STREAM_RNG_COUNTER}[stream.get("rng", "mt19937")]
+                rng = {"mt19937": _lib.STREAM_RNG_MT19937, "counter": _lib.STREAM_RNG_COUNTER}[rng_name]
                 probe = _lib.Stream(self.E, depth, pool_len, self.W, self.L, self.H, lo, hi, 0, 0, None, None, None, None, None, None, rng, 0)
                 _lib.check(self.lib.bpp_stream_sizes(ctypes.byref(probe), sizes))
+                if kind == "cut1":      # the caps of the CUT-1 kernel and the ranges the reference's cutter fails on
+                    try:
+                        _lib.stream_kinds_info(probe, kind, box_range)
+                    except RuntimeError as exc:
+                        raise ValueError(str(exc))
                 self._mt = torch.zeros((self.E, int(sizes[0]) // self.E), dtype=torch.int32, device=dev)
                 self._work = torch.zeros(((int(sizes[1]) + 15) // 16, 4), dtype=torch.int32, device=dev)
                 self.gen_next = torch.zeros((self.E,), dtype=torch.int32, device=dev)
@@ -403,7 +441,9 @@ class BppVecEnv(BranchOps):
                 self._seq_cache = torch.zeros((self.E * _lib.SEQ_CACHE_BYTES_PER_BIN,), dtype=torch.uint8, device=dev) if cache else None
                 pool_rows, pool_mode = depth * self.E, _lib.POOL_RING
                 self.stream_spec = dict(bound=(lo, hi), seed=int(stream.get("seed", 0)), depth=depth, pool_len=pool_len,
-                                        refill_every=self.refill_every, rng=stream.get("rng", "mt19937"), cache=cache)
+                                        refill_every=self.refill_every, rng=rng_name, cache=cache)
+                if kind != "cut2":      # (a spec without `kind` is CUT-2, as before the other kinds existed)
+                    self.stream_spec.update(kind=kind, **kind_spec)
             self.hmap = torch.zeros((self.E, self.A), dtype=torch.uint8, device=dev)  # Space.plain as bytes
             self.state = torch.zeros((self.E, 12), dtype=torch.int32, device=dev)  # bpp_env_state[E], 48 B each
             # episode statistics kept inside the step kernel, one row per bin: [return sum, final-ratio sum, length
@@ -424,6 +464,7 @@ class BppVecEnv(BranchOps):
                                        self._work.data_ptr(), self.gen_next.data_ptr(), self.state.data_ptr(),
                                        self.stream_overflow.data_ptr(),
                                        {"mt19937": _lib.STREAM_RNG_MT19937, "counter": _lib.STREAM_RNG_COUNTER}[sp["rng"]], 0)
+            self._box_range = _lib.box_range_arg(sp["box_range"]) if sp.get("kind") == "cut1" else None
             with torch.cuda.device(dev):
                 _lib.check(self.lib.bpp_stream_init(ctypes.byref(self._stream), self._stream_ptr()))
             self.refill()
@@ -623,7 +664,14 @@ class BppVecEnv(BranchOps):
         if self._stream is None:
             raise RuntimeError("refill() needs a streaming env (stream=dict(...))")
         self._on_device()
-        _lib.check(self.lib.bpp_stream_refill(ctypes.byref(self._stream), self._stream_ptr()))
+        kind = self.stream_spec.get("kind", "cut2")
+        if kind == "cut1":
+            rc = self.lib.bpp_stream_refill_cut1(ctypes.byref(self._stream), self._box_range, int(self.can_rotate), self._stream_ptr())
+        elif kind == "rs":
+            rc = self.lib.bpp_stream_refill_rs(ctypes.byref(self._stream), self._box_set.data_ptr(), int(self._box_set.shape[0]), self._stream_ptr())
+        else:
+            rc = self.lib.bpp_stream_refill(ctypes.byref(self._stream), self._stream_ptr())
+        _lib.check(rc)
         self._since_refill = 0
 
     def _reset_seq_cache(self):
@@ -746,6 +794,15 @@ class BppVecEnv(BranchOps):
             actions = torch.empty((self.E,), dtype=torch.int64, device=self.device)
         self._on_device()
         self._serial += int(nsteps)
+        if self._stream is not None and self.stream_spec.get("kind", "cut2") != "cut2":
+            self.refill()
+            rs = self.stream_spec["kind"] == "rs"
+            _lib.check(self.lib.bpp_rollout_uniform_stream_kind(
+                self._batch_ref, ctypes.byref(self._plain(self._out)), actions.data_ptr(), int(seed), int(step0), int(nsteps),
+                ctypes.byref(self._stream), self.refill_every, _lib.STREAM_KINDS[self.stream_spec["kind"]], self._box_range, int(self.can_rotate),
+                self._box_set.data_ptr() if rs else None, int(self._box_set.shape[0]) if rs else 0, self._stream_ptr()))
+            self._since_refill = 0
+            return self._res
         if self._stream is not None:
             self.refill()
             if self._side is None:      # the overlapped schedule's side stream + events: this env's own (bpp_side_create), released in close()
@@ -1034,8 +1091,12 @@ class BppVecEnv(BranchOps):
     def _stream_identity(self):
         """What must agree for a streaming checkpoint to continue the same item streams."""
         sp = self.stream_spec
-        return dict(bound=tuple(sp["bound"]), seed=sp["seed"], depth=sp["depth"], pool_len=sp["pool_len"],
-                    num_envs=self.E, env_id_base=self.env_id_base, bin_size=self.bin_size, rng=sp["rng"])
+        ident = dict(bound=tuple(sp["bound"]), seed=sp["seed"], depth=sp["depth"], pool_len=sp["pool_len"],
+                     num_envs=self.E, env_id_base=self.env_id_base, bin_size=self.bin_size, rng=sp["rng"])
+        if sp.get("kind", "cut2") != "cut2":     # the kind and what defines its sequences; a checkpoint without `kind` is CUT-2
+            ident.update(kind=sp["kind"], rotation=self.can_rotate)
+            ident.update({k: sp[k] for k in ("box_range", "box_set") if k in sp})
+        return ident
 
     def load_state_dict(self, sd):
         if self._stream is None and "stream_ring" in sd:
