@@ -98,7 +98,12 @@ def main():
     put("cut1_10_rot", cut1((10, 10, 10), (2, 2, 2, 5, 5, 5), True, 77, 12), [10, 10, 10, 2, 2, 2, 5, 5, 5, 1, 77])
     put("cut1_20", cut1((20, 20, 20), (2, 2, 2, 5, 5, 5), False, 5, 2), [20, 20, 20, 2, 2, 2, 5, 5, 5, 0, 5])
     put("cut1_8x12x9_rot", cut1((8, 12, 9), (1, 2, 1, 4, 6, 3), True, 31, 6), [8, 12, 9, 1, 2, 1, 4, 6, 3, 1, 31])
-    default = None                                                  # RandomBoxCreator.default_box_set: {2..6}^3
+    # ranges the device CUT-1 generator is tested at (tests/stream_kind_cases.py): unit pieces, a high above any side with an
+    # axis that is never cut, three different axes
+    put("cut1_4x4x8_unit_rot", cut1((4, 4, 8), (1, 1, 1, 1, 1, 1), True, 77, 4), [4, 4, 8, 1, 1, 1, 1, 1, 1, 1, 77])
+    put("cut1_16x6x8_high300_rot", cut1((16, 6, 8), (4, 1, 2, 300, 2, 4), True, 77, 6), [16, 6, 8, 4, 1, 2, 300, 2, 4, 1, 77])
+    put("cut1_10_axes_differ", cut1((10, 10, 10), (2, 2, 3, 4, 5, 7), False, 77, 6), [10, 10, 10, 2, 2, 3, 4, 5, 7, 0, 77])
+    default = None                                                 # RandomBoxCreator.default_box_set: {2..6}^3
     put("rs_default", rs(default, 11, 6, 64), [0, 11])
     arg_set = [(i, j, k) for i in range(2, 6) for j in range(2, 6) for k in range(2, 6)]   # acktr/arguments.py:122-128
     put("rs_args", rs(arg_set, 3, 6, 64), [1, 3])

@@ -1,6 +1,8 @@
 """The CUT-1 and RS stream kinds on the device (include/bpp_stream_kinds.h; BppVecEnv(stream=dict(kind=...))): the refill
-kernels against the Python statements lock-step by lock-step (tests/stream_kind_cases.py), the rollout driver against the
-same lock-steps taken one by one, HIP-stream independence, clones, checkpoints and the refusals of the stream spec."""
+kernels against the Python statements lock-step by lock-step (tests/stream_kind_cases.py) and whole ring by whole ring -- at
+every box range and box set of that module, with rows too short and boxes that do not fit (overflow above zero), and on rings
+whose rows need a second round of the refill kernels' grid-stride loop --, the rollout driver against the same lock-steps taken
+one by one, HIP-stream independence, clones, checkpoints and the refusals of the stream spec."""
 import numpy as np
 import pytest
 
@@ -27,8 +29,23 @@ class GpuKindEnv(object):
         return out
 
     def episodes(self):
-        assert int(self.env.stream_overflow.item()) == 0
+        assert int(self.env.stream_overflow.item()) == 0 or self.short_rows
         return self.env.state_numpy()["episode"].copy()
+
+    short_rows = False                                  # rows shorter than the longest sequence: overflow is expected
+
+    def refill(self):
+        self.env.refill()
+
+    def overflow(self):
+        return int(self.env.stream_overflow.item())
+
+    def check_ring(self, kind, size, rot, seed, base, depth, box_range=cases.RANGE, box_set=None):
+        """The whole ring against the statement (one device-to-host copy); returns gen_next."""
+        gen_next = self.env.gen_next.cpu().numpy()
+        cases.ring_check(self.env.pool.cpu().numpy(), gen_next, self.env.state_numpy()["episode"], kind, size, rot, seed, base, depth,
+                         box_range, box_set)
+        return gen_next
 
 
 @pytest.mark.parametrize("kind", ["cut1", "rs"])
@@ -43,6 +60,86 @@ def test_gpu_rows_equal_the_statement(oracle, kind, size, rot, E, depth, refill,
     env = GpuKindEnv(kind, size, rot, E, base, seed, depth, refill, cache)
     episodes = cases.lock_step_check(oracle, env, kind, size, rot, E, base, seed, 64)
     assert int(env.env.gen_next.min().item()) > depth and int(episodes.max()) >= 4
+
+
+def kind_spec(kind, box_range, box_set):
+    return dict(box_range=box_range) if kind == "cut1" else dict(box_set=list(box_set)) if box_set is not None else {}
+
+
+@pytest.mark.parametrize("case", cases.KIND_CASES, ids=cases.case_id)
+def test_gpu_ring_rows_equal_the_statement(oracle, case):
+    """Every entry of every ring row against the statement, at every box range and box set of tests/stream_kind_cases.py: after
+    the first refill, and again with the bins at different episodes.  420 rows: seven workgroups and a tail at 64 lanes."""
+    kind, size, rot, box_range, box_set = case
+    E, base, seed, depth = 70, 40, 11, 6
+    env = GpuKindEnv(kind, size, rot, E, base, seed, depth, 2, False, **kind_spec(kind, box_range, box_set))
+    env.check_ring(kind, size, rot, seed, base, depth, box_range, box_set)
+    cases.race_bins(oracle, env, E)
+    env.refill()
+    gen_next = env.check_ring(kind, size, rot, seed, base, depth, box_range, box_set)
+    assert len(set(gen_next.tolist())) > 2 and env.overflow() == 0
+
+
+def test_gpu_short_cut1_rows_are_cut_and_counted(oracle):
+    """tests/test_stream_kinds.py::test_emulated_short_cut1_rows_are_cut_and_counted on the device."""
+    E, base, seed, depth, T = 20, 40, 11, 6, 36
+    first = cases.expected_overflow("cut1", SIZE, False, seed, base, E, [depth] * E, pool_len_=T)
+    assert 0 < first < E * depth and first == 11
+    env = GpuKindEnv("cut1", SIZE, False, E, base, seed, depth, 2, False, pool_len=T)
+    assert env.env.pool.shape[1] == T
+    env.check_ring("cut1", SIZE, False, seed, base, depth)
+    assert env.overflow() == first
+    cases.race_bins(oracle, env, E)
+    env.refill()
+    gen_next = env.check_ring("cut1", SIZE, False, seed, base, depth)
+    assert len(set(gen_next.tolist())) > 2
+    assert env.overflow() == cases.expected_overflow("cut1", SIZE, False, seed, base, E, gen_next, pool_len_=T) > first
+    # Uniform play puts 18 items at most into these bins: it reaches the terminator of a cut row only where rows are shorter.
+    for T, deepest in ((T, None), (12, 9)):
+        env, played = GpuKindEnv("cut1", SIZE, False, E, base, seed, depth, 2, False, pool_len=T), []
+        env.short_rows = True
+        cases.lock_step_check(oracle, env, "cut1", SIZE, False, E, base, seed, 64, fail=0, pool_len_=T, played=played)
+        assert deepest is None or max(int(o["counter"].max()) for o in played) == deepest
+    gen_next = env.env.gen_next.cpu().numpy()           # at 9 items a row every sequence is cut
+    assert env.overflow() == cases.expected_overflow("cut1", SIZE, False, seed, base, E, gen_next, pool_len_=12) == int(gen_next.sum())
+
+
+def test_gpu_bad_rs_boxes_are_played_as_the_terminator_and_counted_per_sequence():
+    """BppVecEnv refuses a set with such boxes, so the refill is called on an env's bpp_stream with a device set of its own:
+    every bad draw is the terminator in the ring, every other entry the statement's, and a row counts once."""
+    import ctypes
+    import torch
+    E, base, seed, depth = 70, 40, 11, 6
+    bad = cases.bad_box_set(SIZE)
+    rows = [cases.ring_items("rs", SIZE, False, seed, base + e, k, box_set=bad, T=128) for e in range(E) for k in range(depth)]
+    n_bad = [sum(it == SIZE for it in items) for items, over in rows]
+    assert 0 < sum(n > 0 for n in n_bad) < len(rows) and max(n_bad) > 1
+    env = GpuKindEnv("rs", SIZE, False, E, base, seed, depth, 2, False)
+    assert env.env.pool.shape[1] == 128 and env.overflow() == 0
+    env.env.gen_next.zero_()                            # every row is written again
+    dev_set = torch.from_numpy(cases.box_set_array(bad)).to(env.env.device)
+    assert env.env.lib.bpp_stream_refill_rs(ctypes.byref(env.env._stream), dev_set.data_ptr(), int(dev_set.shape[0]), env.env._stream_ptr()) == 0
+    env.check_ring("rs", SIZE, False, seed, base, depth, box_set=bad)
+    assert env.overflow() == sum(n > 0 for n in n_bad)
+
+
+@pytest.mark.parametrize("kind,size,E", [("rs", SIZE, 65536), ("cut1", SIZE, 65536), ("cut1", (18, 8, 7), 32768)])
+def test_gpu_second_round_of_the_grid_stride_loop(kind, size, E):
+    """The smallest rings with more rows than 8 192 workgroups serve in one round (64 lanes at work per workgroup, 32 at
+    18 x 8 x 7): after one refill every bin has its `depth` rows, nothing overflowed, and all rows of six bins across the
+    ring -- look-ahead entries included -- are the statement's."""
+    import torch
+    import bpp_amd
+    from bpp_amd import _lib
+    base, seed, depth = 40, 11, 9
+    env = bpp_amd.BppVecEnv(E, size, env_id_base=base, stream=dict(kind=kind, seed=seed, depth=depth, refill_every=2, cache=False))
+    lanes = _lib.stream_kinds_info(env._stream, kind, cases.RANGE)["lanes"]
+    assert lanes == (32 if size == (18, 8, 7) else 64) and 8192 * lanes < E * depth < 2 * 8192 * lanes
+    gen_next = env.gen_next.cpu().numpy()
+    assert (gen_next == depth).all() and int(env.stream_overflow.item()) == 0
+    bins = [0, 1, 4095, E // 2, E - 2, E - 1]
+    rows = env.pool[torch.from_numpy(cases.ring_rows(E, depth, bins)).to(env.pool.device)].cpu().numpy()
+    cases.ring_check(rows, gen_next, np.zeros(E, np.int64), kind, size, False, seed, base, depth, bins=bins)
 
 
 @pytest.mark.parametrize("kind", ["cut1", "rs"])

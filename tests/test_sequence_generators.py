@@ -41,7 +41,8 @@ def test_cut2_generators_equal_the_reference_creator(ref, name, native):
         assert got[k][:len(w)] == w and all(it == (W, L, H) for it in got[k][len(w):]), (name, k)
 
 
-@pytest.mark.parametrize("name", ["cut1_10", "cut1_10_rot", "cut1_20", "cut1_8x12x9_rot"])
+@pytest.mark.parametrize("name", ["cut1_10", "cut1_10_rot", "cut1_20", "cut1_8x12x9_rot", "cut1_4x4x8_unit_rot", "cut1_16x6x8_high300_rot",
+                                  "cut1_10_axes_differ"])
 @pytest.mark.parametrize("native", [True, False])
 def test_cut1_generators_equal_the_reference_creator(ref, name, native):
     m = [int(v) for v in ref[name + "_meta"]]

@@ -29,11 +29,22 @@ def test_cut2_generator_is_rng_exact(size, n):
             assert tuple(int(v) for v in native[len(ref), :3]) == tuple(size)
 
 
-@pytest.mark.parametrize("size,rot,n", [((10, 10, 10), False, 40), ((10, 10, 10), True, 20), ((20, 20, 20), False, 4)])
-def test_cut1_generator_is_rng_exact(size, rot, n):
+def _cut1_case(size, rot, n, rng=(2, 2, 2, 5, 5, 5), id=None):
+    return pytest.param(size, rot, n, rng, id=id or "%s%s-%s" % ("x".join(map(str, size)), "-rot" if rot else "", "x".join(map(str, rng))))
+
+
+@pytest.mark.parametrize("size,rot,n,rng", [
+    _cut1_case((10, 10, 10), False, 40, id="size0-False-40"), _cut1_case((10, 10, 10), True, 20, id="size1-True-20"),
+    _cut1_case((20, 20, 20), False, 4, id="size2-False-4"),
+    # the ranges the device generator is compared with the statement at (tests/stream_kind_cases.py).  Not the one-piece range:
+    # the drain loop below cannot tell an item equal to the bin from the terminator
+    _cut1_case((12, 10, 8), False, 6, (2, 2, 1, 6, 5, 3)), _cut1_case((10, 10, 10), True, 6, (2, 3, 2, 3, 6, 10)),
+    _cut1_case((8, 12, 9), False, 6, (3, 2, 2, 5, 4, 9)), _cut1_case((4, 4, 8), True, 6, (1, 1, 1, 1, 1, 1)),
+    _cut1_case((16, 6, 8), True, 6, (4, 1, 2, 300, 2, 4)), _cut1_case((15, 9, 6), False, 6, (3, 3, 1, 5, 5, 1)),
+    _cut1_case((10, 10, 10), False, 6, (2, 2, 3, 4, 5, 7))])
+def test_cut1_generator_is_rng_exact(size, rot, n, rng):
     ref_shims.install()
     from envs.bpp0.cutCreator import CuttingBoxCreator
-    rng = (2, 2, 2, 5, 5, 5)
     for s in range(n):
         random.seed(77 + s)
         np.random.seed(77 + s)

@@ -2,7 +2,8 @@
 (include/bpp_stream_kinds.h), on the CPU: the Python statements (sequences.cut1_stream_sequence / rs_stream_sequence) against
 the exact generators' distributions, and the product's refill kernels -- compiled for the host SIMT emulator -- against the
 statements: lock-step by lock-step through a pool-mode env of the C restatement (tests/stream_kind_cases.py), entry by entry
-in the ring, through a clone, and every refusal of the host entry points."""
+in the ring (at every box range and box set of that module; with rows too short and boxes that do not fit, where the overflow
+count is the statement's), through a clone, and every refusal of the host entry points."""
 import ctypes
 import os
 import random
@@ -123,11 +124,11 @@ def bind(emu):
     return L
 
 
-def kind_env(emu, kind, size, rot, E, base, seed, depth, refill, cache, box_range=RANGE, box_set=None, **kw):
+def kind_env(emu, kind, size, rot, E, base, seed, depth, refill, cache, box_range=RANGE, box_set=None, pool_len=None, **kw):
     """emu.OracleEnv over a ring whose refills are the kind's (the front-end's own refill() is CUT-2's)."""
     L = bind(emu)
     rg = _lib.box_range_arg(box_range)
-    bs = sequences.check_box_set(size, box_set)
+    bs = sequences.check_box_set(size, box_set if kind == "rs" else [(1, 1, 1)])     # (CUT-1 hands no set to its refill)
 
     class KindEnv(emu.OracleEnv):
         def refill(self):
@@ -150,7 +151,7 @@ def kind_env(emu, kind, size, rot, E, base, seed, depth, refill, cache, box_rang
             return self.out, a
 
     spec = dict(bound=bound_for_sizes(size), seed=seed, depth=depth, refill_every=refill, rng="counter", cache=cache,
-                pool_len=cases.pool_len(kind, size, box_range, box_set))
+                pool_len=pool_len or cases.pool_len(kind, size, box_range, box_set))
     return KindEnv(None, size, rot, E, env_id_base=base, env_id_total=base + E + 3, stream=spec, **kw)
 
 
@@ -174,48 +175,92 @@ def test_emulated_rows_equal_the_statement(emu, oracle, kind, size, rot, E, base
     assert int(episodes.max()) >= 4
 
 
-def expected_ring(kind, size, rot, seed, base, E, depth, gen_next, have):
-    """{(row, entry): item} for every ring entry the statement predicts: rows of episodes gen_next - depth .. gen_next - 1 of
-    every bin (`have` [E]: the bin's first episode still in the ring), their look-ahead entries where the row they repeat has
-    been generated."""
-    T = cases.pool_len(kind, size)
-    want = {}
-    for e in range(E):
-        for k in range(int(have[e]), int(gen_next[e])):
-            row = (k % depth) * E + e
-            seq = cases.statement(kind, size, rot, seed, base + e, k)
-            for j in range(T - 2):
-                want[(row, 2 + j)] = seq[j] if j < len(seq) else tuple(size)
-            for ahead, entry, item in ((1, 0, 1), (2, 1, 0)):
-                if k + ahead < gen_next[e]:
-                    nxt = cases.statement(kind, size, rot, seed, base + e, k + ahead)
-                    want[(row, entry)] = nxt[item] if item < len(nxt) else tuple(size)
-    return want
+def check_ring(env, kind, size, rot, seed, base, depth, box_range=RANGE, box_set=None):
+    return cases.ring_check(env.pool, env.gen_next, env.state["episode"], kind, size, rot, seed, base, depth, box_range, box_set)
 
 
 @pytest.mark.parametrize("kind,rot", [("cut1", False), ("cut1", True), ("rs", False)])
 def test_emulated_ring_rows_and_look_ahead_entries(emu, oracle, kind, rot):
     E, base, seed, depth = 70, 40, 11, 6
     env = kind_env(emu, kind, SIZE, rot, E, base, seed, depth, 2, False)
-
-    def check():
-        gn = env.gen_next
-        assert (gn == env.state["episode"] + depth).all()
-        want = expected_ring(kind, SIZE, rot, seed, base, E, depth, gn, np.maximum(gn - depth, 0))
-        assert len(want) >= E * depth * (cases.pool_len(kind, SIZE) - 2)
-        for (row, entry), item in want.items():
-            assert tuple(int(v) for v in env.pool[row, entry, :3]) == tuple(item), (row, entry)
-        assert (env.pool[:, :, 3] == 0).all() and int(env.overflow[0]) == 0
-    check()                                             # the first refill: episodes 0 .. depth - 1
-    obs, mask = env.reset()
-    rng = np.random.RandomState(2)
-    for t in range(12):                                 # bins at different episodes; a refill every two lock-steps
-        a = oracle.sample_feasible(mask, 1, t)
-        a[rng.rand(E) < 0.3] = -1
-        mask = env.step(a)["mask"]
+    check_ring(env, kind, SIZE, rot, seed, base, depth)     # the first refill: episodes 0 .. depth - 1
+    cases.race_bins(oracle, env, E)                         # bins at different episodes; a refill every two lock-steps
     env.refill()
     assert len(set(env.gen_next.tolist())) > 2
-    check()
+    check_ring(env, kind, SIZE, rot, seed, base, depth)
+    assert int(env.overflow[0]) == 0
+
+
+@pytest.mark.parametrize("case", cases.KIND_CASES, ids=cases.case_id)
+def test_emulated_ring_rows_equal_the_statement(emu, oracle, case):
+    """Whole rows at every box range and box set of tests/stream_kind_cases.py, after the first refill and again with the bins
+    at different episodes."""
+    kind, size, rot, box_range, box_set = case
+    E, base, seed, depth = 9 + cases.KIND_CASES.index(case) % 12, 40, 11, 6
+    env = kind_env(emu, kind, size, rot, E, base, seed, depth, 2, False, box_range, box_set)
+    check_ring(env, kind, size, rot, seed, base, depth, box_range, box_set)
+    cases.race_bins(oracle, env, E)
+    env.refill()
+    assert len(set(env.gen_next.tolist())) > 2
+    check_ring(env, kind, size, rot, seed, base, depth, box_range, box_set)
+    assert int(env.overflow[0]) == 0
+
+
+@pytest.mark.parametrize("case", [c for c in cases.KIND_CASES if c[0] == "cut1"], ids=cases.case_id)
+def test_emulated_lock_steps_at_every_box_range(emu, oracle, case):
+    kind, size, rot, box_range, _ = case
+    E, base, seed = 9 + cases.KIND_CASES.index(case) % 12, 1000, 77
+    env = kind_env(emu, kind, size, rot, E, base, seed, 6, 3, False, box_range)
+    cases.lock_step_check(oracle, env, kind, size, rot, E, base, seed, 64, box_range)
+    assert int(env.overflow[0]) == 0 and int(env.gen_next.min()) > 6
+
+
+# ---- *s->overflow above zero ------------------------------------------------------------------------------------------------------
+SHORT = 36          # a CUT-1 row of 36 entries holds 33 items; sequences at 10 x 10 x 10 under RANGE have 13 .. 39
+
+
+def test_emulated_short_cut1_rows_are_cut_and_counted(emu, oracle):
+    """Rows too short for some sequences: the row holds the statement's first 33 items and the terminator, the sequence
+    counts once -- also after further refills (the counter is cumulative) -- and the step kernel plays the cut row to its
+    terminator.  The statement alone: 11 of the first 120 sequences are longer."""
+    E, base, seed, depth = 20, 40, 11, 6
+    first = cases.expected_overflow("cut1", SIZE, False, seed, base, E, [depth] * E, pool_len_=SHORT)
+    assert 0 < first < E * depth and first == 11
+    env = kind_env(emu, "cut1", SIZE, False, E, base, seed, depth, 2, False, pool_len=SHORT)
+    assert env.pool.shape[1] == SHORT
+    check_ring(env, "cut1", SIZE, False, seed, base, depth)
+    assert int(env.overflow[0]) == first
+    cases.race_bins(oracle, env, E)
+    env.refill()
+    assert len(set(env.gen_next.tolist())) > 2
+    check_ring(env, "cut1", SIZE, False, seed, base, depth)
+    later = cases.expected_overflow("cut1", SIZE, False, seed, base, E, env.gen_next, pool_len_=SHORT)
+    assert int(env.overflow[0]) == later > first
+    # Uniform play puts 18 items at most into these bins, so at 33 items a row no bin reaches the terminator of a cut row.  At 9
+    # items a row every sequence is cut, and bins do place all nine: the tenth is the terminator on both sides.
+    for T, deepest in ((SHORT, None), (12, 9)):
+        env, played = kind_env(emu, "cut1", SIZE, False, E, base, seed, depth, 2, False, pool_len=T), []
+        cases.lock_step_check(oracle, env, "cut1", SIZE, False, E, base, seed, 64, fail=0, pool_len_=T, played=played)
+        assert deepest is None or max(int(o["counter"].max()) for o in played) == deepest
+    assert int(env.overflow[0]) == cases.expected_overflow("cut1", SIZE, False, seed, base, E, env.gen_next, pool_len_=12) == int(env.gen_next.sum())
+
+
+def test_emulated_bad_rs_boxes_are_played_as_the_terminator_and_counted_per_sequence(emu):
+    """BppVecEnv and check_box_set refuse such a set; the refill itself must play every bad draw as the terminator and count
+    the row once, however many bad draws it has."""
+    E, base, seed, depth = 20, 40, 11, 6
+    bad = cases.bad_box_set(SIZE)
+    rows = [cases.ring_items("rs", SIZE, False, seed, base + e, k, box_set=bad, T=128) for e in range(E) for k in range(depth)]
+    n_bad = [sum(it == SIZE for it in items) for items, over in rows]
+    assert 0 < sum(n > 0 for n in n_bad) < len(rows) and max(n_bad) > 1       # the statement alone: some rows, not all; per row != per item
+    env = kind_env(emu, "rs", SIZE, False, E, base, seed, depth, 2, False)
+    assert env.pool.shape[1] == 128 and int(env.overflow[0]) == 0
+    env.gen_next[:] = 0                                     # every row is written again
+    bs = cases.box_set_array(bad)
+    emu._check(bind(emu).bpp_stream_refill_rs(ctypes.byref(env.stream), bs.ctypes.data, bs.shape[0], None))
+    check_ring(env, "rs", SIZE, False, seed, base, depth, box_set=bad)
+    assert sum(n > 0 for n in n_bad) == cases.expected_overflow("rs", SIZE, False, seed, base, E, env.gen_next, box_set=bad, pool_len_=128)
+    assert int(env.overflow[0]) == sum(n > 0 for n in n_bad)
 
 
 @pytest.mark.parametrize("kind", ["cut1", "rs"])
