@@ -319,9 +319,10 @@ def test_emulated_wide_reduction_equals_the_one_workgroup_form_on_many_rows(emu,
 
 
 def test_emulated_gather_finished_compacts_in_bin_order(emu, oracle):
-    """bpp_gather_finished (ordered compaction by one workgroup, header count, five arrays of n entries) on the emulator ==
-    the oracle's loop: sizes that are not multiples of the 16-bins-per-thread / 16 384-bins-per-round shape, none / all /
-    sparse finished; a count that belongs to another step is refused."""
+    """bpp_gather_finished (ordered compaction by 64 workgroups at most, each over its own chunk of bins in rounds of 4 096;
+    header count, five arrays of n entries) on the emulator == the oracle's loop: sizes that are not multiples of the
+    16-bins-per-thread / 4 096-bins-per-round shape, none / all / sparse finished; a count that belongs to another step is
+    refused.  (Every size, pattern and alignment of `done`: tests/test_stats_kernels.py.)"""
     import ctypes
     rng = np.random.RandomState(11)
     for E, p in ((1, 1.0), (17, 0.5), (1000, 0.1), (16384, 0.11), (16385 + 77, 0.11), (40000, 0.0), (333, 1.0)):
