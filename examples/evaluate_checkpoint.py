@@ -9,7 +9,12 @@ ONE BppVecEnv (2 100 bins for cut_2.pt); a lock-step is one policy forward on th
 finished its trajectory is left alone (BPP_ACTION_NOOP).
 
     python examples/evaluate_checkpoint.py --checkpoint <reference>/pretrained_models/default_cut_2.pt \
-        --dataset <reference>/dataset/cut_2.pt [--rotation]
+        --dataset <reference>/dataset/cut_2.pt [--rotation] [--plans OUT.npz]
+
+--plans OUT.npz: also record where every box was placed (BppVecEnv.record_placements; the reference's space.boxes) and write every
+trajectory's finished packing plan to OUT.npz (bpp_amd.PackingPlans.load reads it back; .boxes(i) is trajectory i's list of
+(x, y, z, lx, ly, lz), .write_txt(path, i) the line format of user_study/user_study.py); the plans are then checked by
+bpp_amd.replay_plans, which rebuilds every bin from its plan.
 
 Only this package and torch are needed: the actor below is the reference's CNNPro actor path (acktr/model.py:265-323)
 rebuilt from plain torch layers; the checkpoint's keys are mapped onto it (`base.share.N.module.weight` -> share.N.weight,
@@ -48,10 +53,11 @@ def load_actor(path, side, n_actions, device, hidden=256):
     return actor.to(device).eval()
 
 
-def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10, 10), policy_device=None, limit=None, native=False):
+def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10, 10), policy_device=None, limit=None, native=False, plans=False):
     """-> dict(ratio float64 [n], counter int32 [n], steps int32 [n], seconds): trajectory i of `dataset` played greedily
     by the checkpoint, all of them at once.  policy_device: where the network runs (default: the env's device).
-    native: the network is bpp_amd.NativePolicy (one fused call per lock-step, logits only) instead of torch layers."""
+    native: the network is bpp_amd.NativePolicy (one fused call per lock-step, logits only) instead of torch layers.
+    plans: also record the packing plans; the dict then has `plans`, the PackingPlans of every trajectory's finished episode."""
     dev = torch.device(device)
     pdev = torch.device(policy_device) if policy_device else dev
     pool = bpp_amd.sequences.from_dataset(dataset, size, first_index=0)          # row r = trajectory r
@@ -65,6 +71,8 @@ def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10,
     else:
         actor = load_actor(checkpoint, size[0], env.action_space.n, pdev)
     obs = env.reset()
+    if plans:
+        env.record_placements()
     mask = env.location_masks
     live = torch.ones(n, dtype=torch.bool, device=dev)
     ratio = torch.zeros(n, dtype=torch.float64, device=dev)
@@ -87,8 +95,11 @@ def evaluate(checkpoint, dataset, rotation=False, device="cuda:0", size=(10, 10,
         obs, mask = res.obs, res.mask
         t += 1
     torch.cuda.synchronize(dev)
-    return dict(ratio=ratio.cpu().numpy(), counter=counter.cpu().numpy(), steps=steps.cpu().numpy(), lock_steps=t,
-                seconds=time.perf_counter() - t0)
+    out = dict(ratio=ratio.cpu().numpy(), counter=counter.cpu().numpy(), steps=steps.cpu().numpy(), lock_steps=t,
+               seconds=time.perf_counter() - t0)
+    if plans:
+        out["plans"] = env.placements(finished=True)
+    return out
 
 
 def main():
@@ -98,11 +109,21 @@ def main():
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--policy-device", default=None)
     ap.add_argument("--native", action="store_true", help="run the network as bpp_amd.NativePolicy (one fused call per lock-step)")
+    ap.add_argument("--plans", default=None, metavar="OUT.npz", help="record the packing plans and write every trajectory's finished plan there")
     args = ap.parse_args()
-    r = evaluate(args.checkpoint, args.dataset, args.rotation, policy_device=args.policy_device, native=args.native)
+    r = evaluate(args.checkpoint, args.dataset, args.rotation, policy_device=args.policy_device, native=args.native, plans=bool(args.plans))
     print("%d trajectories in one batch, %d lock-steps, %.2f s: average space utilization %.4f, average put item number %.4f, "
           "completely packed bins %d" % (len(r["ratio"]), r["lock_steps"], r["seconds"], r["ratio"].mean(), r["counter"].mean(),
                                          int((r["ratio"] == 1.0).sum())))
+    if args.plans:
+        plans = r["plans"]
+        plans.save(args.plans)
+        W, L, H = plans.size
+        _, status, volume = bpp_amd.replay_plans(bpp_amd.PackingPlans.load(args.plans), device=plans.records.device)
+        sound = int((status == -1).sum())
+        same = int((volume.cpu().numpy() / float(W * L * H) == r["ratio"]).sum())
+        print("%d packing plans written to %s: %d sound when replayed box by box, %d reproduce their trajectory's utilization as "
+              "volume / (W L H), %d records dropped" % (len(plans), args.plans, sound, same, int(plans.numpy()["overflow"][0])))
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ UPDATE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_update.h")
 KFAC_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_kfac.h")
 POLICY_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy.h")
 STREAM_KINDS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_stream_kinds.h")
+PLACEMENTS_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_placements.h")
 # everything a rebuild depends on, by glob: a new .inl or header counts from the moment it exists
 DEPS = sorted(f for d, pats in ((CSRC, ("*.hip", "*.inl")), (os.path.dirname(HDR), ("*.h", "*.inl")))
               for pat in pats for f in glob.glob(os.path.join(d, pat)))
@@ -74,6 +75,12 @@ STREAM_KIND_SYMBOLS = ["bpp_stream_refill_cut1", "bpp_stream_refill_rs", "bpp_st
 STREAM_KINDS = {"cut1": 1, "rs": 2}                  # BPP_STREAM_KIND_*
 CUT1_MAX_PIECES, RS_MAX_SET = 128, 4096
 STREAM_KINDS_INFO = ("lanes", "lds_bytes", "pieces", "threads")
+# include/bpp_placements.h: the same, for the recorded packing plans
+PLACEMENT_SYMBOLS = ["bpp_placements_sizes", "bpp_placements_clear", "bpp_placements_note", "bpp_placements_commit", "bpp_placements_copy",
+                     "bpp_placements_gather", "bpp_placements_replay", "bpp_placements_info"]
+PLAN_RUNNING, PLAN_FINISHED = 0, 1                   # BPP_PLAN_*
+PLACEMENT_BYTES, PLACEMENTS_MAX_CAPACITY = 8, 1 << 20
+PLACEMENTS_INFO = ("step_lanes", "step_groups", "plan_waves", "plan_groups", "replay_cells_per_lane", "record_bytes")
 
 
 class Batch(ctypes.Structure):
@@ -287,6 +294,31 @@ def bind_stream_kinds(L, batch=None, step_out=None, stream=None):
     return L
 
 
+def bind_placements(L, batch=None):
+    """Argument types of the PLACEMENT_SYMBOLS on library handle L (`batch`: the ctypes class of struct bpp_batch)."""
+    B = ctypes.POINTER(batch or Batch)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_placements_sizes.argtypes = [i32, i32, i32]
+    L.bpp_placements_sizes.restype = ctypes.c_int64
+    L.bpp_placements_clear.argtypes = [vp, i32, i32, i32, vp]
+    L.bpp_placements_note.argtypes = [B, vp, i32, vp, vp, i32, i32, vp]
+    L.bpp_placements_commit.argtypes = [B, vp, i32, vp, vp, i32, i32, vp]
+    L.bpp_placements_copy.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.bpp_placements_gather.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp]
+    L.bpp_placements_replay.argtypes = [vp, i32, i32, vp] + [i32] * 5 + [vp, vp, vp, vp]
+    L.bpp_placements_info.argtypes = [i32, i32, i32, ctypes.POINTER(i32)]
+    for name in PLACEMENT_SYMBOLS[1:]:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
+def placements_info(E, capacity, A, L=None):
+    """bpp_placements_info: the launch shapes of the plan kernels, as a dict."""
+    out = (ctypes.c_int32 * 6)()
+    check((L or lib()).bpp_placements_info(int(E), int(capacity), int(A), out), L)
+    return dict(zip(PLACEMENTS_INFO, (int(v) for v in out)))
+
+
 def box_range_arg(box_range):
     """The box_range[6] argument of the STREAM_KIND_SYMBOLS."""
     return (ctypes.c_int32 * 6)(*[int(v) for v in box_range])
@@ -406,6 +438,7 @@ def lib():
         bind_kfac(L)
         bind_policy(L)
         bind_stream_kinds(L)
+        bind_placements(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

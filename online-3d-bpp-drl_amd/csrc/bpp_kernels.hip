@@ -44,6 +44,7 @@
 #include "../../include/bpp_kfac.h"
 #include "../../include/bpp_policy.h"
 #include "../../include/bpp_stream_kinds.h"
+#include "../../include/bpp_placements.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1638,3 +1639,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_update.inl"
 #include "bpp_kfac.inl"
 #include "bpp_policy.inl"
+#include "bpp_placements.inl"

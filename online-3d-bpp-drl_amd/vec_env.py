@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .branch import BranchOps
+from .placements import PlacementLog, default_capacity
 from .sequences import check_box_set, check_pool, rs_stream_pool_len
 from .spaces import Box, Discrete
 
@@ -1079,6 +1080,8 @@ class BppVecEnv(BranchOps):
         last observation and its mask."""
         sd = {"format": STATE_FORMAT, "hmap": self.hmap.clone(), "state": self.state.clone(), "ep_acc": self.ep_acc.clone(),
               "first_reset": self._first_reset}
+        if self._plog is not None:     # recorded packing plans: the log as bytes, and what its layout depends on
+            sd["placements"] = dict(log=self._plog.buf.clone(), capacity=self._plog.capacity, keep_finished=bool(self._plog.keep))
         if self._stream is not None:   # streaming supply: the ring, every bin's generator and its progress
             sd.update(stream_ring=self.pool.clone(), stream_mt=self._mt.clone(), stream_gen_next=self.gen_next.clone(),
                       stream_since_refill=self._since_refill, stream_spec=self._stream_identity(), stream_layout=STREAM_LAYOUT)
@@ -1099,6 +1102,16 @@ class BppVecEnv(BranchOps):
         return ident
 
     def load_state_dict(self, sd):
+        plans, log = sd.get("placements"), self._plog
+        if plans is not None and log is None:
+            raise ValueError("checkpoint with recorded packing plans loaded into an env that records none (its plans would be dropped): "
+                             "call record_placements(capacity=%d, keep_finished=%r) first" % (int(plans["capacity"]), bool(plans["keep_finished"])))
+        if plans is None and log is not None:
+            raise ValueError("checkpoint without packing plans loaded into an env that records them (its plans would not be the bins')")
+        if plans is not None and (int(plans["capacity"]) != log.capacity or bool(plans["keep_finished"]) != bool(log.keep) or
+                                  plans["log"].numel() != log.buf.numel()):
+            raise ValueError("checkpoint plans with capacity %d, keep_finished %r; this env records with capacity %d, keep_finished %r"
+                             % (int(plans["capacity"]), bool(plans["keep_finished"]), log.capacity, bool(log.keep)))
         if self._stream is None and "stream_ring" in sd:
             raise ValueError("checkpoint of a streaming env loaded into a pool-based env (its ring and generators would be dropped)")
         if self._stream is not None:
@@ -1149,6 +1162,8 @@ class BppVecEnv(BranchOps):
             self._reset_seq_cache()
             if self._since_refill >= self.refill_every:   # (written by an env with a longer refill period)
                 self.refill()
+        if plans is not None:
+            log.buf.copy_(plans["log"])
         if "obs" in sd:
             bufs, _ = self._buffers()
             if self._res is None or self.fresh_outputs:
@@ -1157,7 +1172,103 @@ class BppVecEnv(BranchOps):
             bufs["obs"].copy_(sd["obs"])
             if "mask" in sd and bufs["mask"] is not None:
                 bufs["mask"].copy_(sd["mask"])
-        
+
+    # ------------------------------------------------------------------ packing plans (include/bpp_placements.h)
+    _plog = None       # the PlacementLog of an env that records (record_placements); never looked at on the step path
+
+    def record_placements(self, capacity=None, keep_finished=True):
+        """From here on keep every bin's packing plan -- the reference's space.boxes / space.flags (envs/bpp0/space.py:23-24,
+        176-177) -- in a device log: bpp_placements_note before and bpp_placements_commit after every lock-step of step_tensors
+        (and so of RolloutStorage.step, step_subset, observe), step / step_async, and step_bins, on the same stream, without a
+        host synchronisation.  capacity: records kept per plan (default min(W L H, 256); a longer plan keeps counting, drops the
+        rest and counts it in `overflow`); keep_finished: also keep every bin's last finished plan.  Allowed directly after
+        reset(), before the first step.  reset() clears the log (an abandoned episode is no finished plan); copy_bins /
+        clone_bins / clone_into copy plans; state_dict() carries the log.  The native rollout drivers (rollout_uniform,
+        rollout_uniform_sets) step bins behind the log's back and raise RuntimeError while recording is on.  The three searches
+        step SCRATCH bins with kernels of their own: a scratch bin's plan is undefined while a search uses it; the real bins,
+        stepped through step_bins / step_tensors, are recorded with the item they really placed (bpp_env_state.item_cur at that
+        moment -- the reorder search's reordered item included).
+        Recording is switched on by shadowing the stepping methods on THIS instance: an env that does not record runs the
+        same code as before, without a launch, an allocation or an attribute lookup more."""
+        if self._plog is not None:
+            raise RuntimeError("this env records its packing plans already")
+        if self._first_reset or bool((self.state[:, [2, 5]] != 0).any()):
+            raise RuntimeError("record_placements() goes directly after reset(), before the first step: the plans of boxes "
+                               "placed earlier are not known")
+        if capacity is None:
+            capacity = default_capacity(self.bin_size)
+        if not 1 <= int(capacity) <= _lib.PLACEMENTS_MAX_CAPACITY:
+            raise ValueError("capacity must be in 1 .. %d" % _lib.PLACEMENTS_MAX_CAPACITY)
+        self._on_device()
+        self._plog = PlacementLog(self, int(capacity), keep_finished)
+        for name in ("step_tensors", "step_bins", "reset", "copy_bins", "clone_bins"):
+            setattr(self, name, getattr(self, "_rec_" + name))
+        self.rollout_uniform = self.rollout_uniform_sets = self._rec_refuse
+        return self
+
+    def placements(self, ids=None, finished=False):
+        """PackingPlans (placements.py) of bins `ids` (default: all): their running plans, or with finished=True the plans of
+        the last episode each finished (count -1: none yet).  One launch, no synchronisation; the tensors are on the device."""
+        if self._plog is None:
+            raise RuntimeError("this env records no packing plans: call record_placements() after reset()")
+        if finished and not self._plog.keep:
+            raise ValueError("record_placements(keep_finished=False) keeps no finished plans")
+        return self._plog.gather(None if ids is None else self._ids(ids), finished, self.bin_size)
+
+    def _rec_refuse(self, *args, **kw):
+        raise RuntimeError("the native rollout drivers step bins without recording their packing plans; step with step_tensors / "
+                           "step / step_bins while record_placements() is on")
+
+    def _rec_step_tensors(self, actions, sample=None, _host=None, _dropin=None, out=None):
+        if self._first_reset:
+            raise RuntimeError("call reset() before step()")
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a))
+        if a.numel() != self.E:
+            raise ValueError("expected %d actions, got %d" % (self.E, a.numel()))
+        if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
+            a = a.to(device=self.device, dtype=torch.int64).contiguous()
+        self._on_device()
+        log, sp = self._plog, self._stream_ptr()
+        log.note(None, 0, a.data_ptr(), sp)
+        res = BppVecEnv.step_tensors(self, a, sample=sample, _host=_host, _dropin=_dropin, out=out)
+        log.commit(None, 0, res.done.data_ptr(), sp)      # (behind the completion word of step_async: the host waits for the word only)
+        return res
+
+    def _rec_step_bins(self, ids, actions, sample=None, check=True):
+        if self._first_reset:
+            raise RuntimeError("call reset() before step_bins()")
+        ids = self._ids(ids)
+        a = torch.as_tensor(actions, device=self.device).reshape(-1)
+        if a.dtype != torch.int64 or not a.is_contiguous():
+            a = a.to(torch.int64).contiguous()
+        if a.numel() != ids.numel():
+            raise ValueError("ids and actions must have the same length")
+        if check:
+            self._check_ids(ids)
+        self._on_device()
+        log, sp, n = self._plog, self._stream_ptr(), ids.numel()
+        log.note(ids.data_ptr(), n, a.data_ptr(), sp)
+        res = BranchOps.step_bins(self, ids, a, sample=sample, check=False)
+        log.commit(ids.data_ptr(), n, res.done.data_ptr(), sp)
+        return res
+
+    def _rec_reset(self, out=None):
+        obs = BppVecEnv.reset(self, out=out)
+        self._plog.clear()
+        return obs
+
+    def _rec_copy_bins(self, src, dst):
+        BppVecEnv.copy_bins(self, src, dst)
+        self._plog.copy(self._ids(src), self._ids(dst))
+
+    def _rec_clone_bins(self, src, dst, check=True):
+        src, dst = self._ids(src), self._ids(dst)
+        BranchOps.clone_bins(self, src, dst, check=check)
+        if src.numel():
+            self._plog.copy(src, dst)
+
     def state_numpy(self):
         """bpp_env_state[E] as a structured numpy array (tests)."""
         dt = np.dtype([("cursor", "<i4"), ("episode", "<i4"), ("n_boxes", "<i4"), ("vol_sum", "<i4"),
