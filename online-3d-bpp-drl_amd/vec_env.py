@@ -19,15 +19,14 @@ import torch
 from . import _lib
 from .branch import BranchOps
 from .placements import PlacementLog, default_capacity
-from .sequences import check_box_set, check_pool, rs_stream_pool_len
+from .sequences import check_pool
 from .spaces import Box, Discrete
+from .supply import STREAM_LAYOUT  # noqa: F401 -- a streaming checkpoint's layout number stays readable as vec_env.STREAM_LAYOUT
+from .supply import StreamSupply, check_checkpoint, copy_stream_records, release_handle, resolve_stream_spec
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 STATE_FORMAT = 1      # state_dict()["format"]: 1 = 48-byte records whose last word is hmax, per-bin ep_acc rows
-STREAM_LAYOUT = 2     # state_dict()["stream_layout"]: layout of the ring rows and generator records of a streaming env.
-#                       2 = ring rows start with two look-ahead entries, item i at entry 2 + i; byte-output MT19937 records /
-#                       16-byte counter records (ABI v12+).  A checkpoint without the key (layout 1 or older) is refused.
 # rollout_uniform_sets: chains of step-kernel launches the bins are split over (include/bpp_pipeline.h), where nothing is asked for.
 # Measured (profiles/pipelined_rollout_ab.json, pipelined_rollout_groups.json): two chains win on every workload,
 # three and four lose to two.  The default is two for the 10x10 bins from 32 768 bins up and one for everything else: smaller
@@ -283,20 +282,12 @@ class MonitorCsv(object):
 
 def copy_bin_records(hmap, state, src, dst, ring=None, mt=None, gen_next=None, depth=None):
     """Bins `dst` become copies of bins `src` (int64 index tensors on the tensors' device): byte heightmap [E][A] and
-    the 48-byte record as int32 [E][12].  Streaming supply (ring [depth * E][T][4], generator records mt [E][*], gen_next
-    [E]): the copy continues the SOURCE's item stream, so its ring column, generator record and progress are copied
-    too -- and, because a ring row number encodes the bin (row = (episode mod depth) * E + bin, advanced by += E in the
-    step kernels), the copied `seq` is rebased from the source's column to the destination's; without that the copy
-    would go on reading the source's column, which the source's refills overwrite."""
+    the 48-byte record as int32 [E][12].  With the buffers of a streaming supply (ring, mt, gen_next, depth) the copy continues
+    the SOURCE's item stream as well (supply.copy_stream_records)."""
     hmap[dst] = hmap[src]
     state[dst] = state[src]
     if ring is not None:
-        E = state.shape[0]
-        cols = ring.view(int(depth), E, -1)
-        cols[:, dst] = cols[:, src]
-        mt[dst] = mt[src]
-        gen_next[dst] = gen_next[src]
-        state[dst, 7] = state[src, 7] - src.to(state.dtype) + dst.to(state.dtype)     # bpp_env_state.seq
+        copy_stream_records(state, src, dst, ring, mt, gen_next, depth)
 
 
 class BppVecEnv(BranchOps):
@@ -319,22 +310,8 @@ class BppVecEnv(BranchOps):
     fresh_outputs:  allocate new output tensors every step (reference semantics: results of earlier
                     steps stay valid); False = reuse one set of buffers, results are valid until the
                     next step/reset call.
-    stream:         instead of `pool`: dict(bound=(lo, hi), seed=s, depth=D, refill_every=R, rng="mt19937") -- an endless
-                    CUT-2 supply generated on the device (include/bpp_abi.h: bpp_stream).  Every bin owns an exact
-                    random.Random(seed + global bin id); its k-th episode plays the k-th sequence that stream
-                    yields through the reference's MDlayerBoxCreator, so no sequence is ever replayed.
-                    rng="counter": the same cutting algorithm on a counter-based generator (distribution parity,
-                    SURVEY 8f2's bar; no per-bin state, no regeneration kernel -- the fast supply).  The ring
-                    is refilled every R <= D - 3 lock-steps, R <= D - 4 with the row cache (default D = 8: R = 4 for
-                    the 10x10 / 20x20 bins, whose tile step kernel keeps a row cache by default -- cache=True / False
-                    overrides --, R = 5 for every other geometry); `rollout_uniform` runs the refills beside the
-                    lock-steps when D >= 2 R + 3 (+ 4 with the cache; e.g. D = 32, R = 14).  Costs 6.6 KB of
-                    generator state per bin (16 bytes with rng="counter") plus D rows of W*L*H / lo^3 + 3 entries.
-                    kind="cut1", box_range=(low_x, low_y, low_z, high_x, high_y, high_z) / kind="rs", box_set=[(x, y, z), ...]
-                    (default sequences.DEFAULT_BOX_SET): the reference's other two generators as endless supplies
-                    (include/bpp_stream_kinds.h; episode k of a bin = sequences.cut1_stream_sequence / rs_stream_sequence for
-                    (seed, global bin id, k)); counter generator only (rng defaults to "counter", "mt19937" is refused),
-                    `bound` is not used; CUT-1 follows enable_rotation; refills run between the lock-steps.  No `kind`: CUT-2.
+    stream:         instead of `pool`: dict(bound=(lo, hi), seed=s, depth=D, refill_every=R, rng=..., kind=...) -- an endless supply
+                    generated on the device; what the keys mean and default to is supply.resolve_stream_spec's contract.
     """
 
     def __init__(self, num_envs, container_size=(10, 10, 10), enable_rotation=False, pool=None, device="cuda",
@@ -372,79 +349,17 @@ class BppVecEnv(BranchOps):
         self.env_id_base = int(env_id_base)
         self.env_id_total = int(env_id_total) if env_id_total is not None else self.env_id_base + self.E
         dev = self.device
-        self.stream_spec = None
+        self.stream_spec = self.supply = self._stream = None
         with torch.cuda.device(dev):
             if stream is None:
-                self.pool = torch.from_numpy(self.pool_host).to(dev)
+                self.pool, seq_cache = torch.from_numpy(self.pool_host).to(dev), None
                 pool_rows, pool_len, pool_mode = self.pool_host.shape[0], self.pool_host.shape[1], _lib.POOL_STATIC
-            else:
-                kind = stream.get("kind", "cut2")
-                if kind not in ("cut2", "cut1", "rs"):
-                    raise ValueError("stream kind must be 'cut2', 'cut1' or 'rs', got %r" % (kind,))
-                depth = int(stream.get("depth", 8))
-                kind_spec = {}
-                if kind == "cut2":
-                    lo, hi = (int(v) for v in stream.get("bound", (2, 5)))
-                    rng_name = stream.get("rng", "mt19937")
-                    default_len = self.W * self.L * self.H // lo ** 3 + 3
-                else:       # include/bpp_stream_kinds.h: counter generator only; `bound` merely sizes the scratch of the scan
-                    rng_name = stream.get("rng", "counter")
-                    if rng_name != "counter":
-                        raise ValueError("stream kind %r is generated by the counter generator only (rng='counter'), got rng=%r" % (kind, rng_name))
-                    lo = max(1, min(self.bin_size) // 2)
-                    hi = 2 * lo - 1
-                    if kind == "cut1":
-                        box_range = tuple(int(v) for v in stream.get("box_range", (2, 2, 2, 5, 5, 5)))
-                        if len(box_range) != 6 or min(box_range[:3]) < 1 or any(box_range[k] > box_range[3 + k] for k in range(3)):
-                            raise ValueError("box_range must be (low_x, low_y, low_z, high_x, high_y, high_z) with 1 <= low <= high, got %r"
-                                             % (box_range,))
-                        default_len = self.W * self.L * self.H // (box_range[0] * box_range[1] * box_range[2]) + 3
-                        kind_spec = dict(box_range=box_range)
-                    else:
-                        box_set = check_box_set(self.bin_size, stream.get("box_set"))
-                        default_len = rs_stream_pool_len(self.bin_size, box_set[:, :3])
-                        if int(stream.get("pool_len", default_len)) < default_len:
-                            raise ValueError("an RS stream needs pool_len >= %d (W*L*H / smallest box volume + 3): a bin must be full "
-                                             "before its row ends" % default_len)
-                        kind_spec = dict(box_set=tuple(tuple(int(v) for v in b[:3]) for b in box_set))
-                        self._box_set = torch.from_numpy(box_set).to(dev)
-                # bpp_batch.seq_cache: the row cache (include/bpp_abi.h) -- no step workgroup waits for a read of the ring;
-                # its lines refer to the row after next, which costs one row of look-ahead.  Default: wherever the refill
-                # schedule leaves that row
-                if stream.get("cache") is not None:
-                    cache = bool(stream["cache"])
-                else:       # only the tile step kernel keeps the cache: any other geometry would pay a row of look-ahead for nothing
-                    cache = depth >= 5 and depth - int(stream.get("refill_every", 1)) >= 4 and \
-                        int(stream.get("pool_len", default_len)) < 8192 and \
-                        _lib.launch_info(self.E, self.bin_size, self.can_rotate)["kernel"] == 2      # BPP_KERNEL_TILE
-                behind = 4 if cache else 3
-                if depth < behind + 1:
-                    raise ValueError("stream depth must be >= %d" % (behind + 1))
-                # entries per ring row: two look-ahead entries (include/bpp_abi.h), the longest possible sequence, the terminator
-                pool_len = int(stream.get("pool_len", default_len))
-                self.refill_every = int(stream.get("refill_every", depth - behind))
-                if not 1 <= self.refill_every <= depth - behind:
-                    raise ValueError("refill_every must be in 1 .. depth - %d" % behind)
-                self.pool = torch.zeros((depth * self.E, pool_len, 4), dtype=torch.uint8, device=dev)   # the ring
-                sizes = (ctypes.c_int64 * 2)()      # the two opaque buffers of a bpp_stream: generator records, scratch
-                rng = {"mt19937": _lib.STREAM_RNG_MT19937, "counter": _lib.STREAM_RNG_COUNTER}[rng_name]
-                probe = _lib.Stream(self.E, depth, pool_len, self.W, self.L, self.H, lo, hi, 0, 0, None, None, None, None, None, None, rng, 0)
-                _lib.check(self.lib.bpp_stream_sizes(ctypes.byref(probe), sizes))
-                if kind == "cut1":      # the caps of the CUT-1 kernel and the ranges the reference's cutter fails on
-                    try:
-                        _lib.stream_kinds_info(probe, kind, box_range)
-                    except RuntimeError as exc:
-                        raise ValueError(str(exc))
-                self._mt = torch.zeros((self.E, int(sizes[0]) // self.E), dtype=torch.int32, device=dev)
-                self._work = torch.zeros(((int(sizes[1]) + 15) // 16, 4), dtype=torch.int32, device=dev)
-                self.gen_next = torch.zeros((self.E,), dtype=torch.int32, device=dev)
-                self.stream_overflow = torch.zeros((1,), dtype=torch.int32, device=dev)
-                self._seq_cache = torch.zeros((self.E * _lib.SEQ_CACHE_BYTES_PER_BIN,), dtype=torch.uint8, device=dev) if cache else None
-                pool_rows, pool_mode = depth * self.E, _lib.POOL_RING
-                self.stream_spec = dict(bound=(lo, hi), seed=int(stream.get("seed", 0)), depth=depth, pool_len=pool_len,
-                                        refill_every=self.refill_every, rng=rng_name, cache=cache)
-                if kind != "cut2":      # (a spec without `kind` is CUT-2, as before the other kinds existed)
-                    self.stream_spec.update(kind=kind, **kind_spec)
+            else:       # the supply (supply.py) owns the ring and all behind it; the names set here are the env's public surface
+                resolved = resolve_stream_spec(self.E, self.bin_size, self.can_rotate, stream)
+                sup = self.supply = StreamSupply(self.lib, dev, resolved, self.env_id_base, self.can_rotate)
+                self.stream_spec, self.refill_every, self._stream = resolved.spec, resolved.refill_every, sup.stream
+                self.pool, self.gen_next, self.stream_overflow, seq_cache = sup.ring, sup.gen_next, sup.overflow, sup.seq_cache
+                pool_rows, pool_len, pool_mode = sup.ring.shape[0], resolved.pool_len, _lib.POOL_RING
             self.hmap = torch.zeros((self.E, self.A), dtype=torch.uint8, device=dev)  # Space.plain as bytes
             self.state = torch.zeros((self.E, 12), dtype=torch.int32, device=dev)  # bpp_env_state[E], 48 B each
             # episode statistics kept inside the step kernel, one row per bin: [return sum, final-ratio sum, length
@@ -454,21 +369,11 @@ class BppVecEnv(BranchOps):
                                  pool_rows, pool_len, self.env_id_base, self.env_id_total,
                                  self.pool.data_ptr(), self.hmap.data_ptr(), self.state.data_ptr(),
                                  self.ep_acc.data_ptr(), pool_mode, 0,
-                                 self._seq_cache.data_ptr() if self.stream_spec is not None and self._seq_cache is not None else None)
+                                 seq_cache.data_ptr() if seq_cache is not None else None)
         self._batch_ref = ctypes.byref(self._batch)
-        self._stream = None
-        self._since_refill = 0
-        if self.stream_spec is not None:
-            sp = self.stream_spec
-            self._stream = _lib.Stream(self.E, sp["depth"], sp["pool_len"], self.W, self.L, self.H, sp["bound"][0], sp["bound"][1],
-                                       self.env_id_base, sp["seed"], self.pool.data_ptr(), self._mt.data_ptr(),
-                                       self._work.data_ptr(), self.gen_next.data_ptr(), self.state.data_ptr(),
-                                       self.stream_overflow.data_ptr(),
-                                       {"mt19937": _lib.STREAM_RNG_MT19937, "counter": _lib.STREAM_RNG_COUNTER}[sp["rng"]], 0)
-            self._box_range = _lib.box_range_arg(sp["box_range"]) if sp.get("kind") == "cut1" else None
-            with torch.cuda.device(dev):
-                _lib.check(self.lib.bpp_stream_init(ctypes.byref(self._stream), self._stream_ptr()))
-            self.refill()
+        if self.supply is not None:
+            self._on_device()
+            self.supply.start(self.state, self._stream_ptr())
         self._bufs = None
         self._out = None
         self._set_owner = object()     # marks the output sets _alloc() makes (StepTensors._owner): no reference back to the env
@@ -481,7 +386,6 @@ class BppVecEnv(BranchOps):
         self._mark = 0             # serial number of the last bpp_mark (never 0: a cleared completion word)
         self._tstart = time.time()
         self.monitor = None        # MonitorCsv (make_vec_envs with a log_dir): step_wait() appends the finished episodes' rows
-        self._side = None          # bpp_side (rollout_uniform in streaming mode): created on first use
         groups = _ENV_ROLLOUT_GROUPS or rollout_groups or default_rollout_groups(self.E, self.W, self.L)
         if not 1 <= int(groups) <= _lib.PIPELINE_MAX_GROUPS:
             raise ValueError("rollout_groups must be in 1 .. %d" % _lib.PIPELINE_MAX_GROUPS)
@@ -662,30 +566,14 @@ class BppVecEnv(BranchOps):
 
     def refill(self):
         """Streaming supply: cut new sequences for the episodes the bins have consumed (four kernels, no host sync)."""
-        if self._stream is None:
+        if self.supply is None:
             raise RuntimeError("refill() needs a streaming env (stream=dict(...))")
         self._on_device()
-        kind = self.stream_spec.get("kind", "cut2")
-        if kind == "cut1":
-            rc = self.lib.bpp_stream_refill_cut1(ctypes.byref(self._stream), self._box_range, int(self.can_rotate), self._stream_ptr())
-        elif kind == "rs":
-            rc = self.lib.bpp_stream_refill_rs(ctypes.byref(self._stream), self._box_set.data_ptr(), int(self._box_set.shape[0]), self._stream_ptr())
-        else:
-            rc = self.lib.bpp_stream_refill(ctypes.byref(self._stream), self._stream_ptr())
-        _lib.check(rc)
-        self._since_refill = 0
-
-    def _reset_seq_cache(self):
-        """`state` or the ring were written behind the library's back: zero the row cache (the kernels then read the ring
-        until their refresh requests have been served again)."""
-        if self._stream is not None and self._seq_cache is not None:
-            self._seq_cache.zero_()
+        self.supply.refill(self._stream_ptr())
 
     def _stepped(self, n=1):
-        if self._stream is not None:
-            self._since_refill += n
-            if self._since_refill >= self.refill_every:
-                self.refill()
+        if self.supply is not None and self.supply.stepped(n):
+            self.refill()
 
     def _on_device(self):
         """HIP launches target the calling thread's current device: make sure it is ours (cheap check,
@@ -728,6 +616,23 @@ class BppVecEnv(BranchOps):
         self._tstart = time.time()
         return bufs["obs"]
 
+    def _actions(self, actions):
+        """The actions of one lock-step (int [E] or [E,1], tensor or array-like) as a contiguous int64 tensor on the env's device."""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a))
+        if a.numel() != self.E:
+            raise ValueError("expected %d actions, got %d" % (self.E, a.numel()))
+        # ([E] and [E,1] contiguous tensors share their memory layout: no reshape needed)
+        if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
+            a = a.to(device=self.device, dtype=torch.int64).contiguous()
+        return a
+
+    def _check_int64(self, t, message):
+        """ValueError(message) unless `t` is a contiguous int64 [E] tensor on the env's device."""
+        if t.device != self.device or t.dtype != torch.int64 or t.numel() != self.E or not t.is_contiguous():
+            raise ValueError(message)
+
     def step_tensors(self, actions, sample=None, _host=None, _dropin=None, out=None):
         """Enqueue one lock-step; returns device tensors, never synchronises.  actions: int64 [E] or [E,1].
         sample=(seed, step, out): additionally draw, inside the step kernel, the uniform-feasible action
@@ -739,14 +644,7 @@ class BppVecEnv(BranchOps):
         (RolloutStorage.step; _caller_set) -- None changes nothing."""
         if self._first_reset:
             raise RuntimeError("call reset() before step()")
-        a = actions
-        if not torch.is_tensor(a):
-            a = torch.as_tensor(np.asarray(a))
-        if a.numel() != self.E:
-            raise ValueError("expected %d actions, got %d" % (self.E, a.numel()))
-        # ([E] and [E,1] contiguous tensors share their memory layout: no reshape needed)
-        if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=torch.int64).contiguous()
+        a = self._actions(actions)
         self._on_device()
         if out is not None:
             if _host is not None or _dropin is not None:
@@ -760,8 +658,7 @@ class BppVecEnv(BranchOps):
             out = self._out          # this output set's own bpp_step_out: the per-call fields are set in place (no struct copy)
         if sample is not None:
             seed, step, nxt = sample
-            if nxt.device != self.device or nxt.dtype != torch.int64 or nxt.numel() != self.E or not nxt.is_contiguous():
-                raise ValueError("sample out tensor must be a contiguous int64 [E] tensor on the env's device")
+            self._check_int64(nxt, "sample out tensor must be a contiguous int64 [E] tensor on the env's device")
             out.next_action, out.sample_seed, out.sample_step = nxt.data_ptr(), int(seed), int(step)
         else:
             out.next_action = None
@@ -795,26 +692,11 @@ class BppVecEnv(BranchOps):
             actions = torch.empty((self.E,), dtype=torch.int64, device=self.device)
         self._on_device()
         self._serial += int(nsteps)
-        if self._stream is not None and self.stream_spec.get("kind", "cut2") != "cut2":
-            self.refill()
-            rs = self.stream_spec["kind"] == "rs"
-            _lib.check(self.lib.bpp_rollout_uniform_stream_kind(
-                self._batch_ref, ctypes.byref(self._plain(self._out)), actions.data_ptr(), int(seed), int(step0), int(nsteps),
-                ctypes.byref(self._stream), self.refill_every, _lib.STREAM_KINDS[self.stream_spec["kind"]], self._box_range, int(self.can_rotate),
-                self._box_set.data_ptr() if rs else None, int(self._box_set.shape[0]) if rs else 0, self._stream_ptr()))
-            self._since_refill = 0
-            return self._res
-        if self._stream is not None:
-            self.refill()
-            if self._side is None:      # the overlapped schedule's side stream + events: this env's own (bpp_side_create), released in close()
-                self._side = ctypes.c_void_p()
-                _lib.check(self.lib.bpp_side_create(ctypes.byref(self._side)))
-            _lib.check(self.lib.bpp_rollout_uniform_stream(self._batch_ref, ctypes.byref(self._plain(self._out)), actions.data_ptr(), int(seed),
-                                                           int(step0), int(nsteps), ctypes.byref(self._stream),
-                                                           self.refill_every, self._side, self._stream_ptr()))
-            return self._res
-        _lib.check(self.lib.bpp_rollout_uniform(self._batch_ref, ctypes.byref(self._plain(self._out)), actions.data_ptr(), int(seed),
-                                                int(step0), int(nsteps), self._stream_ptr()))
+        if self.supply is not None:
+            self.supply.rollout_uniform(self._batch_ref, self._plain(self._out), actions, seed, step0, nsteps, self._stream_ptr())
+        else:
+            _lib.check(self.lib.bpp_rollout_uniform(self._batch_ref, ctypes.byref(self._plain(self._out)), actions.data_ptr(), int(seed),
+                                                    int(step0), int(nsteps), self._stream_ptr()))
         return self._res
 
     def output_sets(self, n):
@@ -844,8 +726,7 @@ class BppVecEnv(BranchOps):
             raise RuntimeError("rollout_uniform_sets drives finite pools; streaming envs use rollout_uniform")
         if not self.compute_mask or self.fresh_outputs:
             raise RuntimeError("rollout_uniform_sets needs compute_mask=True and fresh_outputs=False")
-        if actions.device != self.device or actions.dtype != torch.int64 or actions.numel() != self.E or not actions.is_contiguous():
-            raise ValueError("actions must be a contiguous int64 [E] tensor on the env's device")
+        self._check_int64(actions, "actions must be a contiguous int64 [E] tensor on the env's device")
         if sets is None:
             sets = [self._buffers()]
         for st in sets:                 # a caller's set of another geometry would be written out of bounds
@@ -946,15 +827,11 @@ class BppVecEnv(BranchOps):
         self.closed = True
 
     def _release_side(self):
-        side, self._side = getattr(self, "_side", None), None
+        if getattr(self, "supply", None) is not None:
+            self.supply.close()
         pipe, self._pipe = getattr(self, "_pipe", None), None
-        for handle, destroy in ((side, "bpp_side_destroy"), (pipe, "bpp_pipeline_destroy")):
-            if handle is not None and handle.value:
-                try:
-                    with torch.cuda.device(self.device):
-                        getattr(self.lib, destroy)(handle)
-                except Exception:  # noqa: BLE001 -- interpreter shutdown: the runtime may be gone already
-                    pass
+        if pipe is not None:
+            release_handle(self.lib, self.device, pipe, "bpp_pipeline_destroy")
 
     def __del__(self):
         self._release_side()
@@ -987,8 +864,7 @@ class BppVecEnv(BranchOps):
     def epsilon_override(self, actions, seed, step, eps):
         """bpp_epsilon_override on an int64 [E] device tensor of actions, in place: with probability `eps` a bin's action
         becomes a uniform draw over all act_len entries (the failure-path variant of the benchmark policy)."""
-        if actions.device != self.device or actions.dtype != torch.int64 or actions.numel() != self.E or not actions.is_contiguous():
-            raise ValueError("actions must be a contiguous int64 [E] tensor on the env's device")
+        self._check_int64(actions, "actions must be a contiguous int64 [E] tensor on the env's device")
         self._on_device()
         _lib.check(self.lib.bpp_epsilon_override(actions.data_ptr(), self.E, self.M, self.env_id_base, int(seed), int(step),
                                                  _lib.eps_q24(eps), self._stream_ptr()))
@@ -1063,12 +939,9 @@ class BppVecEnv(BranchOps):
         dst = torch.as_tensor(dst, dtype=torch.int64, device=self.device).reshape(-1)
         if src.numel() != dst.numel():
             raise ValueError("src and dst must have the same length")
-        if self._stream is not None:
-            copy_bin_records(self.hmap, self.state, src, dst, ring=self.pool, mt=self._mt, gen_next=self.gen_next,
-                             depth=self.stream_spec["depth"])
-            self._reset_seq_cache()
-        else:
-            copy_bin_records(self.hmap, self.state, src, dst)
+        copy_bin_records(self.hmap, self.state, src, dst)
+        if self.supply is not None:
+            self.supply.copy_bins(self.state, src, dst)
 
     def heightmaps(self):
         """`Space.plain` of every bin as int32 [E, W, L] (the state itself is kept as bytes)."""
@@ -1082,24 +955,13 @@ class BppVecEnv(BranchOps):
               "first_reset": self._first_reset}
         if self._plog is not None:     # recorded packing plans: the log as bytes, and what its layout depends on
             sd["placements"] = dict(log=self._plog.buf.clone(), capacity=self._plog.capacity, keep_finished=bool(self._plog.keep))
-        if self._stream is not None:   # streaming supply: the ring, every bin's generator and its progress
-            sd.update(stream_ring=self.pool.clone(), stream_mt=self._mt.clone(), stream_gen_next=self.gen_next.clone(),
-                      stream_since_refill=self._since_refill, stream_spec=self._stream_identity(), stream_layout=STREAM_LAYOUT)
+        if self.supply is not None:
+            sd.update(self.supply.state_items())
         if self._res is not None:       # (the env's own output set, or the caller's set the last reset / lock-step wrote)
             sd["obs"] = self._res["obs"].clone()
             if self._res["mask"] is not None:
                 sd["mask"] = self._res["mask"].clone()
         return sd
-
-    def _stream_identity(self):
-        """What must agree for a streaming checkpoint to continue the same item streams."""
-        sp = self.stream_spec
-        ident = dict(bound=tuple(sp["bound"]), seed=sp["seed"], depth=sp["depth"], pool_len=sp["pool_len"],
-                     num_envs=self.E, env_id_base=self.env_id_base, bin_size=self.bin_size, rng=sp["rng"])
-        if sp.get("kind", "cut2") != "cut2":     # the kind and what defines its sequences; a checkpoint without `kind` is CUT-2
-            ident.update(kind=sp["kind"], rotation=self.can_rotate)
-            ident.update({k: sp[k] for k in ("box_range", "box_set") if k in sp})
-        return ident
 
     def load_state_dict(self, sd):
         plans, log = sd.get("placements"), self._plog
@@ -1112,29 +974,7 @@ class BppVecEnv(BranchOps):
                                   plans["log"].numel() != log.buf.numel()):
             raise ValueError("checkpoint plans with capacity %d, keep_finished %r; this env records with capacity %d, keep_finished %r"
                              % (int(plans["capacity"]), bool(plans["keep_finished"]), log.capacity, bool(log.keep)))
-        if self._stream is None and "stream_ring" in sd:
-            raise ValueError("checkpoint of a streaming env loaded into a pool-based env (its ring and generators would be dropped)")
-        if self._stream is not None:
-            if "stream_ring" not in sd:
-                raise ValueError("checkpoint of a pool-based env loaded into a streaming env")
-            layout = sd.get("stream_layout")
-            if layout is None:
-                # checkpoints written before the key existed: layout 1 (ABI <= 11) kept raw 32-bit MT19937 outputs -- another
-                # record width than layout 2's byte outputs (ABI 12 / 13 wrote layout 2 without saying so) -- and rows without the
-                # two look-ahead entries: the buffer shapes tell them apart
-                same = (tuple(sd["stream_ring"].shape) == tuple(self.pool.shape) and tuple(sd["stream_mt"].shape) == tuple(self._mt.shape))
-                layout = STREAM_LAYOUT if same else 1
-            if int(layout) != STREAM_LAYOUT:
-                raise ValueError("streaming checkpoint with ring / generator layout %d, this build reads layout %d: its rows would be "
-                                 "played as other items" % (int(layout), STREAM_LAYOUT))
-            want, got = self._stream_identity(), sd.get("stream_spec")
-            if got is not None:
-                got = dict(got)
-                got.setdefault("rng", "mt19937")      # checkpoints older than the counter generator
-            if got is not None and dict(got) != want:
-                raise ValueError("checkpoint stream_spec %r does not match this env's %r" % (dict(got), want))
-            if tuple(sd["stream_ring"].shape) != tuple(self.pool.shape) or tuple(sd["stream_mt"].shape) != tuple(self._mt.shape):
-                raise ValueError("checkpoint stream_spec: ring / generator buffers have another shape than this env's")
+        check_checkpoint(self.supply, sd)
         if tuple(sd["hmap"].shape) != tuple(self.hmap.shape):
             raise ValueError("checkpoint holds %r heightmaps, this env %r" % (tuple(sd["hmap"].shape), tuple(self.hmap.shape)))
         fmt = int(sd.get("format", 0))
@@ -1154,14 +994,9 @@ class BppVecEnv(BranchOps):
         else:
             self.ep_acc.zero_()
         self._first_reset = bool(sd["first_reset"])
-        if self._stream is not None:
-            self.pool.copy_(sd["stream_ring"])
-            self._mt.copy_(sd["stream_mt"])
-            self.gen_next.copy_(sd["stream_gen_next"])
-            self._since_refill = int(sd["stream_since_refill"])
-            self._reset_seq_cache()
-            if self._since_refill >= self.refill_every:   # (written by an env with a longer refill period)
-                self.refill()
+        if self.supply is not None:
+            self._on_device()
+            self.supply.load_state(sd, self._stream_ptr())
         if plans is not None:
             log.buf.copy_(plans["log"])
         if "obs" in sd:
@@ -1222,13 +1057,7 @@ class BppVecEnv(BranchOps):
     def _rec_step_tensors(self, actions, sample=None, _host=None, _dropin=None, out=None):
         if self._first_reset:
             raise RuntimeError("call reset() before step()")
-        a = actions
-        if not torch.is_tensor(a):
-            a = torch.as_tensor(np.asarray(a))
-        if a.numel() != self.E:
-            raise ValueError("expected %d actions, got %d" % (self.E, a.numel()))
-        if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=torch.int64).contiguous()
+        a = self._actions(actions)
         self._on_device()
         log, sp = self._plog, self._stream_ptr()
         log.note(None, 0, a.data_ptr(), sp)

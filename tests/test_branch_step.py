@@ -310,7 +310,7 @@ def _gpu_assert_same_state(a, b, what):
     assert torch.equal(a.ep_acc, b.ep_acc), "ep_acc " + what
     if a._stream is not None:
         assert torch.equal(a.pool, b.pool), "ring " + what
-        assert torch.equal(a._mt, b._mt), "mt " + what
+        assert torch.equal(a.supply.mt, b.supply.mt), "mt " + what
         assert torch.equal(a.gen_next, b.gen_next), "gen_next " + what
 
 

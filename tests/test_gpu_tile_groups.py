@@ -199,7 +199,7 @@ def test_gpu_row_cache_kernel_under_tile_groups_matches_oracle(bpp, oracle, grou
     def front(sz, n, base, spec):
         assert spec["cache"]
         env = GpuKnobEnv(sz, n, base, spec)
-        assert env.env._seq_cache is not None
+        assert env.env.supply.seq_cache is not None
         return env
 
     knob_check(front, oracle, lambda **kw: bpp._lib.set_knobs(**kw), size, E, 12, 40, lambda t: 0, refill=4, gen=gen)

@@ -241,7 +241,7 @@ def test_gpu_counter_checkpoint_and_stream_identity():
     size, E = (10, 10, 10), 300
     spec = dict(bound=(2, 5), seed=5, depth=6, refill_every=3, rng="counter")
     env = bpp_amd.BppVecEnv(E, size, stream=spec)
-    assert tuple(env._mt.shape) == (E, 4)
+    assert tuple(env.supply.mt.shape) == (E, 4)
     env.reset()
     env.rollout_uniform(seed=3, step0=0, nsteps=17)
     ckpt = env.state_dict()

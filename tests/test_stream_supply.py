@@ -489,14 +489,14 @@ def test_gpu_two_streaming_envs_in_one_process_own_their_side_streams():
 
     a, b = make(1), make(2)
     both = drive([a, b])
-    assert a._side is not None and b._side is not None and a._side.value != b._side.value
+    assert a.supply.side is not None and b.supply.side is not None and a.supply.side.value != b.supply.side.value
     alone = drive([make(1)]) + drive([make(2)])
     for got, want in zip(both, alone):
         for x, y in zip(got, want):
             np.testing.assert_array_equal(x, y)
     assert int(both[0][1][:, 1].sum()) > 2048          # episodes went by
     a.close(), b.close()
-    assert a._side is None and b._side is None
+    assert a.supply.side is None and b.supply.side is None
 
 
 def test_emulated_row_cache_answers_the_look_aheads(emu, oracle):
@@ -549,7 +549,7 @@ def test_gpu_row_cache_on_equals_off_through_kernel_switches_clones_and_restores
     spec = dict(bound=(2, 5), seed=13, depth=12, refill_every=4, rng=gen)
     on = bpp_amd.BppVecEnv(E, size, enable_rotation=rot, stream=dict(spec, cache=True), env_id_base=7, env_id_total=7 + E)
     off = bpp_amd.BppVecEnv(E, size, enable_rotation=rot, stream=dict(spec, cache=False), env_id_base=7, env_id_total=7 + E)
-    assert on._seq_cache is not None and off._seq_cache is None
+    assert on.supply.seq_cache is not None and off.supply.seq_cache is None
     np.testing.assert_array_equal(on.reset().cpu().numpy(), off.reset().cpu().numpy())
     rng = np.random.RandomState(5)
     old = _lib.get_knobs()
