@@ -70,6 +70,12 @@ KFAC_INFO = ("D", "R", "tile", "rows_per_split", "splits", "chain")
 # include/bpp_policy.h: the same, for the CNNPro policy forward
 POLICY_SYMBOLS = ["bpp_policy_forward", "bpp_policy_forward_workspace", "bpp_policy_weights_floats", "bpp_policy_forward_info"]
 POLICY_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "bins_per_head_tile", "head_groups", "tile", "padded_rows", "path")
+# include/bpp_policy_train.h: the same, for the training pass of the CNNPro trunk
+POLICY_TRAIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy_train.h")
+POLICY_TRAIN_SYMBOLS = ["bpp_policy_trunk_forward_train", "bpp_policy_trunk_backward", "bpp_policy_trunk_backward_workspace",
+                        "bpp_policy_trunk_backward_weights_floats", "bpp_policy_trunk_backward_info"]
+POLICY_TRAIN_INFO = ("bins_per_group", "grad_lds_bytes", "bins_per_split", "splits", "chain_rows", "wgrad_lds_bytes", "path", "blocks")
+POLICY_TRUNK_FLOATS, POLICY_TRUNK_BWD_FLOATS = 151380, 148736
 # include/bpp_stream_kinds.h: the same, for the CUT-1 and RS ring refills
 STREAM_KIND_SYMBOLS = ["bpp_stream_refill_cut1", "bpp_stream_refill_rs", "bpp_stream_kinds_info", "bpp_rollout_uniform_stream_kind"]
 STREAM_KINDS = {"cut1": 1, "rs": 2}                  # BPP_STREAM_KIND_*
@@ -279,6 +285,23 @@ def bind_policy(L):
     return L
 
 
+def bind_policy_train(L):
+    """Argument types of the POLICY_TRAIN_SYMBOLS on library handle L."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    geom = ctypes.POINTER(i32)
+    L.bpp_policy_trunk_forward_train.argtypes = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp]
+    L.bpp_policy_trunk_forward_train.restype = ctypes.c_int
+    L.bpp_policy_trunk_backward.argtypes = [vp, ctypes.c_int64, i32, geom] + [vp] * 7 + [ctypes.c_size_t, vp]
+    L.bpp_policy_trunk_backward.restype = ctypes.c_int
+    L.bpp_policy_trunk_backward_workspace.argtypes = [geom, i32]
+    L.bpp_policy_trunk_backward_workspace.restype = ctypes.c_size_t
+    L.bpp_policy_trunk_backward_weights_floats.argtypes = [geom]
+    L.bpp_policy_trunk_backward_weights_floats.restype = ctypes.c_size_t
+    L.bpp_policy_trunk_backward_info.argtypes = [geom, i32, geom]
+    L.bpp_policy_trunk_backward_info.restype = ctypes.c_int
+    return L
+
+
 def bind_stream_kinds(L, batch=None, step_out=None, stream=None):
     """Argument types of the STREAM_KIND_SYMBOLS on library handle L (`batch`, `step_out`, `stream`: the ctypes classes of struct
     bpp_batch, bpp_step_out and bpp_stream)."""
@@ -437,6 +460,7 @@ def lib():
         bind_update(L)
         bind_kfac(L)
         bind_policy(L)
+        bind_policy_train(L)
         bind_stream_kinds(L)
         bind_placements(L)
         if L.bpp_abi_version() != ABI_VERSION:

@@ -43,6 +43,7 @@
 #include "../../include/bpp_update.h"
 #include "../../include/bpp_kfac.h"
 #include "../../include/bpp_policy.h"
+#include "../../include/bpp_policy_train.h"
 #include "../../include/bpp_stream_kinds.h"
 #include "../../include/bpp_placements.h"
 #include "../../include/bpp_gen.inl"
@@ -1639,4 +1640,5 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_update.inl"
 #include "bpp_kfac.inl"
 #include "bpp_policy.inl"
+#include "bpp_policy_train.inl"
 #include "bpp_placements.inl"

@@ -40,6 +40,7 @@ struct PolTrunkArgs {
     long long obs_stride;
     const float *w;
     float *feat;
+    float *acts;                          // training forward only (bpp_policy_train.inl): five arrays [n][64][A]
     PolShape s;
 };
 
@@ -143,7 +144,8 @@ __device__ __forceinline__ void policy_start(KfacAcc (&acc)[NB], const float *bi
 
 __device__ __forceinline__ int policy_slot_row(int s, int lane) { return (s & 3) + 8 * (s >> 2) + 4 * (lane >> 5); }
 
-// grid = ceil(n / P)
+// grid = ceil(n / P).  ACTS: every layer's ReLU output also goes to a.acts, copied from the image it was written to.
+template <bool ACTS>
 __global__ __launch_bounds__(256) void policy_trunk_kernel(PolTrunkArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const PolShape &s = a.s;
@@ -192,6 +194,13 @@ __global__ __launch_bounds__(256) void policy_trunk_kernel(PolTrunkArgs a) {
         float *t = src;
         src = dst;
         dst = t;
+        if (ACTS) {
+            float *out = a.acts + (size_t)layer * (size_t)s.n * (size_t)(kPolC * s.A);
+            for (int idx = tid; idx < s.P * kPolC * s.A; idx += 256) {
+                const int b = idx / (kPolC * s.A), rem = idx - b * (kPolC * s.A), c = rem / s.A, p = rem - c * s.A, y = p / s.S;
+                if (bin0 + b < s.n) out[(size_t)(bin0 + b) * (size_t)(kPolC * s.A) + (size_t)rem] = src[b * s.img + c * s.PP + y * s.PW + (p - y * s.S) + centre];
+            }
+        }
     }
     // the three 1x1 head convolutions as one product with 20 columns; dst is free now and collects [P][20 A]
     const float *w = a.w + s.w_head_conv, *bias = w + kPolC * kPolHeadC;
@@ -352,12 +361,12 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
     if (obs_stride < (int64_t)kPolIn * t.s.A) return ck.bad("obs_stride must be >= 4 A");
     const PolShape &s = t.s;
     const hipStream_t st = (hipStream_t)stream;
-    t.obs = obs, t.obs_stride = obs_stride, t.w = weights, t.feat = (float *)workspace;
+    t.obs = obs, t.obs_stride = obs_stride, t.w = weights, t.feat = (float *)workspace, t.acts = nullptr;
     if (s.trunk_lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_trunk_kernel, raised, kPolLdsBytes);
+        raise_dynamic_lds(policy_trunk_kernel<false>, raised, kPolLdsBytes);
     }
-    hipLaunchKernelGGL(policy_trunk_kernel, dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), (size_t)s.trunk_lds, st, t);
+    hipLaunchKernelGGL(policy_trunk_kernel<false>, dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), (size_t)s.trunk_lds, st, t);
     if (const int rc = launched()) return rc;
     PolHeadArgs h;
     h.feat = (const float *)workspace, h.w = weights, h.s = s, h.nheads = 0;

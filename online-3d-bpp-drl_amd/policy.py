@@ -6,9 +6,15 @@ workgroup, the Linear layers as products over 64 bins, float32 on the matrix cor
     value, logits, pred = policy(obs)                   # the callable ReorderSearch, MultiBinPacker and MCTSearch take
     value, action, log_prob = policy.act(obs, env.location_masks, deterministic=True)
 
-Inference only: nothing here computes a gradient.  Training runs on torch; `refresh(module)` repacks the weights after an
-optimizer step.  A bin's outputs are the same bits whatever batch it is evaluated in.  CPU tensors go through torch_forward, the
-same layers in plain torch.
+NativePolicy is inference only; `refresh(module)` repacks the weights after an optimizer step.  A bin's outputs are the same bits
+whatever batch it is evaluated in.  CPU tensors go through torch_forward, the same layers in plain torch.
+
+Training (include/bpp_policy_train.h): TrainablePolicy is the same network as an nn.Module whose five 3x3 layers
+and 1x1 head convolutions run forward and backward through the native trunk kernels (policy_trunk, an autograd Function); its
+Linear layers are torch.
+
+    net = bpp_amd.TrainablePolicy(10, env.action_space.n).to("cuda:0")
+    value, logits, pred = net(obs); loss.backward(); optimizer.step(); policy.refresh(net)
 """
 import ctypes
 
@@ -257,6 +263,255 @@ class NativePolicy:
         value, logits, _ = self(obs, want=("value", "logits"))
         action, logp = masked_act(logits, location_masks, deterministic=deterministic, **sampler)
         return value.reshape(-1, 1), action, logp
+
+
+# ------------------------------------------------------------------------------------------------- training (bpp_policy_train.h)
+HEAD_CONVS = ("base.actor.0", "base.mask.0", "base.critic.0")
+TRUNK_PARAMETERS = tuple(n + k for n in TRUNK + HEAD_CONVS for k in (".weight", ".bias"))        # the order policy_trunk takes
+TRUNK_FLOATS, TRUNK_BWD_FLOATS = _lib.POLICY_TRUNK_FLOATS, _lib.POLICY_TRUNK_BWD_FLOATS
+
+
+def pack_trunk(weights):
+    """The first 151 380 floats of pack_weights' blob -- share.0 .. share.8 and the head convolutions, all that the trunk
+    kernels read -- from plain tensors under the reference's names."""
+    parts = []
+    for names in [(n,) for n in TRUNK] + [HEAD_CONVS]:
+        w = torch.cat([weights[n + ".weight"].reshape(weights[n + ".weight"].shape[0], -1) for n in names], 0)
+        parts.extend([w.t().reshape(-1), torch.cat([weights[n + ".bias"].reshape(-1) for n in names], 0)])
+    return torch.cat([p.to(torch.float32) for p in parts], 0).contiguous()
+
+
+def pack_trunk_backward(weights):
+    """The float32 blob `weights_bwd` of bpp_policy_trunk_backward, from plain tensors under the reference's names: per layer
+    share.2 .. share.8 the matrix [k' = oc * 9 + i' * 3 + j'][c] = W[oc][c][2 - i'][2 - j'], then the head convolutions [h][c]."""
+    parts = [weights[n + ".weight"].flip(2, 3).permute(0, 2, 3, 1).reshape(-1) for n in TRUNK[1:]]
+    parts += [weights[n + ".weight"].reshape(-1) for n in HEAD_CONVS]
+    return torch.cat([p.to(torch.float32) for p in parts], 0).contiguous()
+
+
+def unpack_trunk_gradient(gw):
+    """{name: gradient in torch's shape} from bpp_policy_trunk_backward's grad_weights [151 380]: [OC][C][3][3] is a view of
+    [k][oc] transposed."""
+    out, at = {}, 0
+    for names, c, taps in [((n,), 4 if n == TRUNK[0] else 64, 3) for n in TRUNK] + [(HEAD_CONVS, 64, 1)]:
+        oc = 64 if taps == 3 else 20
+        k = c * taps * taps
+        w, b = gw[at:at + k * oc].reshape(k, oc).t(), gw[at + k * oc:at + (k + 1) * oc]
+        at += (k + 1) * oc
+        o = 0
+        for n in names:
+            m = 64 if taps == 3 else (4 if n == HEAD_CONVS[2] else 8)
+            out[n + ".weight"], out[n + ".bias"] = w[o:o + m].reshape(m, c, taps, taps), b[o:o + m]
+            o += m
+    return out
+
+
+def trunk_backward_info(geom, n, L=None):
+    """bpp_policy_trunk_backward_info as a dict (_lib.POLICY_TRAIN_INFO)."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check((L or _lib.lib()).bpp_policy_trunk_backward_info(_lib.kfac_geom(geom), int(n), out), L)
+    return dict(zip(_lib.POLICY_TRAIN_INFO, (int(v) for v in out)))
+
+
+def _check_obs(obs, S):
+    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
+        raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
+    if obs.device.type != "cuda":
+        raise RuntimeError("the native trunk needs its tensors on a HIP device")
+    n = int(obs.shape[0])
+    if obs.shape[1] < 4 * S * S or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * S * S):
+        raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * S * S))
+    return n, int(obs.stride(0)) if n > 1 else int(obs.shape[1])
+
+
+def trunk_forward_train(obs, blob, geom, feat=None, acts=None):
+    """(feat [n, 20 A], acts [5, n, 64, S, S]) from bpp_policy_trunk_forward_train: obs as policy_forward takes it, blob the
+    packed weights (pack_trunk's 151 380 floats, or the whole blob of pack_weights).  feat / acts: buffers to write into.  Only
+    enqueues on the current stream."""
+    S, H, M = (int(v) for v in geom)
+    n, stride = _check_obs(obs, S)
+    dev, A = obs.device, S * S
+    if not torch.is_tensor(blob) or blob.dtype != torch.float32 or blob.device != dev or not blob.is_contiguous() or blob.numel() < TRUNK_FLOATS:
+        raise ValueError("the weights must be a packed float32 blob of at least %d floats on %s" % (TRUNK_FLOATS, dev))
+    feat = torch.empty((n, 20 * A), dtype=torch.float32, device=dev) if feat is None else feat
+    acts = torch.empty((5, n, 64, S, S), dtype=torch.float32, device=dev) if acts is None else acts
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().bpp_policy_trunk_forward_train(obs.data_ptr(), stride, n, _lib.kfac_geom((S, H, M)), blob.data_ptr(), feat.data_ptr(),
+                                                             acts.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return feat, acts
+
+
+def trunk_backward(obs, geom, blob_bwd, feat, acts, grad_feat, grads=None, grad_weights=None, workspace=None):
+    """(grads [5 n 64 A + n 20 A] flat: G_1 .. G_5 then gf', grad_weights [151 380]) from bpp_policy_trunk_backward.  grads /
+    grad_weights / workspace: buffers to use (workspace: float32, at least bpp_policy_trunk_backward_workspace bytes)."""
+    S, H, M = (int(v) for v in geom)
+    n, stride = _check_obs(obs, S)
+    dev, A = obs.device, S * S
+    g = _lib.kfac_geom((S, H, M))
+    L = _lib.lib()
+    for name, t, numel in (("blob_bwd", blob_bwd, TRUNK_BWD_FLOATS), ("feat", feat, n * 20 * A), ("acts", acts, 5 * n * 64 * A),
+                           ("grad_feat", grad_feat, n * 20 * A)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError("%s must be a contiguous float32 tensor of %d elements on %s" % (name, numel, dev))
+    need = int(L.bpp_policy_trunk_backward_workspace(g, n))
+    if need == 0:
+        _lib.check(L.bpp_policy_trunk_backward_info(g, n, (ctypes.c_int32 * 8)()))
+    grads = torch.empty(n * (5 * 64 + 20) * A, dtype=torch.float32, device=dev) if grads is None else grads
+    grad_weights = torch.empty(TRUNK_FLOATS, dtype=torch.float32, device=dev) if grad_weights is None else grad_weights
+    workspace = torch.empty(need // 4, dtype=torch.float32, device=dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.bpp_policy_trunk_backward(obs.data_ptr(), stride, n, g, blob_bwd.data_ptr(), feat.data_ptr(), acts.data_ptr(),
+                                               grad_feat.data_ptr(), grads.data_ptr(), grad_weights.data_ptr(), workspace.data_ptr(),
+                                               workspace.numel() * 4, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return grads, grad_weights
+
+
+class _TrunkBuffers:
+    """What one (n, device, side) needs between a forward and its backward passes, and both blobs with the parameter versions
+    they were packed from."""
+
+    def __init__(self):
+        self.versions = self.blob = self.blob_bwd = self.acts = self.grads = self.workspace = None
+        self.forwards = 0
+
+
+_TRUNK_BUFFERS = {}     # (n, device, side) -> _TrunkBuffers: policy_trunk's default cache (a module brings its own)
+
+
+def clear_trunk_buffers():
+    """Release what policy_trunk's default cache holds (activations, gradients, workspace, blobs of every batch size seen)."""
+    _TRUNK_BUFFERS.clear()
+
+
+class _PolicyTrunk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, obs, side, cache, keep, *params):
+        S = int(side)
+        if len(params) != len(TRUNK_PARAMETERS):
+            raise ValueError("policy_trunk takes the %d tensors of TRUNK_PARAMETERS" % len(TRUNK_PARAMETERS))
+        n = int(obs.shape[0])
+        key = (n, obs.device, S)
+        buf = cache.get(key)
+        if buf is None:
+            buf = cache[key] = _TrunkBuffers()
+        versions = tuple((p.data_ptr(), p._version) for p in params)
+        if buf.versions != versions:
+            plain = {name: p.detach() for name, p in zip(TRUNK_PARAMETERS, params)}
+            buf.blob, buf.blob_bwd, buf.versions = pack_trunk(plain), pack_trunk_backward(plain), versions
+        geom = (S, HIDDEN_STEP, S * S)          # H and M do not enter the trunk
+        if not keep:                                # nothing will be differentiated: the kept activations stay as they are
+            return trunk_forward_train(obs, buf.blob, geom)[0]
+        if buf.acts is None:
+            A = S * S
+            need = int(_lib.lib().bpp_policy_trunk_backward_workspace(_lib.kfac_geom(geom), n))
+            buf.acts = torch.empty((5, n, 64, S, S), dtype=torch.float32, device=obs.device)
+            buf.grads = torch.empty(n * (5 * 64 + 20) * A, dtype=torch.float32, device=obs.device)
+            buf.workspace = torch.empty(max(1, need // 4), dtype=torch.float32, device=obs.device)
+        feat, _ = trunk_forward_train(obs, buf.blob, geom, acts=buf.acts)
+        ctx.save_for_backward(obs, feat)
+        buf.forwards += 1
+        ctx.buf, ctx.geom, ctx.blob_bwd, ctx.stamp = buf, geom, buf.blob_bwd, buf.forwards
+        return feat
+
+    @staticmethod
+    def backward(ctx, grad_feat):
+        obs, feat = ctx.saved_tensors
+        buf = ctx.buf
+        if buf.forwards != ctx.stamp:
+            raise RuntimeError("policy_trunk: another forward of the same batch size has overwritten the activations of this graph")
+        _, gw = trunk_backward(obs, ctx.geom, ctx.blob_bwd, feat, buf.acts, grad_feat.contiguous(), grads=buf.grads, workspace=buf.workspace)
+        named = unpack_trunk_gradient(gw)
+        return (None,) * 4 + tuple(named[name] if ctx.needs_input_grad[4 + i] else None for i, name in enumerate(TRUNK_PARAMETERS))
+
+
+def policy_trunk(obs, trunk_parameters, side, cache=None):
+    """feat [n, 20 A] = the head features of CNNPro's trunk (five 3x3 layers, three 1x1 head convolutions, all with ReLU) for
+    obs float32 [n, >= 4 A] on a HIP device, differentiable with respect to trunk_parameters: the 16 tensors of TRUNK_PARAMETERS
+    (a dict under those names, or a sequence in that order), in torch's shapes.  Forward and backward are the native calls of
+    include/bpp_policy_train.h; no gradient is computed with respect to obs, and an obs that requires one is refused.
+
+    The activations of a forward are kept per (n, device, side) until the next differentiable forward of the same key:
+    backward passes over one graph may be repeated (retain_graph=True) and give the same bits, a backward after a newer such
+    forward is refused.  A forward under no_grad, or with no parameter that requires grad, keeps nothing and disturbs nothing.
+    The buffers (activations 5 n 64 A floats, gradients slightly more, the workspace, both blobs, re-packed when a parameter's
+    version changes) live in `cache`, a dict the caller owns -- TrainablePolicy gives its own, so they go with the module; the
+    default is one dict for the process, which clear_trunk_buffers() empties.  Callers with different parameters that share a
+    cache re-pack the blobs at every alternation: give each its own."""
+    if torch.is_tensor(obs) and obs.requires_grad:
+        raise ValueError("policy_trunk computes no gradient with respect to obs: pass obs.detach()")
+    if isinstance(trunk_parameters, dict):
+        trunk_parameters = [trunk_parameters[name] for name in TRUNK_PARAMETERS]
+    S = int(side)
+    if not 1 <= S <= MAX_SIDE:
+        raise ValueError("side must lie in 1 .. %d: the two LDS images of a bin must fit" % MAX_SIDE)
+    obs = obs.reshape(obs.shape[0], -1) if obs.dim() != 2 else obs
+    _check_obs(obs, S)
+    keep = torch.is_grad_enabled() and any(p.requires_grad for p in trunk_parameters)
+    return _PolicyTrunk.apply(obs, S, _TRUNK_BUFFERS if cache is None else cache, keep, *trunk_parameters)
+
+
+class TrainablePolicy(torch.nn.Module):
+    """The reference's Policy(CNNPro) for training: parameters under the reference's names (`base.share.0.weight` ...
+    `dist.linear.bias`), the trunk and the head convolutions through policy_trunk, the Linear layers in torch.
+    forward(obs) -> (value [n], logits [n, M], pred [n, M]) as NativePolicy returns them.  On CPU tensors the forward is
+    torch_forward on the same parameters (no native code, for inspection only)."""
+
+    def __init__(self, side, n_actions, hidden=256):
+        super().__init__()
+        NativePolicy(side, n_actions, hidden)                 # its refusals
+        self._trunk_cache = {}                                # policy_trunk's buffers, per batch size: released with the module
+        self.side, self.n_actions, self.hidden = int(side), int(n_actions), int(hidden)
+        relu = torch.nn.init.calculate_gain("relu")
+        for name, shape in layer_shapes(self.side, self.hidden, self.n_actions):
+            at = self
+            for part in name.split("."):                      # plain containers: only the names matter
+                if part not in at._modules:
+                    at.add_module(part, torch.nn.Module())
+                at = at._modules[part]
+            w = torch.empty(shape)
+            torch.nn.init.orthogonal_(w, gain=0.01 if name == "dist.linear" else relu)     # acktr/model.py:268, distributions.py:65
+            at.weight, at.bias = torch.nn.Parameter(w), torch.nn.Parameter(torch.zeros(shape[0]))
+
+    def named_weights(self):
+        """{reference name: parameter}"""
+        return dict(self.named_parameters())
+
+    def release_buffers(self):
+        """Drop the activations, gradients and workspaces kept for the batch sizes seen so far (21 GB at n = 65 536)."""
+        self._trunk_cache.clear()
+
+    def load_state_dict(self, state, strict=True, assign=False):
+        """A state dict in any of the three forms plain_weights takes (the reference's names, the K-FAC-split checkpoint form,
+        kfac.plain_state_dict's output), not only this module's own.  Every layer must be there whatever `strict` says
+        (ValueError otherwise, as NativePolicy.load_state_dict raises); strict=True also refuses a key that names no layer.
+        Returns nn.Module's (missing_keys, unexpected_keys) result; `assign` is not supported."""
+        if assign:
+            raise ValueError("TrainablePolicy.load_state_dict copies into its parameters: assign=True is not supported")
+        plain = plain_weights(state, self.side, self.hidden, self.n_actions)
+        known = {k.replace("module.", "").replace("add_bias.", "").replace("_bias", "bias"): k for k in state}
+        unexpected = [k for name, k in known.items() if name not in plain]
+        if strict and unexpected:
+            raise RuntimeError("unexpected key(s) in state_dict: %s" % ", ".join(sorted(unexpected)))
+        with torch.no_grad():
+            for name, p in self.named_weights().items():
+                p.copy_(plain[name].to(p.device))
+        return torch.nn.modules.module._IncompatibleKeys([], unexpected)
+
+    def forward(self, obs):
+        w = self.named_weights()
+        obs = obs.reshape(obs.shape[0], -1) if obs.dim() != 2 else obs
+        if obs.device.type != "cuda":
+            return torch_forward(w, obs.to(torch.float32))
+        A = self.side ** 2
+        feat = policy_trunk(obs if obs.dtype == torch.float32 else obs.to(torch.float32), w, self.side, cache=self._trunk_cache)
+
+        def head(name, lo, hi):
+            return F.relu(F.linear(feat[:, lo * A:hi * A], w[name + ".3.weight"], w[name + ".3.bias"]))
+
+        value = F.linear(head("base.critic", 16, 20), w["base.critic_linear.weight"], w["base.critic_linear.bias"]).reshape(-1)
+        logits = F.linear(head("base.actor", 0, 8), w["dist.linear.weight"], w["dist.linear.bias"])
+        pred = F.relu(F.linear(head("base.mask", 8, 16), w["base.mask.5.weight"], w["base.mask.5.bias"]))
+        return value, logits, pred
 
 
 def _numel(shape):
