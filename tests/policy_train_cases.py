@@ -1,7 +1,9 @@
 """Shared cases of the trunk-training tests (tests/test_policy_train.py on the emulator, tests/test_gpu_policy_train.py on the
 device): exact-integer networks whose forward, input gradients and weight gradients are known in int64, real-valued networks with
-a float64 torch autograd reference, and the runners that call bpp_policy_trunk_forward_train and bpp_policy_trunk_backward
-(include/bpp_policy_train.h) with host or device pointers.  The forward-side helpers are those of tests/policy_cases.py."""
+a float64 torch autograd reference, the header's arithmetic stated in numpy (fma32, normative) with the cases whose bits are
+recorded in tests/golden/trunk_train_chain_bits.npz, the split identity, and the runners that call
+bpp_policy_trunk_forward_train and bpp_policy_trunk_backward (include/bpp_policy_train.h) with host or device pointers, plain
+or into guarded buffers.  The forward-side helpers are those of tests/policy_cases.py."""
 import ctypes
 
 import numpy as np
@@ -118,7 +120,7 @@ def exact_case(S, n, seed, stride=None, taps=3, density=None):
     border = np.ones((S, S), bool)
     border[1:-1, 1:-1] = False
     img[:, :, border] = np.maximum(img[:, :, border], 1)
-    obs = np.full((n, stride), 7.0, np.float32)
+    obs = np.full((n, stride), np.nan, np.float32)          # the padding of a row: one stray read of it and an output is NaN
     obs[:, :4 * A] = img.reshape(n, 4 * A)
     shapes = pol.layer_shapes(S, H, A)[:8]
     w = {}
@@ -194,9 +196,9 @@ def exact_case(S, n, seed, stride=None, taps=3, density=None):
 
 def exact_spec(L, name):
     """The arguments of exact_case for EXACT_SPECS[name] under library handle L's own P and bins per split."""
-    S, nf, seed, taps = EXACT_SPECS[name]
+    S, nf, seed, taps, pad = EXACT_SPECS[name]
     i = info(L, geom_of(S), 1)
-    return dict(S=S, n=nf(i["bins_per_group"], i["bins_per_split"]), seed=seed, taps=taps)
+    return dict(S=S, n=nf(i["bins_per_group"], i["bins_per_split"]), seed=seed, taps=taps, stride=4 * S * S + pad if pad else None)
 
 
 def check_exact(run, case):
@@ -206,13 +208,24 @@ def check_exact(run, case):
     return got
 
 
-# name -> (side, n as a function of (bins per input-gradient workgroup P, bins per split B) of that side, seed, taps per channel)
+# name -> (side, n as a function of (bins per input-gradient workgroup P, bins per split B) of that side, seed, taps per channel,
+# floats of NaN padding behind the 4 A of an obs row: obs_stride = 4 A + padding)
 EXACT_SPECS = {
-    "s10_n1": (10, lambda P, B: 1, 1, 3), "s10_nP1": (10, lambda P, B: P + 1, 2, 3), "s10_n5": (10, lambda P, B: 5, 3, 3),
-    "s5_n2": (5, lambda P, B: 2, 4, 3), "s5_three_splits": (5, lambda P, B: 2 * B + 1, 5, 3),
-    "s3_n3": (3, lambda P, B: 3, 6, 3), "s1_n3": (1, lambda P, B: 3, 7, 20),       # A = 1: only the centre taps count, so more of them
-    "s11_n3": (11, lambda P, B: 3, 8, 3), "s15_n2": (15, lambda P, B: 2, 9, 3),
+    "s10_n1": (10, lambda P, B: 1, 1, 3, 0), "s10_nP1": (10, lambda P, B: P + 1, 2, 3, 0), "s10_n5": (10, lambda P, B: 5, 3, 3, 0),
+    "s5_n2": (5, lambda P, B: 2, 4, 3, 0), "s5_three_splits": (5, lambda P, B: 2 * B + 1, 5, 3, 0),
+    "s3_n3": (3, lambda P, B: 3, 6, 3, 0), "s1_n3": (1, lambda P, B: 3, 7, 20, 0),       # A = 1: only the centre taps count, so more of them
+    "s11_n3": (11, lambda P, B: 3, 8, 3, 0), "s15_n2": (15, lambda P, B: 2, 9, 3, 0),
+    # every other side the header accepts; the 64-bin cap on a split (S <= 4) and the shipped 10 x 10 over more than one split;
+    # padded rows of obs
+    "s2_three_splits": (2, lambda P, B: 2 * B + 1, 20, 3, 3), "s3_three_splits": (3, lambda P, B: 2 * B + 1, 20, 3, 0),
+    "s4_nP1": (4, lambda P, B: P + 1, 20, 3, 5), "s4_two_splits": (4, lambda P, B: B + 1, 20, 3, 0),
+    "s6_nP1": (6, lambda P, B: P + 1, 20, 3, 0), "s7_nP1": (7, lambda P, B: P + 1, 20, 3, 1), "s8_nP1": (8, lambda P, B: P + 1, 20, 3, 0),
+    "s9_nP1": (9, lambda P, B: P + 1, 20, 3, 0), "s12_n2": (12, lambda P, B: 2, 20, 3, 7), "s13_n2": (13, lambda P, B: 2, 20, 3, 0),
+    "s14_n2": (14, lambda P, B: 2, 20, 3, 0), "s10_two_splits": (10, lambda P, B: B + 1, 20, 3, 9),
 }
+# name -> (splits, bins of the last split) of the cases that are there for their splits
+EXACT_SPLITS = {"s5_three_splits": (3, 1), "s2_three_splits": (3, 1), "s3_three_splits": (3, 1), "s4_two_splits": (2, 1),
+                "s10_two_splits": (2, 1)}
 
 
 # ----------------------------------------------------------------------------------------------------------------- real cases
@@ -287,3 +300,282 @@ def check_gradients(mine, ref64, ref32, label=""):
     for k, (e_native, e_torch) in figures.items():
         assert e_torch > 0 and e_native <= pc.FACTOR * e_torch, (label, k, e_native, e_torch)
     return figures
+
+
+# ------------------------------------------------------------- the header's arithmetic in numpy (include/bpp_policy_train.h)
+def fma32(a, b, c):
+    """The exactly rounded float32 fused multiply-add float32(a * b + c) of float32 arrays, as libm's fmaf gives it.  In
+    float64 the product of two float32 is exact (24 + 24 bits); TwoSum gives the error of the float64 sum s = p + c exactly;
+    where that error is not zero and s is even, s moves one float64 towards the error's side, which rounds the true sum to odd
+    at 53 bits; a value rounded to odd at 24 + 2 bits or more rounds to float32 as the true sum does."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    t = s - p
+    err = (p - (s - t)) + (c - t)
+    fix = (err != 0) & ((s.view(np.int64) & 1) == 0) & np.isfinite(s)
+    s = np.where(fix, np.where(err > 0, np.nextafter(s, np.inf), np.nextafter(s, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def header_bins_per_split(S):
+    """`bins per split` as DESIGN.md 3.15 states it: clamp(1024 / A, 1, 64), a function of the geometry alone."""
+    return max(1, min(64, 1024 // (S * S)))
+
+
+def _pad1(x):
+    return np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)))
+
+
+def _relu32(x):
+    return np.where(x > 0, x, np.float32(0)).astype(np.float32)
+
+
+def normative(plain, obs, grad_feat, S, bins_per_split):
+    """{feat [n, 20, A], acts [5, n, 64, A], grads [5, n, 64, A], gf [n, 20, A], gw [151380]} as include/bpp_policy.h and
+    include/bpp_policy_train.h state them, one fma32 per step of every chain, in plain numpy: no convolution of torch and
+    nothing of the emulator.
+      forward   every output element one chain from the bias over ascending k = c * 9 + i * 3 + j (the head convolutions over c)
+      gf'       grad_feat where feat > 0
+      D_5       one chain over h = 0 .. 19 from +0;  G_l = acts_l > 0 ? D_l : 0
+      D_{l-1}   one chain over ascending k' = oc * 9 + i' * 3 + j' from +0 on W[oc][c][2 - i'][2 - j']
+      dW_l      per split of `bins_per_split` consecutive bins one chain per element [k][oc] from +0 over ascending (b, p), the
+                bias a row of the patch with the value 1; the splits are added in split order in float64 and cast once
+    gw is packed with pol.pack_trunk."""
+    w = {k: np.asarray(v, np.float32) for k, v in plain.items()}
+    n, A, B = obs.shape[0], S * S, int(bins_per_split)
+    x = np.ascontiguousarray(obs[:, :4 * A], np.float32).reshape(n, 4, S, S)
+    inputs, acts = [], []
+    for name in pol.TRUNK:
+        W, bias = w[name + ".weight"], w[name + ".bias"]
+        inputs.append(x)
+        xp = _pad1(x)
+        acc = np.broadcast_to(bias[None, :, None, None], (n, 64, S, S)).astype(np.float32)
+        for c in range(W.shape[1]):
+            for i in range(3):
+                for j in range(3):
+                    acc = fma32(xp[:, c, None, i:i + S, j:j + S], W[None, :, c, i, j, None, None], acc)
+        x = _relu32(acc)
+        acts.append(x)
+    Wh = np.concatenate([w[nm + ".weight"] for nm in pol.HEAD_CONVS], 0)[:, :, 0, 0]
+    bh = np.concatenate([w[nm + ".bias"] for nm in pol.HEAD_CONVS], 0)
+    acc = np.broadcast_to(bh[None, :, None, None], (n, 20, S, S)).astype(np.float32)
+    for c in range(64):
+        acc = fma32(x[:, c, None], Wh[None, :, c, None, None], acc)
+    feat = _relu32(acc)
+    gf = np.where(feat > 0, np.asarray(grad_feat, np.float32).reshape(feat.shape), np.float32(0)).astype(np.float32)
+    d = np.zeros((n, 64, S, S), np.float32)
+    for h in range(20):
+        d = fma32(gf[:, h, None], Wh[None, h, :, None, None], d)
+    G = [None] * 5
+    for l in range(4, -1, -1):
+        G[l] = np.where(acts[l] > 0, d, np.float32(0)).astype(np.float32)
+        if l == 0:
+            break
+        W, gp, d = w[pol.TRUNK[l] + ".weight"], _pad1(G[l]), np.zeros((n, 64, S, S), np.float32)
+        for oc in range(64):
+            for i in range(3):
+                for j in range(3):
+                    d = fma32(gp[:, oc, None, i:i + S, j:j + S], W[None, oc, :, 2 - i, 2 - j, None, None], d)
+
+    def wgrad(xin, g, taps):
+        """xin [n, C, S, S], g [n, OC, S, S] -> (dW [OC, C, taps, taps], db [OC])"""
+        C, OC = xin.shape[1], g.shape[1]
+        xp = _pad1(xin) if taps == 3 else xin
+        total = np.zeros((C * taps * taps + 1, OC), np.float64)
+        for b0 in range(0, n, B):
+            acc = np.zeros((C * taps * taps + 1, OC), np.float32)
+            for b in range(b0, min(n, b0 + B)):
+                for y in range(S):
+                    for xx in range(S):
+                        patch = np.append(xp[b, :, y:y + taps, xx:xx + taps].reshape(-1), np.float32(1))
+                        acc = fma32(patch[:, None], g[b, None, :, y, xx], acc)
+            total = total + acc.astype(np.float64)
+        total = total.astype(np.float32)
+        return total[:-1].T.reshape(OC, C, taps, taps), total[-1]
+
+    grad = {}
+    for l, name in enumerate(pol.TRUNK):
+        grad[name + ".weight"], grad[name + ".bias"] = wgrad(inputs[l], G[l], 3)
+    dwh, dbh = wgrad(acts[4], gf, 1)
+    o = 0
+    for nm in pol.HEAD_CONVS:
+        m = w[nm + ".weight"].shape[0]
+        grad[nm + ".weight"], grad[nm + ".bias"] = dwh[o:o + m], dbh[o:o + m]
+        o += m
+    gw = pol.pack_trunk({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in grad.items()}).numpy()
+    return dict(feat=feat.reshape(n, 20, A), acts=np.stack(acts).reshape(5, n, 64, A), grads=np.stack(G).reshape(5, n, 64, A),
+                gf=gf.reshape(n, 20, A), gw=gw)
+
+
+# ---- the recorded bits of that reference on real-valued data (tests/golden/make_trunk_train_chain_bits.py) -------------------
+TRAIN_CHAIN_FIXTURE = "trunk_train_chain_bits"
+# (S, n) -> (splits, bins of the last split, bins per input-gradient workgroup): one split and P = 2 with an absent bin; three
+# splits under the 64-bin cap with a last split of 2 bins, even A; two splits, odd A; the shipped geometry in splits of 10 and
+# 1; P = 1 with both LDS budgets near their limit
+TRAIN_CHAIN_CASES = {(5, 3): (1, 3, 2), (2, 130): (3, 2, None), (3, 66): (2, 2, None), (10, 11): (2, 1, 2), (15, 1): (1, 1, 1)}
+TRAIN_CHAIN_INPUTS = ("obs", "blob", "blob_bwd", "grad_feat")
+SAMPLE = 2048           # floats of an output kept in the fixture beside the CRC32 of all of them
+
+
+def train_chain_name(S, n):
+    return "trunk_s%d_n%d" % (S, n)
+
+
+def train_chain_case(S, n, seed=7):
+    """dict(geom, obs, plain, blob, blob_bwd, grad_feat) from numpy.random.RandomState alone (pc.chain_case: weights normal *
+    sqrt(2 / fan_in), biases uniform in +-0.1, the states of pc.synthetic_states), the gradient at feat standard normal."""
+    base = pc.chain_case(S, H, S * S, n, seed)
+    plain = {k: v for k, v in base["plain"].items() if k in pol.TRUNK_PARAMETERS}
+    assert all(float(v.abs().min()) > 0 for k, v in plain.items() if k.endswith(".bias"))
+    grad_feat = np.random.RandomState(seed + 1000).standard_normal((n, 20 * S * S)).astype(np.float32)
+    blob, blob_bwd = blobs(plain)
+    return dict(geom=geom_of(S), obs=base["obs"], plain=plain, blob=blob, blob_bwd=blob_bwd, grad_feat=grad_feat)
+
+
+def sample_step(size):
+    """The smallest odd step (coprime to 64, so that no lane, tile slot or channel is passed over) that leaves at most SAMPLE."""
+    return -(-size // SAMPLE) | 1
+
+
+def train_chain_entries(case, outputs, name):
+    """{key: array} of one case for the fixture: a CRC32 of each input; per output a CRC32 of all its bits and every
+    sample_step-th of them."""
+    out = {"%s.crc.%s" % (name, k): pc.crc(np.ascontiguousarray(case[k], np.float32)) for k in TRAIN_CHAIN_INPUTS}
+    for key in OUTPUTS:
+        bits = np.ascontiguousarray(outputs[key], np.float32).reshape(-1).view(np.uint32)
+        out["%s.%s.crc" % (name, key)] = pc.crc(bits)
+        out["%s.%s.sample" % (name, key)] = bits[::sample_step(bits.size)].copy()
+    return out
+
+
+def check_train_chain(got, fixture, name, label=""):
+    """Every output of `got` against the recorded reference: the CRC32 of all its bits.  Where one differs, the largest distance
+    in ulps over the recorded sample is printed and reported for every output before the assertion."""
+    report = {}
+    for key in OUTPUTS:
+        bits = np.ascontiguousarray(got[key], np.float32).reshape(-1).view(np.uint32)
+        sample, want = fixture["%s.%s.sample" % (name, key)], fixture["%s.%s.crc" % (name, key)]
+        mine = bits[::sample_step(bits.size)]
+        assert mine.shape == sample.shape, (name, key, mine.shape, sample.shape)
+        report[key] = dict(crc_equal=bool(pc.crc(bits) == want), sampled=int(sample.size), sampled_differing=int((mine != sample).sum()),
+                           largest_ulps_in_sample=pc.ulps(mine, sample))
+    print(label, name, report)
+    assert all(r["crc_equal"] for r in report.values()), (label, name, report)
+
+
+def load_fixture(name):
+    import os
+    return np.load(os.path.join(pc.ROOT, "tests", "golden", name + ".npz"))
+
+
+# ------------------------------------------------------------------------------------------------------------ the split identity
+def check_split_identity(run, case, B):
+    """gw of the whole batch == float32(the float64 sum, in split order, of the gw of every split run as a call of its own), bit
+    for bit over all 151 380 floats; every split's rows of feat, acts, grads and gf are the whole batch's; and the float32
+    running sum of the same parts does NOT give those bits, so the comparison can tell a float reduce from the stated one.
+    Returns the number of floats in which the float32 sum differs."""
+    n = case["obs"].shape[0]
+    args = lambda lo, hi: (case["obs"][lo:hi], case["geom"], case["blob"], case["blob_bwd"], case["grad_feat"][lo:hi])       # noqa: E731
+    whole = run(*args(0, n))
+    sum64, sum32 = np.zeros(pol.TRUNK_FLOATS, np.float64), np.zeros(pol.TRUNK_FLOATS, np.float32)
+    assert n > 2 * B, (n, B)
+    for b0 in range(0, n, B):
+        part = run(*args(b0, b0 + B))
+        for key in ("feat", "gf"):
+            assert pc.same_bits(part[key], whole[key][b0:b0 + B]), (key, b0)
+        for key in ("acts", "grads"):
+            assert pc.same_bits(part[key], whole[key][:, b0:b0 + B]), (key, b0)
+        sum64 = sum64 + part["gw"].astype(np.float64)
+        sum32 = sum32 + part["gw"]
+    differing = int((sum64.astype(np.float32).view(np.uint32) != whole["gw"].view(np.uint32)).sum())
+    assert differing == 0, "gw of the whole batch differs from the double sum of its splits in %d floats, %d ulps at most" % (
+        differing, pc.ulps(sum64.astype(np.float32), whole["gw"]))
+    in_float = int((sum32.view(np.uint32) != whole["gw"].view(np.uint32)).sum())
+    assert in_float > 0, "a float32 sum of the splits gives the same bits: this case cannot tell the two reduces apart"
+    return in_float
+
+
+# --------------------------------------------------------------------------------------------------------------- guarded buffers
+GUARD, WS_TAIL = 1024, 4096                       # floats before and after every output; floats of workspace beyond the stated bytes
+GUARD_BITS, NAN_BITS = np.uint32(0x5A5A5A5A), np.float32(np.nan).view(np.uint32)
+
+
+def guarded_buffers(S, n, ws_floats):
+    """{name: uint32 [GUARD + size + tail]} for feat, acts, grads, gw and the workspace: GUARD_BITS everywhere, NaN in the
+    `size` floats a call may write.  The tail is GUARD floats, and WS_TAIL more behind the workspace."""
+    A = S * S
+    sizes = dict(feat=n * 20 * A, acts=5 * n * 64 * A, grads=n * (5 * 64 + 20) * A, gw=pol.TRUNK_FLOATS, ws=ws_floats)
+    bufs = {}
+    for k, size in sizes.items():
+        bufs[k] = np.full(GUARD + size + GUARD + (WS_TAIL if k == "ws" else 0), GUARD_BITS, np.uint32)
+        bufs[k][GUARD:GUARD + size] = NAN_BITS
+    return bufs, sizes
+
+
+def inactive_tiles(blocks):
+    """bool [blocks, 4]: the 32 x 32 tiles of the weight-gradient kernel's 64-row blocks with no row below K + 1 or no column
+    below OC (csrc/bpp_policy_train.inl: such a tile `does nothing and writes nothing`)."""
+    out = []
+    for rows, oc in [(37, 64)] + [(577, 64)] * 4 + [(65, 20)]:
+        for f0 in range(0, rows, 64):
+            out.append([not (f0 + 32 * (wave >> 1) < rows and 32 * (wave & 1) < oc) for wave in range(4)])
+    assert len(out) == blocks, (len(out), blocks)
+    return np.array(out)
+
+
+def check_guards(bufs, sizes, splits, blocks):
+    """After a forward and a backward into guarded_buffers: every guard float and the workspace beyond the stated bytes still
+    hold GUARD_BITS, no output holds a NaN, and the workspace tiles of inactive waves were not stored to.  Returns the outputs
+    as split_outputs gives them (views of bufs)."""
+    for k, size in sizes.items():
+        for what, part in (("before", bufs[k][:GUARD]), ("behind", bufs[k][GUARD + size:])):
+            assert (part == GUARD_BITS).all(), "%d floats %s %s were written" % (int((part != GUARD_BITS).sum()), what, k)
+        if k != "ws":
+            assert not np.isnan(bufs[k][GUARD:GUARD + size].view(np.float32)).any(), "%s: not every float was written" % k
+    assert sizes["ws"] == splits * blocks * 4096
+    tiles = bufs["ws"][GUARD:GUARD + sizes["ws"]].reshape(splits, blocks, 4, 1024)
+    idle = inactive_tiles(blocks)
+    assert idle.sum() == 4 * 2 + 5 and (tiles[:, idle] == NAN_BITS).all() and not np.isnan(tiles[:, ~idle].view(np.float32)).any()
+    return {k: bufs[k][GUARD:GUARD + sizes[k]].view(np.float32) for k in ("feat", "acts", "grads", "gw")}
+
+
+def guarded_host_runner(L):
+    """host_runner with every output and the workspace carved out of guarded_buffers, checked by check_guards."""
+    def run(obs, geom, blob, blob_bwd, grad_feat):
+        obs = np.ascontiguousarray(obs, np.float32)
+        n, stride = obs.shape
+        g = pc.geom_arg(geom)
+        blob, blob_bwd = np.ascontiguousarray(blob, np.float32), np.ascontiguousarray(blob_bwd, np.float32)
+        grad_feat = np.ascontiguousarray(grad_feat, np.float32)
+        bytes_ = L.bpp_policy_trunk_backward_workspace(g, n)
+        bufs, sizes = guarded_buffers(geom[0], n, bytes_ // 4)
+        at = {k: v[GUARD:].ctypes.data for k, v in bufs.items()}
+        rc = L.bpp_policy_trunk_forward_train(obs.ctypes.data, stride, n, g, blob.ctypes.data, at["feat"], at["acts"], None)
+        assert rc == 0, (rc, L.bpp_last_error())
+        rc = L.bpp_policy_trunk_backward(obs.ctypes.data, stride, n, g, blob_bwd.ctypes.data, at["feat"], at["acts"], grad_feat.ctypes.data,
+                                         at["grads"], at["gw"], at["ws"], bytes_, None)
+        assert rc == 0, (rc, L.bpp_last_error())
+        i = info(L, geom, n)
+        return split_outputs(geom[0], n, **check_guards(bufs, sizes, i["splits"], i["blocks"]))
+    return run
+
+
+def guarded_device_runner(L, device="cuda:0"):
+    """device_runner with every output and the workspace a slice of a larger device tensor filled as guarded_buffers fills it;
+    workspace_bytes is what bpp_policy_trunk_backward_workspace states.  L: the product library, for the sizes."""
+    def run(obs, geom, blob, blob_bwd, grad_feat):
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)        # noqa: E731
+        o = dev(obs)
+        n, S = o.shape[0], geom[0]
+        bufs, sizes = guarded_buffers(S, n, L.bpp_policy_trunk_backward_workspace(pc.geom_arg(geom), n) // 4)
+        whole = {k: torch.from_numpy(v.view(np.float32)).to(device) for k, v in bufs.items()}
+        t = {k: v[GUARD:GUARD + sizes[k]] for k, v in whole.items()}
+        pol.trunk_forward_train(o, dev(blob), geom, feat=t["feat"].view(n, -1), acts=t["acts"].view(5, n, 64, S, S))
+        pol.trunk_backward(o, geom, dev(blob_bwd), t["feat"].view(n, -1), t["acts"].view(5, n, 64, S, S), dev(grad_feat), grads=t["grads"],
+                           grad_weights=t["gw"], workspace=t["ws"])
+        torch.cuda.synchronize()
+        bufs = {k: v.cpu().numpy().view(np.uint32) for k, v in whole.items()}
+        i = info(L, geom, n)
+        return split_outputs(S, n, **check_guards(bufs, sizes, i["splits"], i["blocks"]))
+    return run

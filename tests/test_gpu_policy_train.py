@@ -1,6 +1,7 @@
 """The trunk-training kernels (include/bpp_policy_train.h), bpp_amd.policy_trunk and bpp_amd.TrainablePolicy on
 the device: the exact-integer networks of tests/policy_train_cases.py bit for bit, the training forward against the inference
-forward's workspace, real-valued gradients against float64 torch autograd under the 8 x rule, independence of the batch, the
+forward's workspace, real-valued gradients against float64 torch autograd under the 8 x rule, real-valued outputs bit for bit
+against the recorded bits of the header's arithmetic (tc.normative), the split identity, guarded buffers, independence of the batch, the
 same bits on every run / on another stream / in a replayed graph / over a retained graph, the module against the reference's own
 Policy (oracle/_ref/, where it is present) under a2c_loss, and examples/train_with_storage.py --native-trunk against its torch
 stand-in."""
@@ -380,3 +381,60 @@ def test_the_example_trains_through_the_native_trunk():
         assert len(history) == 2 and all(np.isfinite(v) for terms in history for v in terms)
     with pytest.raises(ValueError, match="native-trunk"):
         ex.train(envs=64, updates=1, native_trunk=True, acktr=True, verbose=False)
+
+
+# ------------------------------------------------------------------------- the header's arithmetic, bit for bit (tc.normative)
+@pytest.mark.parametrize("S,n", sorted(tc.TRAIN_CHAIN_CASES))
+def test_real_valued_chains_equal_the_headers_arithmetic_bit_for_bit(lib, S, n):
+    """Device: feat, acts, grads, gf' and grad_weights on real-valued data against the recorded bits of tc.normative
+    (tests/golden/make_trunk_train_chain_bits.py): the CRC32 of every output, one forward and one backward call per case."""
+    splits, last, P = tc.TRAIN_CHAIN_CASES[(S, n)]
+    i = tc.info(lib, tc.geom_of(S), n)
+    assert i["splits"] == splits and n - (splits - 1) * i["bins_per_split"] == last and (P is None or i["bins_per_group"] == P)
+    case, name, bits = tc.train_chain_case(S, n), tc.train_chain_name(S, n), tc.load_fixture(tc.TRAIN_CHAIN_FIXTURE)
+    for k in tc.TRAIN_CHAIN_INPUTS:
+        assert pc.crc(case[k]) == bits["%s.crc.%s" % (name, k)], k
+    got = tc.device_runner(DEV)(case["obs"], case["geom"], case["blob"], case["blob_bwd"], case["grad_feat"])
+    tc.check_train_chain(got, bits, name, "device:")
+
+
+@pytest.mark.parametrize("S,n,splits", [(3, 150, 3), (10, 21, 3)])
+def test_the_whole_batch_is_the_double_sum_of_its_splits(lib, S, n, splits):
+    i = tc.info(lib, tc.geom_of(S), n)
+    assert i["splits"] == splits and i["bins_per_split"] == tc.header_bins_per_split(S)
+    differing = tc.check_split_identity(tc.device_runner(DEV), tc.train_chain_case(S, n), i["bins_per_split"])
+    print("S = %d, n = %d: a float32 sum of the splits differs in %d floats" % (S, n, differing))
+
+
+@pytest.mark.parametrize("name", ["s10_nP1", "s7_nP1", "s15_n2"])
+def test_nothing_is_stored_outside_the_outputs(lib, name):
+    """Outputs and workspace as slices of larger device tensors (tc.guarded_buffers): 1024 guard floats on either side of each
+    and the workspace beyond the stated bytes untouched, every output float written, the bits of the plain runner."""
+    case = tc.exact_case(**tc.exact_spec(lib, name))
+    got = tc.check_exact(tc.guarded_device_runner(lib, DEV), case)
+    plain = tc.device_runner(DEV)(case["obs"], case["geom"], case["blob"], case["blob_bwd"], case["grad_feat"])
+    assert all(pc.same_bits(got[k], plain[k]) for k in tc.OUTPUTS)
+
+
+@pytest.mark.parametrize("n", [1, 3])
+def test_policy_trunk_on_a_column_slice_and_a_strided_gradient(real10, n):
+    """obs a column slice of a wider tensor (stride(0) > 4 A, every other column NaN), the backward from feat[:, ::2].sum(), whose
+    gradient at feat is not contiguous: the bits of the contiguous call."""
+    import bpp_amd
+    case, t, _ = real10
+    order = lambda p: [p[k] for k in pol.TRUNK_PARAMETERS]        # noqa: E731
+    wide = torch.full((n, 5 + 400 + 32), float("nan"), device=DEV)
+    wide[:, 5:405] = t["obs"][:n]
+    obs = wide[:, 5:405]
+    assert obs.stride(0) == 437 and obs.data_ptr() != wide.data_ptr()
+    p1 = {k: case["plain"][k].to(DEV).requires_grad_(True) for k in pol.TRUNK_PARAMETERS}
+    feat = bpp_amd.policy_trunk(obs, p1, 10, cache={})
+    g1 = torch.autograd.grad(feat[:, ::2].sum(), order(p1))
+    p2 = {k: case["plain"][k].to(DEV).requires_grad_(True) for k in pol.TRUNK_PARAMETERS}
+    same = bpp_amd.policy_trunk(t["obs"][:n].contiguous(), p2, 10, cache={})
+    at_feat = torch.zeros(n, 2000, device=DEV)
+    at_feat[:, ::2] = 1.0
+    g2 = torch.autograd.grad(same, order(p2), at_feat)
+    assert torch.equal(feat.view(torch.int32), same.view(torch.int32)) and not torch.isnan(feat).any() and float(feat.detach().max()) > 0
+    for k, a, b in zip(pol.TRUNK_PARAMETERS, g1, g2):
+        assert torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)) and float(a.abs().max()) > 0, k

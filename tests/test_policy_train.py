@@ -2,7 +2,9 @@
 bpp_amd.TrainablePolicy without a GPU: the product kernels of csrc/bpp_policy_train.inl compiled by g++ against the SIMT emulator.
 Exact-integer networks bit for bit against int64 numpy (forward, every activation, every input gradient, every weight and bias
 gradient); the training forward against the inference forward; real-valued networks against float64 torch autograd within 8 x
-the error of float32 torch autograd; batch independence; the refusals of the header on the product library, which has no device
+the error of float32 torch autograd; real-valued networks bit for bit against the header's arithmetic in numpy (tc.normative,
+recorded in tests/golden/trunk_train_chain_bits.npz) and the split identity of grad_weights; stores outside the outputs; batch
+independence; the refusals of the header on the product library, which has no device
 here; the packing of the second blob; the module's names and state-dict forms.  Helpers: tests/policy_train_cases.py."""
 import ctypes
 import os
@@ -47,7 +49,9 @@ def test_exact_integer_networks_equal_int64_numpy_bit_for_bit(emu_lib, name):
     if name == "s5_three_splits":
         i = tc.info(emu_lib, tc.geom_of(5), spec["n"])
         assert i["splits"] == 3 and spec["n"] == 2 * i["bins_per_split"] + 1 and i["chain_rows"] == i["bins_per_split"] * 25
-    tc.check_exact(tc.host_runner(emu_lib), tc.exact_case(**spec))
+    case = tc.exact_case(**spec)
+    assert case["obs"].shape[1] == 4 * spec["S"] ** 2 + tc.EXACT_SPECS[name][4] and np.isnan(case["obs"][:, 4 * spec["S"] ** 2:]).all()
+    tc.check_exact(tc.host_runner(emu_lib), case)
 
 
 def test_the_shapes_of_the_exact_cases_are_what_their_names_say(emu_lib):
@@ -55,6 +59,19 @@ def test_the_shapes_of_the_exact_cases_are_what_their_names_say(emu_lib):
     assert tc.info(emu_lib, tc.geom_of(11), 3)["bins_per_group"] == 1
     i = tc.info(emu_lib, tc.geom_of(15), 2)
     assert i["grad_lds_bytes"] == 151296 and i["wgrad_lds_bytes"] <= 160 * 1024
+    assert sorted(tc.EXACT_SPLITS) == sorted(k for k in tc.EXACT_SPECS if k.endswith("_splits"))
+    for name, (splits, last) in tc.EXACT_SPLITS.items():                # every multi-split name: its splits and its last split's bins
+        spec = tc.exact_spec(emu_lib, name)
+        i = tc.info(emu_lib, tc.geom_of(spec["S"]), spec["n"])
+        assert i["splits"] == splits and spec["n"] - (splits - 1) * i["bins_per_split"] == last, (name, i)
+        assert i["chain_rows"] == i["bins_per_split"] * spec["S"] ** 2 and i["bins_per_split"] == tc.header_bins_per_split(spec["S"])
+    for name in ("s2_three_splits", "s3_three_splits", "s4_two_splits"):        # the 64-bin cap on a split, with more than one split
+        assert tc.info(emu_lib, tc.geom_of(tc.EXACT_SPECS[name][0]), 1)["bins_per_split"] == 64
+    assert tc.exact_spec(emu_lib, "s10_two_splits")["n"] == 11 and tc.exact_spec(emu_lib, "s2_three_splits")["n"] == 129
+    assert {tc.EXACT_SPECS[k][0] for k in tc.EXACT_SPECS} == set(range(1, 16))             # every side the header accepts
+    assert sum(1 for k in tc.EXACT_SPECS if tc.EXACT_SPECS[k][4]) == 5                     # padded rows of obs
+    i = tc.info(emu_lib, tc.geom_of(7), 3)
+    assert i["bins_per_group"] == 2 and tc.exact_spec(emu_lib, "s7_nP1")["n"] == 3          # the last workgroup has one bin of its two
 
 
 @pytest.mark.parametrize("S,H,M,n", [(10, 256, 100, 5), (11, 32, 121, 3)])
@@ -223,3 +240,108 @@ def test_the_module_carries_the_reference_names_and_loads_the_three_forms():
         bpp_amd.TrainablePolicy(20, 400)
     with pytest.raises(ValueError, match="base.mask.5"):
         bpp_amd.TrainablePolicy(10, 200).load_state_dict({k: v for k, v in plain.items() if not k.startswith("base.mask.5")})
+
+
+# ------------------------------------------------------------------------- the header's arithmetic, bit for bit (tc.normative)
+def _fmaf():
+    libm = ctypes.CDLL("libm.so.6")
+    libm.fmaf.restype, libm.fmaf.argtypes = ctypes.c_float, [ctypes.c_float] * 3
+    return lambda a, b, c: np.array([libm.fmaf(float(x), float(y), float(z)) for x, y, z in zip(a, b, c)], np.float32)
+
+
+def _boundary_triples():
+    """Small-integer triples whose a * b + c lies at or one unit next to a float32 rounding boundary that float64 cannot tell
+    from the boundary itself: c = +-m 2^e with m in [2^23, 2^24) and e = 2 h + 1, so that c's neighbours are 2^e apart and the
+    boundary lies 2^(2 h) from c; a * b = (2^h + 1)(2^h - 1) = 2^(2 h) - 1 (one short of the boundary) or 2^h 2^h (on it), towards
+    either neighbour.  h >= 16: the missing 1 is below half a unit of float64 at c.  Returns (a, b, c, next_to_a_boundary)."""
+    rng = np.random.RandomState(3)
+    rows = []
+    for h in range(16, 24):
+        for m in [2 ** 23, 2 ** 24 - 1] + list(rng.randint(2 ** 23, 2 ** 24, 14)):
+            for sign_c in (1.0, -1.0):
+                for sign_p in (1.0, -1.0):
+                    rows.append((sign_p * (2.0 ** h + 1), 2.0 ** h - 1, sign_c * float(m) * 2.0 ** (2 * h + 1), True))
+                    rows.append((sign_p * 2.0 ** h, 2.0 ** h, sign_c * float(m) * 2.0 ** (2 * h + 1), False))
+    a, b, c, near = (np.array(v) for v in zip(*rows))
+    f = lambda v: v.astype(np.float32)        # noqa: E731
+    assert (f(a) == a).all() and (f(b) == b).all() and (f(c) == c).all()
+    return f(a), f(b), f(c), near.astype(bool)
+
+
+def test_fma32_is_libm_fmaf_on_random_triples_and_at_rounding_boundaries():
+    fmaf = _fmaf()
+    rng = np.random.RandomState(0)
+    N = 100000
+    a, b = rng.standard_normal(N).astype(np.float32), rng.standard_normal(N).astype(np.float32)
+    c = (rng.standard_normal(N) * 10.0 ** rng.randint(-6, 3, N)).astype(np.float32)
+    a[:N // 4], b[:N // 4] = rng.randint(1, 1 << 12, N // 4), rng.randint(1, 1 << 12, N // 4)
+    c[:N // 4] = rng.randint(1, 1 << 24, N // 4).astype(np.float32) * np.float32(2.0) ** rng.randint(-30, 30, N // 4)
+    c[N // 4:N // 2] = -(a[N // 4:N // 2] * b[N // 4:N // 2])                              # cancellation: the result is the product's own rounding error
+    assert pc.same_bits(tc.fma32(a, b, c), fmaf(a, b, c))
+    a, b, c, near = _boundary_triples()
+    want = fmaf(a, b, c)
+    assert pc.same_bits(tc.fma32(a, b, c), want)
+    naive = (a.astype(np.float64) * b + c).astype(np.float32)            # rounds twice: to float64, then to float32
+    wrong = naive.view(np.uint32) != want.view(np.uint32)
+    print("float32(float64(a) * b + c) is wrong in %d of %d boundary triples" % (wrong.sum(), wrong.size))
+    assert wrong[near].sum() >= near.sum() // 4 and not wrong[~near].any()            # the set is not too easy: double rounding fails it
+    z = np.float32(0)
+    assert pc.same_bits(tc.fma32(z, np.float32(-3), z), z) and pc.same_bits(tc.fma32(z, np.float32(3), np.float32(-0.0)), z)        # as fmaf: +0
+
+
+@pytest.fixture(scope="module")
+def chain_bits():
+    return tc.load_fixture(tc.TRAIN_CHAIN_FIXTURE)
+
+
+def test_the_recorded_chain_bits_hold_every_case_once(chain_bits):
+    names = [tc.train_chain_name(S, n) for S, n in tc.TRAIN_CHAIN_CASES]
+    want = ["%s.crc.%s" % (nm, k) for nm in names for k in tc.TRAIN_CHAIN_INPUTS] + \
+           ["%s.%s.%s" % (nm, k, what) for nm in names for k in tc.OUTPUTS for what in ("crc", "sample")]
+    assert sorted(chain_bits.files) == sorted(want)
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", tc.TRAIN_CHAIN_FIXTURE + ".npz")) < 250000
+    for S, n in tc.TRAIN_CHAIN_CASES:
+        assert all(tc.sample_step(size) % 2 == 1 and -(-size // tc.sample_step(size)) <= tc.SAMPLE <= 4096
+                   for size in (n * 20 * S * S, 5 * n * 64 * S * S, pol.TRUNK_FLOATS))
+
+
+@pytest.mark.parametrize("S,n", [(5, 3), (3, 66)])
+def test_the_recorded_chain_bits_are_the_reference_computed_now(chain_bits, S, n):
+    """tc.normative live, about 1 s and 9 s: every recorded array of the case."""
+    case = tc.train_chain_case(S, n)
+    want = tc.normative(case["plain"], case["obs"], case["grad_feat"], S, tc.header_bins_per_split(S))
+    for key, v in tc.train_chain_entries(case, want, tc.train_chain_name(S, n)).items():
+        assert np.array_equal(chain_bits[key], v), key
+    assert not np.isnan(want["gw"]).any() and min(float(np.abs(want[k]).max()) for k in tc.OUTPUTS) > 0
+
+
+@pytest.mark.parametrize("S,n", sorted(tc.TRAIN_CHAIN_CASES))
+def test_real_valued_chains_equal_the_headers_arithmetic_bit_for_bit(emu_lib, chain_bits, S, n):
+    """Emulator: feat, acts, grads, gf' and grad_weights on real-valued data against the recorded bits of tc.normative."""
+    splits, last, P = tc.TRAIN_CHAIN_CASES[(S, n)]
+    i = tc.info(emu_lib, tc.geom_of(S), n)
+    assert i["splits"] == splits and n - (splits - 1) * i["bins_per_split"] == last and i["bins_per_split"] == tc.header_bins_per_split(S)
+    assert P is None or i["bins_per_group"] == P
+    case, name = tc.train_chain_case(S, n), tc.train_chain_name(S, n)
+    for k in tc.TRAIN_CHAIN_INPUTS:
+        assert pc.crc(case[k]) == chain_bits["%s.crc.%s" % (name, k)], k
+    got = tc.host_runner(emu_lib)(case["obs"], case["geom"], case["blob"], case["blob_bwd"], case["grad_feat"])
+    tc.check_train_chain(got, chain_bits, name, "emulator:")
+
+
+@pytest.mark.parametrize("S,n,splits", [(3, 150, 3), (10, 21, 3)])
+def test_the_whole_batch_is_the_double_sum_of_its_splits(emu_lib, S, n, splits):
+    i = tc.info(emu_lib, tc.geom_of(S), n)
+    assert i["splits"] == splits and i["bins_per_split"] == tc.header_bins_per_split(S)
+    differing = tc.check_split_identity(tc.host_runner(emu_lib), tc.train_chain_case(S, n), i["bins_per_split"])
+    print("S = %d, n = %d: a float32 sum of the splits differs in %d floats" % (S, n, differing))
+
+
+@pytest.mark.parametrize("name", ["s10_nP1", "s7_nP1", "s15_n2"])
+def test_nothing_is_stored_outside_the_outputs(emu_lib, name):
+    """Outputs and workspace carved out of guarded buffers (tc.guarded_buffers): guards and the workspace beyond the stated bytes
+    untouched, every output float written, the bits of the plain runner."""
+    case = tc.exact_case(**tc.exact_spec(emu_lib, name))
+    got = tc.check_exact(tc.guarded_host_runner(emu_lib), case)
+    plain = tc.host_runner(emu_lib)(case["obs"], case["geom"], case["blob"], case["blob_bwd"], case["grad_feat"])
+    assert all(pc.same_bits(got[k], plain[k]) for k in tc.OUTPUTS)
