@@ -596,6 +596,18 @@ void raise_dynamic_lds(Kern kernel, std::atomic<uint64_t> &raised, int bytes) {
     }
 }
 
+// The launch of a kernel whose `lds` bytes of dynamic LDS may exceed 64 KiB: opts in to `most` bytes where they do (the set of
+// devices is this instantiation's, so the kernel's own), launches, and returns the launch error.
+template <auto kernel, typename... Args>
+int launch_large_lds(dim3 grid, dim3 block, size_t lds, int most, hipStream_t stream, const Args &...args) {
+    if (lds > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        raise_dynamic_lds(kernel, raised, most);
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return launched();
+}
+
 int check_geometry(int E, int W, int L, int H, int rotation, int rule) {
     if (E <= 0 || W <= 0 || L <= 0 || H <= 0) return fail(BPP_E_BADARG, "non-positive size");
     if (rotation != 0 && rotation != 1) return fail(BPP_E_BADARG, "rotation must be 0 or 1");
@@ -785,22 +797,10 @@ Launch configure(int E, int W, int L, int H, int rotation, int rule, bool tile =
     return l;
 }
 
-template <int K, bool ROT, int MODE, bool SUB>
-void launch_fast_rot(const Launch &l, hipStream_t s) {
-    auto kern = bpp_fast_kernel<K, ROT, MODE, SUB>;
-    if (l.lds > 64 * 1024) {  // large workgroups
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(kern, raised, 160 * 1024);
-    }
-    hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
-}
-
 template <int K, int MODE, bool SUB>
-void launch_fast(const Launch &l, hipStream_t s) {
-    if (l.p.rotation)
-        launch_fast_rot<K, true, MODE, SUB>(l, s);
-    else
-        launch_fast_rot<K, false, MODE, SUB>(l, s);
+int launch_fast(const Launch &l, hipStream_t s) {   // more than 64 KiB: large workgroups
+    if (l.p.rotation) return launch_large_lds<bpp_fast_kernel<K, true, MODE, SUB>>(dim3(l.blocks), dim3(kWave * l.wpb), l.lds, 160 * 1024, s, l.p);
+    return launch_large_lds<bpp_fast_kernel<K, false, MODE, SUB>>(dim3(l.blocks), dim3(kWave * l.wpb), l.lds, 160 * 1024, s, l.p);
 }
 
 template <int W, int L, int K, int MODE, int EPW, int NIT>
@@ -867,9 +867,9 @@ int launch(const Launch &l, hipStream_t s) {
             launch_tile<t.W, t.L, t.K, MODE, t.epw>(l, s);
         });
     else if (l.kind == BPP_KERNEL_PREFIX_RT && l.K == 1)
-        launch_fast<1, MODE, SUB>(l, s);
+        return launch_fast<1, MODE, SUB>(l, s);
     else if (l.kind == BPP_KERNEL_PREFIX_RT)
-        launch_fast<2, MODE, SUB>(l, s);
+        return launch_fast<2, MODE, SUB>(l, s);
     else if (l.p.A % 4 == 0)
         hipLaunchKernelGGL((bpp_kernel<true, MODE, SUB>), dim3(l.blocks), dim3(kWave * l.wpb), l.lds, s, l.p);
     else
@@ -1638,6 +1638,7 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_mcts.inl"
 #include "bpp_returns.inl"
 #include "bpp_update.inl"
+#include "bpp_mfma.inl"
 #include "bpp_kfac.inl"
 #include "bpp_policy.inl"
 #include "bpp_policy_train.inl"

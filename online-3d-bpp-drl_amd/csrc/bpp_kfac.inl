@@ -9,27 +9,17 @@
 // address pattern and is never written anywhere.  The partial tiles go to the workspace; kfac_reduce_kernel adds them per
 // element in split order in double, scales, casts, applies the running average and writes both triangles.
 //
-// g++ compiles this file too (tests/emu): kfac_mac is the only function that differs.  On the device it issues the MFMA;
-// emulated, a lane walks its 16 accumulator slots and applies fmaf in the same k order to operands read from the same LDS
-// image.  The instruction is defined as that chain, so the two give the same bits.
+// The tile -- accumulator, layout, the instruction and its emulated chain -- is bpp_mfma.inl's.  g++ compiles this file too
+// (tests/emu); nothing in it differs between the two builds.
 
 namespace {
 
-constexpr int kKfacTile = 32;                       // side of an output tile
+constexpr int kKfacTile = kMfmaTile;                // side of an output tile
 constexpr int kKfacBlock = 2 * kKfacTile;           // features of a block
 constexpr int kKfacUnitRows = 64;                   // ROWS: rows staged at a time; NCHW: at most
 constexpr int kKfacNchwStride = kKfacUnitRows + 1;  // NCHW: floats between two features of the staged unit (odd: no bank conflicts)
 constexpr int kKfacGroups = 1024;                   // workgroups aimed at: pairs x splits
 constexpr int kKfacLdsBytes = 64 * 1024;
-
-#ifdef BPP_EMU_HIP_RUNTIME_H
-struct KfacAcc {
-    float v[16];
-    float &operator[](int i) { return v[i]; }
-};
-#else
-typedef float KfacAcc __attribute__((ext_vector_type(16)));
-#endif
 
 struct KfacShape {
     int layout, D, nt, nb, pairs, T;          // tiles and blocks per side, block pairs, tiles on or above the diagonal
@@ -109,29 +99,14 @@ __device__ __forceinline__ int kfac_stage(const float *src, const KfacShape &s, 
 // acc += A^T-by-B of rows r and r + 1 of the staged unit (row r + 1 counts as zeros when the unit ends at r):
 // acc[i][j] = fmaf(x[r + 1][i], x[r + 1][j], fmaf(x[r][i], x[r][j], acc[i][j])).  ta / tb: the feature offsets of the tile's 32
 // rows / 32 columns, fa / fb this lane's own (ta[lane & 31], tb[lane & 31]); rtab: the row offsets of the unit.
-// Lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; slot s of its accumulator is
-// C[(s & 3) + 8 (s >> 2) + 4 (l >> 5)][l & 31].
-__device__ __forceinline__ void kfac_mac(KfacAcc &acc, const float *img, const int *ta, const int *tb, int fa, int fb, const int *rtab,
+__device__ __forceinline__ void kfac_mac(MfmaAcc &acc, const float *img, const int *ta, const int *tb, int fa, int fb, const int *rtab,
                                          int r, int nr, int lane) {
-#ifdef BPP_EMU_HIP_RUNTIME_H
-    const int col = lane & 31, half = lane >> 5;
-    for (int k = 0; k < 2; ++k) {
-        const bool ok = r + k < nr;
-        const int ro = ok ? rtab[r + k] : 0;
-        const float b = ok ? img[tb[col] + ro] : 0.0f;
-        for (int s = 0; s < 16; ++s) {
-            const int row = (s & 3) + 8 * (s >> 2) + 4 * half;
-            const float a = ok ? img[ta[row] + ro] : 0.0f;
-            acc[s] = fmaf(a, b, acc[s]);
-        }
-    }
-#else
-    const int k = r + (lane >> 5);
+    const int k = r + (lane >> 5);                    // the lane's own operands, the only ones the device fetches
     const bool ok = k < nr;
     const int ro = rtab[ok ? k : r];
     const float a = ok ? img[fa + ro] : 0.0f, b = ok ? img[fb + ro] : 0.0f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-#endif
+    const auto x = [&](const int *t, int f, int kk) { return r + kk < nr ? img[t[f] + rtab[r + kk]] : 0.0f; };
+    mfma_step(acc, lane, a, b, [&](int i, int kk) { return x(ta, i, kk); }, [&](int kk, int j) { return x(tb, j, kk); });
 }
 
 // index of tile (ti <= tj) among the tiles on or above the diagonal, row by row
@@ -164,9 +139,9 @@ __global__ __launch_bounds__(256) void kfac_partial_kernel(KfacArgs a) {
     const bool active = ti < s.nt && tj < s.nt && tj >= ti;
     const int *ta = ftab + wi * kKfacTile, *tb = ftab + kKfacBlock + wj * kKfacTile;
     const int fa = ta[lane & 31], fb = tb[lane & 31];
-    KfacAcc acc;
+    MfmaAcc acc;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+    for (int k = 0; k < kMfmaSlots; ++k) acc[k] = 0.0f;
     const long long u0 = (long long)split * s.ups, u1 = min(s.units, u0 + s.ups);
     for (long long u = u0; u < u1; ++u) {
         const int nr = kfac_stage(a.src, s, u, bi, img, tid);
@@ -181,7 +156,7 @@ __global__ __launch_bounds__(256) void kfac_partial_kernel(KfacArgs a) {
     if (active) {
         float *out = a.part + ((size_t)split * (size_t)s.T + (size_t)kfac_tile_index(s.nt, ti, tj)) * 1024u;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) out[k * kWave + lane] = acc[k];
+        for (int k = 0; k < kMfmaSlots; ++k) out[k * kWave + lane] = acc[k];
     }
 }
 
@@ -197,7 +172,7 @@ __global__ __launch_bounds__(256) void kfac_reduce_kernel(const float *part, flo
         ++ti;
     }
     const int tj = ti + rest;
-    const int row = (slot & 3) + 8 * (slot >> 2) + 4 * (lane >> 5), col = lane & 31;
+    const int row = mfma_slot_row(slot, lane), col = lane & 31;
     const int i = ti * kKfacTile + row, j = tj * kKfacTile + col;
     if (i >= D || j >= D || j < i) return;
     double sum = 0.0;

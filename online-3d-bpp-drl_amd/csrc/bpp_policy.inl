@@ -11,12 +11,12 @@
 // to the workspace in rows.  policy_head_kernel: a workgroup owns 64 bins and one head; the features pass through LDS 64 input
 // features at a time, the hidden vector stays in LDS between the two Linear layers.
 //
-// g++ compiles this file too (tests/emu): policy_chain is the only function that differs.  On the device it issues the MFMAs;
-// emulated, a lane walks its accumulator slots and applies fmaf in the same k order to the same operands.
+// The tile -- accumulator, layout, the instruction and its emulated chain -- is bpp_mfma.inl's.  g++ compiles this file too
+// (tests/emu): policy_chain is the only function that differs, by the software-pipelined loop that only the device has.
 
 namespace {
 
-constexpr int kPolTile = 32;              // side of an MFMA tile
+constexpr int kPolTile = kMfmaTile;
 constexpr int kPolC = 64;                 // trunk channels
 constexpr int kPolIn = 4;                 // input channels
 constexpr int kPolHeadC = 20;             // actor 8 + mask 8 + critic 4
@@ -58,31 +58,26 @@ struct PolHeadArgs {
 // column ncol - 1 instead and its result is never used.  A table must repeat with period 2 U: ftab[k + 2 U] - ftab[k] is one
 // constant (U = 9: two channels of a 3x3 layer).
 //
-// On the device two k go into one v_mfma_f32_32x32x2_f32: lane l holds A[l & 31][k + (l >> 5)] and B[k + (l >> 5)][l & 31]; slot s
-// of its accumulator is C[(s & 3) + 8 (s >> 2) + 4 (l >> 5)][l & 31].  The operands of U instructions per column tile are
-// fetched while the U before them issue: with one wave per SIMD nothing else hides the latency of the weights.
+// Two k go into one mfma_step (bpp_mfma.inl): lane l passes A[l & 31][k + (l >> 5)] and B[k + (l >> 5)][l & 31].  On the device
+// the operands of U instructions per column tile are fetched while the U before them issue: with one wave per SIMD nothing else
+// hides the latency of the weights.  What that loop leaves of K goes through the plain loop behind it; emulated, all of K does.
+// Both walk k in pairs, so K must be even as stated above: every caller's is (36, 576, 64, 20, H, and 4 A or 8 A in chunks of 64).
 template <int NB, int U>
-__device__ __forceinline__ void policy_chain(KfacAcc (&acc)[NB], const float *img, const int *rt, int ro, const int *ftab, int kstride, int K,
+__device__ __forceinline__ void policy_chain(MfmaAcc (&acc)[NB], const float *img, const int *rt, int ro, const int *ftab, int kstride, int K,
                                              const float *__restrict__ w, int ldw, int col0, int ncol, int lane) {
     const int col = lane & 31, half = lane >> 5;
+    const auto column = [&](int t, int j) { return min(col0 + kPolTile * t + j, ncol - 1); };
     int cc[NB];
 #pragma unroll
-    for (int t = 0; t < NB; ++t) cc[t] = min(col0 + kPolTile * t + col, ncol - 1);
-#ifdef BPP_EMU_HIP_RUNTIME_H
-    for (int k = 0; k < K; ++k) {
-        const int ko = ftab ? ftab[k] : k * kstride;
-        for (int t = 0; t < NB; ++t) {
-            const float b = w[(size_t)k * (size_t)ldw + (size_t)cc[t]];
-            for (int s = 0; s < 16; ++s) acc[t][s] = fmaf(img[rt[(s & 3) + 8 * (s >> 2) + 4 * half] + ko], b, acc[t][s]);
-        }
-    }
-#else
+    for (int t = 0; t < NB; ++t) cc[t] = column(t, col);
+    const float *ap = img + ro;
+    int k0 = 0;
+#ifndef BPP_EMU_HIP_RUNTIME_H
     int off[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) off[u] = ftab ? ftab[2 * u + half] : (2 * u + half) * kstride;
     const int adv = ftab ? ftab[2 * U] - ftab[0] : 2 * U * kstride;
     const int nb = K / (2 * U);
-    const float *ap = img + ro;
     const float *__restrict__ wp = w + (size_t)half * (size_t)ldw;
     float a0[U], b0[U][NB];
     if (nb > 0) {
@@ -108,7 +103,7 @@ __device__ __forceinline__ void policy_chain(KfacAcc (&acc)[NB], const float *im
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
-            for (int t = 0; t < NB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u][t], acc[t], 0, 0, 0);
+            for (int t = 0; t < NB; ++t) mfma_issue(acc[t], a0[u], b0[u][t]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -122,27 +117,27 @@ __device__ __forceinline__ void policy_chain(KfacAcc (&acc)[NB], const float *im
             }
         }
     }
-    for (int k = nb * 2 * U + half; k < K; k += 2) {
-        const float a = ap[ftab ? ftab[k] : k * kstride];
-#pragma unroll
-        for (int t = 0; t < NB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w[(size_t)k * (size_t)ldw + (size_t)cc[t]], acc[t], 0, 0, 0);
-    }
+    k0 = nb * 2 * U;
 #endif
+    const auto koff = [&](int k) { return ftab ? ftab[k] : k * kstride; };
+    for (int k = k0 + half; k < K; k += 2) {
+        const float a = ap[koff(k)];
+#pragma unroll
+        for (int t = 0; t < NB; ++t)
+            mfma_step(acc[t], lane, a, w[(size_t)k * (size_t)ldw + (size_t)cc[t]],
+                      [&](int i, int kk) { return img[rt[i] + koff(k - half + kk)]; },
+                      [&](int kk, int j) { return w[(size_t)(k - half + kk) * (size_t)ldw + (size_t)column(t, j)]; });
+    }
 }
 
 // every slot of acc[t] = bias of the lane's column (0 from column ncol on): the chain starts from the bias
 template <int NB>
-__device__ __forceinline__ void policy_start(KfacAcc (&acc)[NB], const float *bias, int col0, int ncol, int lane) {
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
+__device__ __forceinline__ void policy_start(MfmaAcc (&acc)[NB], const float *bias, int col0, int ncol, int lane) {
+    mfma_fill(acc, [&](int t) {
         const int c = col0 + kPolTile * t + (lane & 31);
-        const float b = c < ncol ? bias[c] : 0.0f;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc[t][s] = b;
-    }
+        return c < ncol ? bias[c] : 0.0f;
+    });
 }
-
-__device__ __forceinline__ int policy_slot_row(int s, int lane) { return (s & 3) + 8 * (s >> 2) + 4 * (lane >> 5); }
 
 // grid = ceil(n / P).  ACTS: every layer's ReLU output also goes to a.acts, copied from the image it was written to.
 template <bool ACTS>
@@ -177,14 +172,14 @@ __global__ __launch_bounds__(256) void policy_trunk_kernel(PolTrunkArgs a) {
         for (int pt = wave; pt < s.tiles; pt += 4) {
             const int *rt = rtab + pt * kPolTile;
             const int ro = rt[col];
-            KfacAcc acc[2];
+            MfmaAcc acc[2];
             policy_start<2>(acc, bias, 0, kPolC, lane);
             policy_chain<2, 9>(acc, src, rt, ro, ftab, 0, K, w, kPolC, 0, kPolC, lane);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int row = pt * kPolTile + policy_slot_row(q, lane);
+                for (int q = 0; q < kMfmaSlots; ++q) {
+                    const int row = pt * kPolTile + mfma_slot_row(q, lane);
                     const float v = acc[t][q];
                     if (row < s.rows) dst[rtab[row] + (kPolTile * t + col) * s.PP + centre] = v > 0.0f ? v : 0.0f;
                 }
@@ -208,12 +203,12 @@ __global__ __launch_bounds__(256) void policy_trunk_kernel(PolTrunkArgs a) {
     for (int pt = wave; pt < s.tiles; pt += 4) {
         const int *rt = rtab + pt * kPolTile;
         const int ro = rt[col];
-        KfacAcc acc[1];
+        MfmaAcc acc[1];
         policy_start<1>(acc, bias, 0, kPolHeadC, lane);
         policy_chain<1, 8>(acc, src + centre, rt, ro, nullptr, s.PP, kPolC, w, kPolHeadC, 0, kPolHeadC, lane);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int row = pt * kPolTile + policy_slot_row(q, lane);
+        for (int q = 0; q < kMfmaSlots; ++q) {
+            const int row = pt * kPolTile + mfma_slot_row(q, lane);
             const float v = acc[0][q];
             if (row < s.rows && col < kPolHeadC) {
                 const int b = row / s.A;
@@ -246,7 +241,7 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
     // first Linear: a pass covers 256 hidden features, a wave 32 bins by 128 of them
     for (int h0 = 0; h0 < s.H; h0 += 8 * kPolTile) {
         const int col0 = h0 + cgroup * 4 * kPolTile;
-        KfacAcc acc[4];
+        MfmaAcc acc[4];
         policy_start<4>(acc, b1, col0, s.H, lane);
         for (int k0 = 0; k0 < K1; k0 += kPolChunk) {
             const int kc = min(kPolChunk, K1 - k0);
@@ -262,9 +257,9 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
         for (int t = 0; t < 4; ++t) {
             const int c = col0 + kPolTile * t + col;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
+            for (int q = 0; q < kMfmaSlots; ++q) {
                 const float v = acc[t][q];
-                if (c < s.H) hid[c * kPolStride + rtile * kPolTile + policy_slot_row(q, lane)] = v > 0.0f ? v : 0.0f;
+                if (c < s.H) hid[c * kPolStride + rtile * kPolTile + mfma_slot_row(q, lane)] = v > 0.0f ? v : 0.0f;
             }
         }
     }
@@ -272,15 +267,15 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
     // second Linear: a wave takes 32 bins by 64 outputs at a time
     float *out = a.out[head];
     for (int col0 = cgroup * 2 * kPolTile; col0 < Mh; col0 += 4 * kPolTile) {
-        KfacAcc acc[2];
+        MfmaAcc acc[2];
         policy_start<2>(acc, b2, col0, Mh, lane);
         policy_chain<2, 8>(acc, hid, rt, ro, nullptr, kPolStride, s.H, w2, Mh, col0, Mh, lane);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int c = col0 + kPolTile * t + col;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const long long bin = bin0 + rtile * kPolTile + policy_slot_row(q, lane);
+            for (int q = 0; q < kMfmaSlots; ++q) {
+                const long long bin = bin0 + rtile * kPolTile + mfma_slot_row(q, lane);
                 const float v = acc[t][q];
                 if (c < Mh && bin < s.n) out[(size_t)bin * (size_t)Mh + (size_t)c] = head == 1 && !(v > 0.0f) ? 0.0f : v;
             }
@@ -362,12 +357,9 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
     const PolShape &s = t.s;
     const hipStream_t st = (hipStream_t)stream;
     t.obs = obs, t.obs_stride = obs_stride, t.w = weights, t.feat = (float *)workspace, t.acts = nullptr;
-    if (s.trunk_lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_trunk_kernel<false>, raised, kPolLdsBytes);
-    }
-    hipLaunchKernelGGL(policy_trunk_kernel<false>, dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), (size_t)s.trunk_lds, st, t);
-    if (const int rc = launched()) return rc;
+    if (const int rc = launch_large_lds<policy_trunk_kernel<false>>(dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), s.trunk_lds,
+                                                                    kPolLdsBytes, st, t))
+        return rc;
     PolHeadArgs h;
     h.feat = (const float *)workspace, h.w = weights, h.s = s, h.nheads = 0;
     h.out[0] = logits, h.out[1] = pred, h.out[2] = value;
@@ -375,13 +367,8 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
         h.heads[k] = 0;
         if (h.out[k]) h.heads[h.nheads++] = k;
     }
-    if (s.head_lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_head_kernel, raised, kPolLdsBytes);
-    }
-    hipLaunchKernelGGL(policy_head_kernel, dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), (size_t)s.head_lds,
-                       st, h);
-    return launched();
+    return launch_large_lds<policy_head_kernel>(dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), s.head_lds,
+                                                kPolLdsBytes, st, h);
 }
 
 }  // extern "C"

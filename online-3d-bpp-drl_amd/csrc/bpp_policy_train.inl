@@ -4,10 +4,10 @@
 //
 // Forward: policy_trunk_kernel<true> (bpp_policy.inl), the inference kernel with one more store per layer.
 //
-// policy_trunk_grad_kernel: its sibling on the second blob.  The same two LDS images per bin, the same tables; the masked head
-// gradient gf' is staged as 20 channels, D5 = gf' x W_head^T is one product with K = 20, and every layer below is the forward's
-// 3x3 product on the flipped and transposed weights, started from +0.  After a layer's product the image holds D; one pass over
-// it reads the stored activation, applies the mask, and writes G to the image and to `grads` in rows.
+// policy_trunk_grad_kernel: its sibling on the second blob.  The same two LDS images per bin, the same tables.  The masked head
+// gradient gf' is staged as 20 channels, D5 = gf' x W_head^T is one product with K = 20, and every layer below is
+// the forward's 3x3 product on the flipped and transposed weights, started from +0.  After a layer's product the image holds D;
+// one pass over it reads the stored activation, applies the mask, and writes G to the image and to `grads` in rows.
 //
 // policy_wgrad_kernel: kfac_partial_kernel's sibling with two staged operands.  A workgroup of four waves owns 64 rows k of one
 // layer's [K + 1][OC] gradient (a wave one 32 x 32 tile of the 2 x 2) and one split of the bins.  Per bin it stages the channels
@@ -16,7 +16,7 @@
 // bias: a plane of ones staged behind the channels, so db is the chain fmaf(1, g, acc).  The partial tiles go to the workspace;
 // policy_wgrad_reduce_kernel adds them per element in split order in double and casts once.
 //
-// g++ compiles this file too (tests/emu): policy_chain (bpp_policy.inl) and policy_wgrad_mac are the only functions that differ.
+// The tile -- accumulator, layout, the instruction and its emulated chain -- is bpp_mfma.inl's.  g++ compiles this file too (tests/emu); nothing in it differs between the two builds.
 
 namespace {
 
@@ -50,15 +50,6 @@ __host__ __device__ __forceinline__ int pt_channels(int layer) { return layer ==
 __host__ __device__ __forceinline__ int pt_taps(int layer) { return layer == 5 ? 1 : 9; }
 __host__ __device__ __forceinline__ int pt_outputs(int layer) { return layer == 5 ? kPolHeadC : kPolC; }
 __host__ __device__ __forceinline__ int pt_rows(int layer) { return pt_channels(layer) * pt_taps(layer) + 1; }     // K + 1: the bias row
-
-template <int NB>
-__device__ __forceinline__ void policy_zero(KfacAcc (&acc)[NB]) {
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc[t][s] = 0.0f;
-    }
-}
 
 // grid = ceil(n / P)
 __global__ __launch_bounds__(256) void policy_trunk_grad_kernel(PtGradArgs a) {
@@ -97,8 +88,8 @@ __global__ __launch_bounds__(256) void policy_trunk_grad_kernel(PtGradArgs a) {
         for (int pt = wave; pt < s.tiles; pt += 4) {
             const int *rt = rtab + pt * kPolTile;
             const int ro = rt[col];
-            KfacAcc acc[2];
-            policy_zero<2>(acc);
+            MfmaAcc acc[2];
+            mfma_fill(acc, [](int) { return 0.0f; });
             if (layer == 4)
                 policy_chain<2, 5>(acc, src + centre, rt, ro, nullptr, s.PP, kPolHeadC, a.wb + (size_t)4 * kPtBwdLayer, kPolC, 0, kPolC, lane);
             else
@@ -106,8 +97,8 @@ __global__ __launch_bounds__(256) void policy_trunk_grad_kernel(PtGradArgs a) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int row = pt * kPolTile + policy_slot_row(q, lane);
+                for (int q = 0; q < kMfmaSlots; ++q) {
+                    const int row = pt * kPolTile + mfma_slot_row(q, lane);
                     if (row < s.rows) dst[rtab[row] + (kPolTile * t + col) * s.PP + centre] = acc[t][q];
                 }
             }
@@ -136,29 +127,15 @@ __global__ __launch_bounds__(256) void policy_trunk_grad_kernel(PtGradArgs a) {
 
 // acc += A^T-by-B of rows r and r + 1 of the staged bin (row r + 1 counts as zeros when the bin ends at r):
 // acc[i][j] = fmaf(x[r + 1][i], g[r + 1][j], fmaf(x[r][i], g[r][j], acc[i][j])), x[r][i] = img[ta[i] + rtab[r]] the patch value of
-// feature i at position r, g[r][j] = gimg[tb[j] + r].  fa / fb: this lane's own ta[lane & 31] / tb[lane & 31].  Operand and
-// accumulator layout as kfac_mac (bpp_kfac.inl).
-__device__ __forceinline__ void policy_wgrad_mac(KfacAcc &acc, const float *img, const float *gimg, const int *ta, const int *tb, int fa, int fb,
+// feature i at position r, g[r][j] = gimg[tb[j] + r].  fa / fb: this lane's own ta[lane & 31] / tb[lane & 31].
+__device__ __forceinline__ void policy_wgrad_mac(MfmaAcc &acc, const float *img, const float *gimg, const int *ta, const int *tb, int fa, int fb,
                                                  const int *rtab, int r, int nr, int lane) {
-#ifdef BPP_EMU_HIP_RUNTIME_H
-    const int col = lane & 31, half = lane >> 5;
-    for (int k = 0; k < 2; ++k) {
-        const bool ok = r + k < nr;
-        const int ro = ok ? rtab[r + k] : 0;
-        const float b = ok ? gimg[tb[col] + r + k] : 0.0f;
-        for (int s = 0; s < 16; ++s) {
-            const int row = (s & 3) + 8 * (s >> 2) + 4 * half;
-            const float x = ok ? img[ta[row] + ro] : 0.0f;
-            acc[s] = fmaf(x, b, acc[s]);
-        }
-    }
-#else
-    const int k = r + (lane >> 5);
+    const int k = r + (lane >> 5);                    // the lane's own operands, the only ones the device fetches
     const bool ok = k < nr;
     const int kk = ok ? k : r;
     const float x = ok ? img[fa + rtab[kk]] : 0.0f, b = ok ? gimg[fb + kk] : 0.0f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x, b, acc, 0, 0, 0);
-#endif
+    mfma_step(acc, lane, x, b, [&](int i, int q) { return r + q < nr ? img[ta[i] + rtab[r + q]] : 0.0f; },
+              [&](int q, int j) { return r + q < nr ? gimg[tb[j] + r + q] : 0.0f; });
 }
 
 // grid = blocks x splits: workgroup g takes block g % blocks and split g / blocks
@@ -202,9 +179,9 @@ __global__ __launch_bounds__(256) void policy_wgrad_kernel(PtWgradArgs a) {
     const bool active = f0 + wi * kPolTile < K1 && wj * kPolTile < OC;
     const int *ta = ftab + wi * kPolTile, *tb = ftab + kPtBlock + wj * kPolTile;
     const int fa = ta[lane & 31], fb = tb[lane & 31];
-    KfacAcc acc;
+    MfmaAcc acc;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+    for (int k = 0; k < kMfmaSlots; ++k) acc[k] = 0.0f;
     const float *x = layer == 0 ? a.obs : a.acts + (size_t)(layer == 5 ? 4 : layer - 1) * (size_t)p.n * (size_t)CA;
     const size_t xstride = layer == 0 ? (size_t)a.obs_stride : (size_t)CA;
     const float *g = a.grads + (size_t)layer * (size_t)p.n * (size_t)CA;
@@ -231,7 +208,7 @@ __global__ __launch_bounds__(256) void policy_wgrad_kernel(PtWgradArgs a) {
     if (active) {
         float *out = a.part + (((size_t)split * (size_t)s.blocks + (size_t)blk) * 4u + (size_t)wave) * 1024u;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) out[k * kWave + lane] = acc[k];
+        for (int k = 0; k < kMfmaSlots; ++k) out[k * kWave + lane] = acc[k];
     }
 }
 
@@ -244,10 +221,8 @@ __global__ __launch_bounds__(256) void policy_wgrad_reduce_kernel(const float *p
     const int OC = pt_outputs(layer), idx = e - (int)(layer == 5 ? s.p.w_head_conv : s.p.w_conv[layer]);
     const int k = idx / OC, oc = idx - k * OC;
     const int blk = s.blk0[layer] + k / kPtBlock, wave = 2 * ((k % kPtBlock) / kPolTile) + oc / kPolTile;
-    const int i = k % kPolTile, j = oc % kPolTile;
-    const int q = ((i & 3) + 4 * (i >> 3)) * kWave + j + 32 * ((i >> 2) & 1);
     const size_t stride = (size_t)s.blocks * 4096u;
-    const float *at = part + ((size_t)blk * 4u + (size_t)wave) * 1024u + (size_t)q;
+    const float *at = part + ((size_t)blk * 4u + (size_t)wave) * 1024u + (size_t)mfma_stored_at(k % kPolTile, oc % kPolTile);
     double sum = 0.0;
     for (int sp = 0; sp < s.splits; ++sp) sum = sum + (double)at[(size_t)sp * stride];
     gw[e] = (float)sum;
@@ -307,13 +282,8 @@ int bpp_policy_trunk_forward_train(const float *obs, int64_t obs_stride, int32_t
     if (obs_stride < (int64_t)kPolIn * t.s.A) return ck.bad("obs_stride must be >= 4 A");
     const PolShape &s = t.s;
     t.obs = obs, t.obs_stride = obs_stride, t.w = weights, t.feat = feat, t.acts = acts;
-    if (s.trunk_lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_trunk_kernel<true>, raised, kPolLdsBytes);
-    }
-    hipLaunchKernelGGL(policy_trunk_kernel<true>, dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), (size_t)s.trunk_lds,
-                       (hipStream_t)stream, t);
-    return launched();
+    return launch_large_lds<policy_trunk_kernel<true>>(dim3((unsigned)(((long long)n + s.P - 1) / s.P)), dim3(256), s.trunk_lds, kPolLdsBytes,
+                                                       (hipStream_t)stream, t);
 }
 
 int bpp_policy_trunk_backward(const float *obs, int64_t obs_stride, int32_t n, const int32_t geom[], const float *weights_bwd, const float *feat,
@@ -329,19 +299,12 @@ int bpp_policy_trunk_backward(const float *obs, int64_t obs_stride, int32_t n, c
     const hipStream_t st = (hipStream_t)stream;
     PtGradArgs g;
     g.feat = feat, g.acts = acts, g.grad_feat = grad_feat, g.wb = weights_bwd, g.grads = grads, g.s = s.p;
-    if (s.p.trunk_lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_trunk_grad_kernel, raised, kPolLdsBytes);
-    }
-    hipLaunchKernelGGL(policy_trunk_grad_kernel, dim3((unsigned)(((long long)n + s.p.P - 1) / s.p.P)), dim3(256), (size_t)s.p.trunk_lds, st, g);
-    if (const int rc = launched()) return rc;
+    if (const int rc = launch_large_lds<policy_trunk_grad_kernel>(dim3((unsigned)(((long long)n + s.p.P - 1) / s.p.P)), dim3(256), s.p.trunk_lds,
+                                                                  kPolLdsBytes, st, g))
+        return rc;
     w.obs = obs, w.obs_stride = obs_stride, w.acts = acts, w.grads = grads, w.part = (float *)workspace;
-    if (s.wg_lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        raise_dynamic_lds(policy_wgrad_kernel, raised, kPolLdsBytes);
-    }
-    hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)s.blocks * (unsigned)s.splits), dim3(256), (size_t)s.wg_lds, st, w);
-    if (const int rc = launched()) return rc;
+    if (const int rc = launch_large_lds<policy_wgrad_kernel>(dim3((unsigned)s.blocks * (unsigned)s.splits), dim3(256), s.wg_lds, kPolLdsBytes, st, w))
+        return rc;
     const int floats = (int)s.p.w_lin[0][0];
     hipLaunchKernelGGL(policy_wgrad_reduce_kernel, dim3((unsigned)((floats + 255) / 256)), dim3(256), 0, st, (const float *)workspace, grad_weights,
                        s);

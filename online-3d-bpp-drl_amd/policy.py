@@ -154,13 +154,7 @@ def policy_forward(obs, weights, geom, want=HEADS):
     want = tuple(want)
     if not want or any(h not in HEADS for h in want):
         raise ValueError("want must name at least one of %r" % (HEADS,))
-    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
-        raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
-    if obs.device.type != "cuda":
-        raise RuntimeError("policy_forward needs its tensors on a HIP device")
-    n = int(obs.shape[0])
-    if obs.shape[1] < 4 * S * S or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * S * S):
-        raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * S * S))
+    n, stride = _check_obs(obs, S, "policy_forward")
     dev = obs.device
     g = _lib.kfac_geom((S, H, M))
     L = _lib.lib()
@@ -184,8 +178,8 @@ def policy_forward(obs, weights, geom, want=HEADS):
         logits = torch.empty((n, M), dtype=torch.float32, device=dev) if "logits" in want else None
         pred = torch.empty((n, M), dtype=torch.float32, device=dev) if "pred" in want else None
         ptr = [t.data_ptr() if t is not None else None for t in (value, logits, pred)]
-        _lib.check(L.bpp_policy_forward(obs.data_ptr(), int(obs.stride(0)) if n > 1 else int(obs.shape[1]), n, g, weights.data_ptr(),
-                                        ptr[0], ptr[1], ptr[2], ws.data_ptr(), ctypes.c_void_p(stream)))
+        _lib.check(L.bpp_policy_forward(obs.data_ptr(), stride, n, g, weights.data_ptr(), ptr[0], ptr[1], ptr[2], ws.data_ptr(),
+                                        ctypes.c_void_p(stream)))
     return value, logits, pred
 
 
@@ -313,11 +307,12 @@ def trunk_backward_info(geom, n, L=None):
     return dict(zip(_lib.POLICY_TRAIN_INFO, (int(v) for v in out)))
 
 
-def _check_obs(obs, S):
+def _check_obs(obs, S, who="the native trunk"):
+    """(n, floats between two rows) of an obs the native calls take; `who`: the subject of the wrong-device error."""
     if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
         raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
     if obs.device.type != "cuda":
-        raise RuntimeError("the native trunk needs its tensors on a HIP device")
+        raise RuntimeError("%s needs its tensors on a HIP device" % who)
     n = int(obs.shape[0])
     if obs.shape[1] < 4 * S * S or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * S * S):
         raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * S * S))
