@@ -63,6 +63,12 @@ ROLLOUT_SYMBOLS = ["bpp_compute_returns", "bpp_compute_returns_host", "bpp_compu
 # include/bpp_update.h: the same, for the fused loss of the A2C update
 UPDATE_SYMBOLS = ["bpp_a2c_loss", "bpp_a2c_loss_workspace", "bpp_a2c_loss_info"]
 A2C_TERMS = ("value_loss", "action_loss", "dist_entropy", "prob_loss", "graph_loss", "loss")
+# include/bpp_ppo.h: the same, for the PPO update (advantages, mini-batch gather, clipped loss)
+PPO_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_ppo.h")
+PPO_SYMBOLS = ["bpp_ppo_advantages", "bpp_ppo_advantages_workspace", "bpp_ppo_advantages_info", "bpp_gather_rows", "bpp_ppo_loss",
+               "bpp_ppo_loss_workspace", "bpp_ppo_loss_info"]
+PPO_TERMS = ("value_loss", "action_loss", "dist_entropy", "prob_loss", "graph_loss", "loss", "clip_fraction")
+PPO_ROWS = ("value_term", "action_term", "entropy", "bad", "sq", "ratio", "clipped")
 # include/bpp_kfac.h: the same, for the Kronecker factors of K-FAC
 KFAC_SYMBOLS = ["bpp_kfac_factor", "bpp_kfac_factor_workspace", "bpp_kfac_factor_info"]
 KFAC_PATCH, KFAC_ROWS, KFAC_NCHW = 0, 1, 2
@@ -254,6 +260,26 @@ def bind_update(L):
     L.bpp_a2c_loss_workspace.restype = ctypes.c_size_t
     L.bpp_a2c_loss_info.argtypes = [i32, i32, ctypes.POINTER(i32)]
     L.bpp_a2c_loss_info.restype = ctypes.c_int
+    return L
+
+
+def bind_ppo(L):
+    """Argument types of the PPO_SYMBOLS on library handle L."""
+    vp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+    L.bpp_ppo_advantages.argtypes = [vp] * 4 + [i32, vp, vp]
+    L.bpp_ppo_advantages.restype = ctypes.c_int
+    L.bpp_ppo_advantages_workspace.argtypes = [i32]
+    L.bpp_ppo_advantages_workspace.restype = ctypes.c_size_t
+    L.bpp_ppo_advantages_info.argtypes = [i32, ctypes.POINTER(i32)]
+    L.bpp_ppo_advantages_info.restype = ctypes.c_int
+    L.bpp_gather_rows.argtypes = [vp, i64, i64, vp, i32, i32, vp, vp]
+    L.bpp_gather_rows.restype = ctypes.c_int
+    L.bpp_ppo_loss.argtypes = [vp] * 10 + [f64] * 5 + [i32] + [vp] * 6 + [i32, i32, i32, vp]
+    L.bpp_ppo_loss.restype = ctypes.c_int
+    L.bpp_ppo_loss_workspace.argtypes = [i32, i32]
+    L.bpp_ppo_loss_workspace.restype = ctypes.c_size_t
+    L.bpp_ppo_loss_info.argtypes = [i32, i32, ctypes.POINTER(i32)]
+    L.bpp_ppo_loss_info.restype = ctypes.c_int
     return L
 
 
@@ -458,6 +484,7 @@ def lib():
         bind_mcts(L)
         bind_rollout(L)
         bind_update(L)
+        bind_ppo(L)
         bind_kfac(L)
         bind_policy(L)
         bind_policy_train(L)

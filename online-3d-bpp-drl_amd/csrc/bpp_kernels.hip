@@ -41,6 +41,7 @@
 #include "../../include/bpp_pipeline.h"
 #include "../../include/bpp_rollout.h"
 #include "../../include/bpp_update.h"
+#include "../../include/bpp_ppo.h"
 #include "../../include/bpp_kfac.h"
 #include "../../include/bpp_policy.h"
 #include "../../include/bpp_policy_train.h"
@@ -1638,6 +1639,7 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_mcts.inl"
 #include "bpp_returns.inl"
 #include "bpp_update.inl"
+#include "bpp_ppo.inl"
 #include "bpp_mfma.inl"
 #include "bpp_kfac.inl"
 #include "bpp_policy.inl"

@@ -10,6 +10,7 @@
 //
 // The sums of the five per-row terms are taken in double, without atomics, in an order fixed by E alone: a workgroup owns
 // `4 * iters` consecutive rows and publishes one partial, at most kA2cWidth partials exist, one final workgroup adds them.
+// LossRow, pred_mask_row, loss_rows, loss_sums, a2c_shape and a2c_regs are shared with the PPO loss (bpp_ppo.inl).
 
 namespace {
 
@@ -28,23 +29,31 @@ struct A2cArgs {
 // Row e through row_stats and row_terms (bpp_heads.inl): NJ > 0 entries per lane in registers (M <= 64 * NJ), NJ = 0 a row of
 // any length walked in memory.  out = {adv * adv, -(adv * logp), ent, bad, sq}, in every lane.
 template <int NJ>
-__device__ __forceinline__ void a2c_row(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
+using LossRow = std::conditional_t<(NJ > 0), RegRow<(NJ > 0) ? NJ : 1>, MemRow>;
+
+// The mask-prediction term of a row (shared with bpp_ppo.inl): sq = sum_k (pred[k] - mask[k])^2 in every lane, and
+// g_pred[k] = c_p (pred[k] - mask[k]).  pred and g_pred point at the row.
+template <int NJ>
+__device__ __forceinline__ float pred_mask_row(const LossRow<NJ> &row, const float *pred, float *g_pred, float c_p) {
     constexpr bool kRegs = NJ > 0;
+    float s = 0.0f;
+    float pv[kRegs ? NJ : 1];       // the register form: every load of the row is issued before any arithmetic
+    if constexpr (kRegs) row.each([&](int j, int k) { pv[j] = pred[k]; });
+    row.each([&](int j, int k) {
+        const float d = (kRegs ? pv[j] : pred[k]) - row.m(j, k);
+        s += d * d;
+        g_pred[k] = c_p * d;
+    });
+    return wave_sum(s);
+}
+
+template <int NJ>
+__device__ __forceinline__ void a2c_row(const A2cArgs &a, size_t e, int lane, float (&out)[5]) {
     const int M = a.M;
     const size_t off = e * (size_t)M;
     const float *x = a.logits + off, *m = a.mask + off;
-    std::conditional_t<kRegs, RegRow<kRegs ? NJ : 1>, MemRow> row(x, m, M, lane);
-    float s = 0.0f;
-    if (a.pred) {
-        float pv[kRegs ? NJ : 1];       // the register form: every load of the row is issued before any arithmetic
-        if constexpr (kRegs) row.each([&](int j, int k) { pv[j] = a.pred[off + k]; });
-        row.each([&](int j, int k) {
-            const float d = (kRegs ? pv[j] : a.pred[off + k]) - row.m(j, k);
-            s += d * d;
-            a.g_pred[off + k] = a.c_p * d;
-        });
-        s = wave_sum(s);
-    }
+    LossRow<NJ> row(x, m, M, lane);
+    const float s = a.pred ? pred_mask_row<NJ>(row, a.pred + off, a.g_pred + off, a.c_p) : 0.0f;
     const float adv = a.returns[e] - a.values[e];
     const HeadGrad w{a.action[e], -(adv * a.cE), a.g_ent, a.g_bad};
     float h, b;
@@ -55,56 +64,75 @@ __device__ __forceinline__ void a2c_row(const A2cArgs &a, size_t e, int lane, fl
     out[0] = adv * adv, out[1] = -(adv * logp), out[2] = h, out[3] = b, out[4] = s;
 }
 
-template <int NJ>
-__global__ __launch_bounds__(256) void a2c_loss_kernel(A2cArgs a) {
-    static __shared__ double part[4][5];
+// The sums of NC per-row terms, shared with bpp_ppo.inl.  loss_rows: a 256-lane workgroup owns rows [blockIdx.x 4 iters, + 4 iters) of
+// n, wave w takes rows w, w + 4, ...; fn(row, lane, out) computes a row's NC terms in every lane; they are added in double, stored
+// to rows[row][0 .. NC) when asked for, and the workgroup publishes ((w0 + w1) + w2) + w3 as partial[blockIdx.x][0 .. NC).
+template <int NC, typename RowFn>
+__device__ __forceinline__ void loss_rows(int n, int iters, float *rows, double *partial, double (*part)[NC], RowFn fn) {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    const size_t e0 = (size_t)blockIdx.x * 4u * (size_t)a.iters;
-    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < a.iters; ++i) {
+    const size_t e0 = (size_t)blockIdx.x * 4u * (size_t)iters;
+    double acc[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) acc[j] = 0.0;
+    for (int i = 0; i < iters; ++i) {
         const size_t e = e0 + 4u * (size_t)i + (size_t)wave;
-        if (e >= (size_t)a.E) break;       // a whole wave: its later rows lie further out still
-        float r[5];
-        a2c_row<NJ>(a, e, lane, r);
+        if (e >= (size_t)n) break;       // a whole wave: its later rows lie further out still
+        float r[NC];
+        fn(e, lane, r);
 #pragma unroll
-        for (int j = 0; j < 5; ++j) acc[j] = acc[j] + (double)r[j];
-        if (lane == 0 && a.rows) {
+        for (int j = 0; j < NC; ++j) acc[j] = acc[j] + (double)r[j];
+        if (lane == 0 && rows) {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) a.rows[e * 5 + j] = r[j];
+            for (int j = 0; j < NC; ++j) rows[e * NC + j] = r[j];
         }
     }
     if (lane == 0) {
 #pragma unroll
-        for (int j = 0; j < 5; ++j) part[wave][j] = acc[j];
+        for (int j = 0; j < NC; ++j) part[wave][j] = acc[j];
     }
     __syncthreads();
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < NC) {
         const int j = threadIdx.x;
-        a.partial[(size_t)blockIdx.x * 5 + j] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+        partial[(size_t)blockIdx.x * NC + j] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
     }
+}
+
+// loss_sums: ONE workgroup of kA2cWidth lanes adds the G partials of loss_rows; lane t takes partials t, t + kA2cWidth, ..., a
+// binary tree (stride kA2cWidth / 2, ..., 1) adds the lanes.  Afterwards part[j][0] is the sum of column j (valid in lane 0).
+template <int NC>
+__device__ __forceinline__ void loss_sums(const double *partial, int G, double (*part)[kA2cWidth]) {
+    const int t = threadIdx.x;
+    double s[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) s[j] = 0.0;
+    for (int gi = t; gi < G; gi += kA2cWidth) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) s[j] = s[j] + partial[(size_t)gi * NC + j];
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j) part[j][t] = s[j];
+    __syncthreads();
+    for (int d = kA2cWidth / 2; d > 0; d >>= 1) {
+        if (t < d) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) part[j][t] = part[j][t] + part[j][t + d];
+        }
+        __syncthreads();
+    }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void a2c_loss_kernel(A2cArgs a) {
+    static __shared__ double part[4][5];
+    loss_rows<5>(a.E, a.iters, a.rows, a.partial, part, [&](size_t e, int lane, float (&r)[5]) { a2c_row<NJ>(a, e, lane, r); });
 }
 
 // One workgroup: the G partials -> the six terms.
 __global__ __launch_bounds__(kA2cWidth) void a2c_terms_kernel(const double *partial, int G, int E, int M, double vc, double ec,
                                                               double ic, double mc, float *terms) {
     static __shared__ double part[5][kA2cWidth];
-    const int t = threadIdx.x;
-    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int gi = t; gi < G; gi += kA2cWidth) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) s[j] = s[j] + partial[(size_t)gi * 5 + j];
-    }
-#pragma unroll
-    for (int j = 0; j < 5; ++j) part[j][t] = s[j];
-    __syncthreads();
-    for (int d = kA2cWidth / 2; d > 0; d >>= 1) {
-        if (t < d) {
-#pragma unroll
-            for (int j = 0; j < 5; ++j) part[j][t] = part[j][t] + part[j][t + d];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
+    loss_sums<5>(partial, G, part);
+    if (threadIdx.x == 0) {
         const double n = (double)E, nm = (double)E * (double)M;
         const double value_loss = part[0][0] / n, action_loss = part[1][0] / n, dist_entropy = part[2][0] / n;
         const double prob_loss = part[3][0] / nm, graph_loss = part[4][0] / nm;

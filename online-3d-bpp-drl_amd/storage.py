@@ -197,6 +197,46 @@ class RolloutStorage(object):
                         s["returns"][:-1].view(T * N), **coefs)
 
 
+    # ------------------------------------------------------------------ PPO (acktr/algo/ppo.py; include/bpp_ppo.h)
+    def normalized_advantages(self):
+        """[T, N, 1]: (adv - adv.mean()) / (adv.std() + 1e-5) of adv = returns[:-1] - value_preds[:-1] (ppo.py:34-36).  A device
+        storage: one native call (bpp_ppo_advantages), the same bits on every run.  A CPU storage: these torch expressions in the
+        slabs' dtype."""
+        s = self._slabs
+        if self.device.type == "cuda":
+            from .ppo import normalized_advantages
+            return normalized_advantages(s["returns"][:-1], s["value_preds"][:-1])[0].unsqueeze(-1)
+        adv = s["returns"][:-1] - s["value_preds"][:-1]
+        return ((adv - adv.mean()) / (adv.std() + 1e-5)).unsqueeze(-1)
+
+    def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, generator=None):
+        """The reference's generator (acktr/storage.py:113-149): mini-batches of rows of [:-1] in the order of
+        BatchSampler(SubsetRandomSampler(range(T * N)), mini_batch_size, drop_last=True) -- torch.randperm(T * N) on the CPU cut
+        into chunks, the remainder dropped, so the same torch seed gives the same mini-batches.  Each item is a ppo.MiniBatch."""
+        from .ppo import MiniBatch
+        num_steps, num_processes = self.num_steps, self.num_envs
+        batch_size = num_processes * num_steps
+        if mini_batch_size is None:
+            assert batch_size >= num_mini_batch, (
+                "PPO requires the number of processes ({}) * number of steps ({}) = {} to be greater than or equal to the number of "
+                "PPO mini batches ({}).".format(num_processes, num_steps, num_processes * num_steps, num_mini_batch))
+            mini_batch_size = batch_size // num_mini_batch
+        perm = torch.randperm(batch_size, generator=generator).to(self.device)
+        for i in range(batch_size // mini_batch_size):
+            yield MiniBatch(self, perm[i * mini_batch_size:(i + 1) * mini_batch_size], advantages)
+
+    def ppo_loss(self, logits, values, pred_mask, batch, advantages, **kw):
+        """The loss of one PPO mini-batch and its gradients (ppo.ppo_loss): logits [B, M], values [B, 1] and pred_mask [B, M] or
+        None are the network's outputs on batch.obs_batch; the slabs and batch.indices are handed over as they are, nothing of the
+        rollout is gathered.  A CPU storage states the same in torch (ppo.ppo_loss_torch)."""
+        from .ppo import ppo_loss, ppo_loss_torch
+        s, T, N = self._slabs, self.num_steps, self.num_envs
+        fn = ppo_loss if self.device.type == "cuda" else ppo_loss_torch
+        return fn(logits, values, pred_mask, s["location_masks"][:-1].view(T * N, -1), s["actions"].view(T * N),
+                  s["value_preds"][:-1].view(T * N), s["returns"][:-1].view(T * N), s["action_log_probs"].view(T * N),
+                  advantages.reshape(T * N), indices=batch.indices if batch is not None else None, **kw)
+
+
 class _Step(int):
     """`storage.step`: the reference's integer attribute -- and callable, `storage.step(env, actions, value, action_log_prob)`
     being the zero-copy lock-step (RolloutStorage.lockstep)."""
