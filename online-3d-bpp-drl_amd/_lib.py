@@ -93,6 +93,11 @@ PLACEMENT_SYMBOLS = ["bpp_placements_sizes", "bpp_placements_clear", "bpp_placem
 PLAN_RUNNING, PLAN_FINISHED = 0, 1                   # BPP_PLAN_*
 PLACEMENT_BYTES, PLACEMENTS_MAX_CAPACITY = 8, 1 << 20
 PLACEMENTS_INFO = ("step_lanes", "step_groups", "plan_waves", "plan_groups", "replay_cells_per_lane", "record_bytes")
+# include/bpp_heuristic.h: the same, for the lowest-top packing heuristic
+HEURISTIC_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_heuristic.h")
+HEURISTIC_SYMBOLS = ["bpp_heuristic_act", "bpp_heuristic_act_info"]
+HEURISTIC_RULES = {"lowest_top": 0, "lowest_top_plain": 1}      # BPP_HEUR_*
+HEURISTIC_INFO = ("bins_per_wave", "lds_bytes", "workgroups", "path")
 
 
 class Batch(ctypes.Structure):
@@ -361,6 +366,23 @@ def bind_placements(L, batch=None):
     return L
 
 
+def bind_heuristic(L):
+    """Argument types of the HEURISTIC_SYMBOLS on library handle L."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    L.bpp_heuristic_act.argtypes = [vp, ctypes.c_int64, vp] + [i32] * 5 + [vp, vp, vp]
+    L.bpp_heuristic_act_info.argtypes = [i32] * 4 + [ctypes.POINTER(i32)]
+    for name in HEURISTIC_SYMBOLS:
+        getattr(L, name).restype = ctypes.c_int
+    return L
+
+
+def heuristic_info(size, rotation, n, L=None):
+    """bpp_heuristic_act_info: the launch shape of the heuristic for a geometry and n bins, as a dict."""
+    out = (ctypes.c_int32 * 4)()
+    check((L or lib()).bpp_heuristic_act_info(int(size[0]), int(size[1]), int(bool(rotation)), int(n), out), L)
+    return dict(zip(HEURISTIC_INFO, (int(v) for v in out)))
+
+
 def placements_info(E, capacity, A, L=None):
     """bpp_placements_info: the launch shapes of the plan kernels, as a dict."""
     out = (ctypes.c_int32 * 6)()
@@ -490,6 +512,7 @@ def lib():
         bind_policy_train(L)
         bind_stream_kinds(L)
         bind_placements(L)
+        bind_heuristic(L)
         if L.bpp_abi_version() != ABI_VERSION:
             raise RuntimeError("libbpp_hip.so ABI version %d != %d" % (L.bpp_abi_version(), ABI_VERSION))
         _lib = L

@@ -47,6 +47,7 @@
 #include "../../include/bpp_policy_train.h"
 #include "../../include/bpp_stream_kinds.h"
 #include "../../include/bpp_placements.h"
+#include "../../include/bpp_heuristic.h"
 #include "../../include/bpp_gen.inl"
 
 #include <atomic>
@@ -1645,3 +1646,4 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_policy.inl"
 #include "bpp_policy_train.inl"
 #include "bpp_placements.inl"
+#include "bpp_heuristic.inl"

@@ -9,6 +9,11 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
     return v;
 }
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, kWave));
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, kWave));

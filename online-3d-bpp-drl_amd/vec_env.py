@@ -861,6 +861,23 @@ class BppVecEnv(BranchOps):
             _lib.check(rc)
         return out
 
+    def heuristic_act(self, rule="lowest_top", out=None, top=None):
+        """The lowest-top heuristic's action per bin (bpp_heuristic_act, include/bpp_heuristic.h) on the env's current observation
+        and mask, int64 [E] on the device, enqueued on the env's stream.  rule: "lowest_top" (then smoothest surface, then lowest
+        index) or "lowest_top_plain"; top: int32 [E] tensor that receives the chosen top."""
+        from .heuristic import check_outputs, rule_id
+        res = self._res
+        if res is None or res.mask is None:
+            raise RuntimeError("no observation and mask available (reset() first; compute_mask=False?)")
+        r = rule_id(rule)
+        out, top = check_outputs(self.E, res.obs.device, out, top)
+        self._on_device()
+        rc = self.lib.bpp_heuristic_act(res.obs.data_ptr(), self.obs_len, res.mask.data_ptr(), self.E, self.W, self.L, int(self.can_rotate), r,
+                                        out.data_ptr(), top.data_ptr() if top is not None else None, self._stream_ptr())
+        if rc:
+            _lib.check(rc)
+        return out
+
     def epsilon_override(self, actions, seed, step, eps):
         """bpp_epsilon_override on an int64 [E] device tensor of actions, in place: with probability `eps` a bin's action
         becomes a uniform draw over all act_len entries (the failure-path variant of the benchmark policy)."""
