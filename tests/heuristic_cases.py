@@ -20,8 +20,18 @@ CANARY64, CANARY32 = np.int64(-0x5a5a5a5a5a5a5a5b), np.int32(-0x5a5a5a5b)
 # every geometry of the edge cases: ((W, L, H), rotation)
 GEOMS = [((10, 10, 10), False), ((10, 10, 10), True), ((20, 20, 20), True), ((7, 13, 8), True), ((5, 4, 6), False), ((1, 1, 3), False),
          ((4, 4, 255), False), ((32, 32, 10), False)]
+# the kernel takes 16 lanes per bin up to A = 128 and a wave per bin beyond: A = 128 in four shapes (path 0), 129 and 130 (path 1);
+# the largest M and LDS layout (32 x 32 with rotation); strips, where one side of the item can exceed the bin's other dimension;
+# heights and z at 255 on the wave-per-bin path
+GEOMS += [((8, 16, 10), True), ((16, 8, 10), False), ((128, 1, 5), True), ((1, 128, 5), True), ((3, 43, 6), True), ((43, 3, 6), False),
+          ((10, 13, 9), True), ((32, 32, 10), True), ((255, 4, 12), True), ((4, 255, 12), True), ((1, 255, 4), True), ((12, 12, 255), True)]
 GEOM_IDS = ["%dx%dx%d%s" % (s + ("r" if r else "",)) for s, r in GEOMS]
 BATCHES = (1, 3, 63, 65, 257)
+# geometries of the batch-size tests and of the carved-rows / top = NULL tests, the first three of each from the outset
+BATCH_GEOMS = [((10, 10, 10), True), ((20, 20, 20), True), ((7, 13, 8), True), ((8, 16, 10), True), ((3, 43, 6), True), ((32, 32, 10), True)]
+BATCH_IDS = ["10r", "20r", "7x13r", "8x16r", "3x43r", "32r"]
+CARVED_GEOMS = [((10, 10, 10), True), ((20, 20, 20), False), ((5, 4, 6), False), ((8, 16, 10), True), ((255, 4, 12), True)]
+CARVED_IDS = ["10r", "20", "5x4", "8x16r", "255x4r"]
 # the recorded deep states: name -> (rows, then the issue's four bounds: share of rows with more than one tied entry, share of rows
 # where the smooth rule picks another action than the plain one, all-ones fallback rows, most tied entries on one row)
 DEEP = {"rollout_deep_cut2_10": (1920, 0.80, 0.30, 10, 81), "rollout_deep_cut2_10_rot": (1920, 0.80, 0.30, 10, 162),
@@ -189,6 +199,19 @@ def check_rows(run, obs, mask, size, rotation, names=None):
         np.testing.assert_array_equal(top, want[1])
 
 
+def check_batches(run, size, rotation):
+    """check_rows at every batch size of BATCHES.  batch_rows(n) is the first n rows of batch_rows(max): the oracle runs once, on the
+    largest batch, and every smaller batch is held to its first rows."""
+    obs, mask = batch_rows(size, rotation, max(BATCHES))
+    want = {r: expected(obs, mask, size, rotation, r) for r in RULES}
+    for n in BATCHES:
+        o, m = np.ascontiguousarray(obs[:n]), np.ascontiguousarray(mask[:n])
+        for r in RULES:
+            act, top = run(o, m, size, rotation, r)
+            np.testing.assert_array_equal(act, want[r][0][:n], err_msg="%s %s: %d rows" % (size, r, n))
+            np.testing.assert_array_equal(top, want[r][1][:n])
+
+
 def check_independence(run, size, rotation):
     """A row gives the same action alone, first, in the middle and last of a batch."""
     obs, mask = batch_rows(size, rotation, 70)
@@ -262,10 +285,11 @@ def host_runner(L, want_top=True):
 
 
 class Fenced(object):
-    """A copy of a float32 array that ends exactly where an inaccessible page begins: a read past its end is a host fault."""
+    """A copy of an array (float32 unless told otherwise) that ends exactly where an inaccessible page begins: a read past its end
+    is a host fault.  tests/test_ppo.py fences the gather's source and indices with it as well."""
 
-    def __init__(self, arr):
-        arr = np.ascontiguousarray(arr, np.float32)
+    def __init__(self, arr, dtype=np.float32):
+        arr = np.ascontiguousarray(arr, dtype)
         page = mmap.PAGESIZE
         size = (arr.nbytes + page - 1) // page * page
         self.map = mmap.mmap(-1, size + page)
@@ -274,7 +298,7 @@ class Fenced(object):
         libc.mprotect.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
         if libc.mprotect(base + size, page, 0) != 0:
             raise OSError(ctypes.get_errno(), "mprotect")
-        self.array = np.frombuffer(self.map, np.float32, arr.size, size - arr.nbytes).reshape(arr.shape)
+        self.array = np.frombuffer(self.map, arr.dtype, arr.size, size - arr.nbytes).reshape(arr.shape)
         self.array[...] = arr
 
 
@@ -307,3 +331,43 @@ def check_info(L):
             per_bin = (A + 3) // 4 * 4 + (M + 3) // 4 * 4 + (2 * M + 3) // 4 * 4
             assert got == dict(bins_per_wave=bpw, lds_bytes=4 * bpw * per_bin, workgroups=(n + 4 * bpw - 1) // (4 * bpw), path=int(A > 128)), (size, n, got)
             assert got["lds_bytes"] <= 64 * 1024
+    # both sides of the switch, and the largest layout, by name
+    assert info(L, (8, 16, 10), True, 1)["path"] == 0 and info(L, (128, 1, 5), True, 1)["path"] == 0
+    assert info(L, (3, 43, 6), True, 1)["path"] == 1 and info(L, (43, 3, 6), False, 1)["path"] == 1
+    big = info(L, (32, 32, 10), True, 1)
+    assert big["path"] == 1 and big["lds_bytes"] == 4 * (1024 + 2048 + 2 * 2048) <= 64 * 1024
+
+
+# ------------------------------------------------------------------------------------------------------ a small bin enumerated
+ENUM_SIZE = (3, 3, 4)
+FOOTPRINTS = [(x, y) for x in (1, 2, 3) for y in (1, 2, 3)]
+
+
+def enumerated_rows(levels):
+    """Every heightmap of the 3 x 3 bin with heights below `levels`, rotation on, the mask all ones, items (x, y, 1).
+    levels = 3: the 3^9 = 19 683 maps, map i with footprint number i mod 9.  levels = 2: the 2^9 maps times all nine footprints.
+    -> (obs [n, 36], mask [n, 18], least share of rows on which the two rules must differ, from the oracle alone)."""
+    maps = (np.arange(levels ** 9)[:, None] // levels ** np.arange(9)[None, :]) % levels
+    if levels == 3:
+        item = np.arange(len(maps)) % 9
+    else:
+        maps, item = np.repeat(maps, 9, axis=0), np.tile(np.arange(9), len(maps))
+    fp = np.array(FOOTPRINTS)[item]
+    obs = np.empty((len(maps), 36), np.float32)
+    obs[:, :9] = maps
+    obs[:, 9:18], obs[:, 18:27], obs[:, 27:] = fp[:, :1], fp[:, 1:], 1.0
+    return obs, np.ones((len(maps), 18), np.float32), {3: 0.25, 2: 0.30}[levels]
+
+
+def check_enumerated(run, levels):
+    """Both rules on the whole enumeration, one call each; before that, from the oracle alone, that the smooth rule decides
+    otherwise than the plain one on the stated share of rows (so the score R(m) - R(h) cannot go unexercised)."""
+    obs, mask, share = enumerated_rows(levels)
+    want = {r: expected(obs, mask, ENUM_SIZE, True, r) for r in RULES}
+    differ = (want["lowest_top"][0] != want["lowest_top_plain"][0]).mean()
+    print("3x3 bin, heights below %d: %d rows, smooth != plain on %.1f %%" % (levels, obs.shape[0], 100 * differ))
+    assert differ >= share
+    for r in RULES:
+        act, top = run(obs, mask, ENUM_SIZE, True, r)
+        np.testing.assert_array_equal(act, want[r][0], err_msg="enumerated, %s" % r)
+        np.testing.assert_array_equal(top, want[r][1])

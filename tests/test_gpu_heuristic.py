@@ -59,14 +59,12 @@ def test_gpu_edge_rows_of_every_geometry(size, rotation):
     hc.check_rows(run, obs[:1], mask[:1], size, rotation, names[:1])
 
 
-@pytest.mark.parametrize("size,rotation", [((10, 10, 10), True), ((20, 20, 20), True), ((7, 13, 8), True)], ids=["10r", "20r", "7x13r"])
+@pytest.mark.parametrize("size,rotation", hc.BATCH_GEOMS, ids=hc.BATCH_IDS)
 def test_gpu_batch_sizes_with_tails_in_a_wave_a_workgroup_and_a_block_of_bins(size, rotation):
-    for n in hc.BATCHES:
-        obs, mask = hc.batch_rows(size, rotation, n)
-        hc.check_rows(run, obs, mask, size, rotation)
+    hc.check_batches(run, size, rotation)
 
 
-@pytest.mark.parametrize("size,rotation", [((10, 10, 10), True), ((20, 20, 20), False), ((5, 4, 6), False)], ids=["10r", "20", "5x4"])
+@pytest.mark.parametrize("size,rotation", hc.CARVED_GEOMS, ids=hc.CARVED_IDS)
 def test_gpu_rows_carved_from_a_wider_tensor_with_nan_padding_and_top_null(size, rotation):
     import bpp_amd
     W, L, H, A, M = hc.dims(size, rotation)
@@ -86,6 +84,11 @@ def test_gpu_rows_carved_from_a_wider_tensor_with_nan_padding_and_top_null(size,
             bpp_amd.heuristic_act(bad, dev(mask), size, rotation)
     with pytest.raises(ValueError):
         bpp_amd.heuristic_act(dev(obs), dev(mask)[:, :-1], size, rotation)
+
+
+@pytest.mark.parametrize("levels", [2, 3], ids=["binary-times-footprints", "ternary"])
+def test_gpu_a_three_by_three_bin_enumerated_completely(levels):
+    hc.check_enumerated(run, levels)
 
 
 # ------------------------------------------------------------------------------------------------------------------- 3. garbage

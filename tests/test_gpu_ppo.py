@@ -53,6 +53,34 @@ def test_gpu_ppo_loss_pieces_terms_and_float64(B, M):
             assert np.array_equal(pc.bits(other[k]), pc.bits(out[k])), k
 
 
+# ------------------------------------------------------------------------ the sizes that select a form, and off-contract rows
+@pytest.mark.parametrize("M", pc.PPO_MS)
+@pytest.mark.parametrize("B", pc.PPO_BS)
+def test_gpu_ppo_loss_at_every_form_and_on_both_sides_of_every_edge(B, M):
+    c = pc.edge_case(B, M)
+    out = run_device(c, coefs=pc.ALL_COEFS)
+    err = pc.check_edge(out, c, lib_info(B, M), dev_evaluate, dev_backward)
+    print("ratio: max relative error against float64 exp (device) = %.3g" % err)
+    again = run_device(c, coefs=pc.ALL_COEFS)
+    dense = run_device(pc.gathered(c), coefs=pc.ALL_COEFS)
+    null = run_device(pc.gathered(c), coefs=pc.ALL_COEFS, idx="null")
+    for k in KEYS:
+        for other in (again, dense, null):
+            assert np.array_equal(pc.bits(other[k]), pc.bits(out[k])), k
+
+
+@pytest.mark.parametrize("M", pc.ACTION_MS)
+def test_gpu_ppo_loss_actions_outside_the_row_are_no_entry_of_it(M):
+    """The device's expf and logf are not libm's: the evaluate and backward kernels are the comparator here, the statement that reads
+    nothing of a kernel runs on the emulator (tests/test_ppo.py)."""
+    pc.check_bad_actions(M, lambda c: run_device(c, coefs=pc.ALL_COEFS), lib_info(9, M), dev_evaluate, dev_backward)
+
+
+@pytest.mark.parametrize("B,M", pc.SCALAR_SHAPES)
+def test_gpu_ppo_loss_off_contract_scalars_stay_in_their_row_and_clips_outside_the_usual_range(B, M):
+    pc.check_off_contract_scalars(B, M, lambda c, clip: run_device(c, clip=clip, coefs=pc.ALL_COEFS), lib_info(B, M), dev_evaluate, dev_backward)
+
+
 @pytest.mark.parametrize("clipped_value,pred", [(True, False), (False, True), (False, False)])
 def test_gpu_ppo_loss_other_value_loss_and_no_pred_mask(clipped_value, pred):
     for B, M in ((5, 37), (9, 600)):
@@ -195,7 +223,55 @@ def test_gpu_advantages_bit_for_bit_on_two_streams_and_in_a_replayed_graph():
         assert torch.equal(got.view(torch.int32), want.view(torch.int32))
 
 
+def adv_info(E):
+    import ctypes
+    from bpp_amd import _lib
+    out = (ctypes.c_int32 * 3)()
+    assert _lib.lib().bpp_ppo_advantages_info(E, out) == 0
+    return list(out)
+
+
+@pytest.mark.parametrize("E", pc.ADV_EDGES)
+def test_gpu_advantages_at_the_block_shape_change(E):
+    import bpp_amd
+    C, G, W = adv_info(E)
+    assert [C, G, W] == pc.adv_shape_rule(E)
+    ret, vp = pc.advantages_case(E)
+    adv, stats = bpp_amd.normalized_advantages(dev(ret), dev(vp))
+    pc.check_advantages(adv.cpu().numpy(), stats.cpu().numpy(), ret, vp, C, W)
+
+
+@pytest.mark.parametrize("E", [320, 256 * 1024])
+def test_gpu_advantages_of_equal_raw_values_are_zero_and_a_large_offset_keeps_the_float64_bound(E):
+    import bpp_amd
+    C, G, W = adv_info(E)
+    ret, vp = pc.advantages_constant(E)
+    adv, stats = bpp_amd.normalized_advantages(dev(ret), dev(vp))
+    pc.check_advantages_constant(adv.cpu().numpy(), stats.cpu().numpy())
+    ret, vp = pc.advantages_offset(E)
+    adv, stats = bpp_amd.normalized_advantages(dev(ret), dev(vp))
+    pc.check_advantages(adv.cpu().numpy(), stats.cpu().numpy(), ret, vp, C, W)
+
+
 # -------------------------------------------------------------------------------------------------------------------- gather
+@pytest.mark.parametrize("n", pc.GATHER_LENS)
+def test_gpu_gather_rows_at_the_part_boundary(n):
+    """Dense rows and a padded stride, every window of ppo_cases.GATHER_SEQ as the indices, guards on both sides of dst.  (On the
+    emulator the source and the indices end at an inaccessible page: tests/test_ppo.py.)"""
+    import bpp_amd
+    for pad in (0, 1000):
+        src, stride = pc.gather_edge_case(n, pad)
+        view = dev(src)[:, :n]
+        assert view.stride(0) == stride
+        for B in pc.GATHER_BS:
+            for idx in pc.gather_index_vectors(B):
+                wd = dev(pc.guarded((B, n))[0])
+                bpp_amd.gather_rows(view, dev(idx), out=wd[pc.GUARD:pc.GUARD + B * n].view(B, n))
+                back = wd.cpu().numpy()
+                assert pc.guards_intact(back), (pad, B, idx)
+                assert pc.same_or_nan(back[pc.GUARD:-pc.GUARD].reshape(B, n), pc.gather_expected(src, idx, n)), (pad, B, idx)
+
+
 @pytest.mark.parametrize("n", [1, 3, 400, 1600])
 @pytest.mark.parametrize("B", [1, 65])
 def test_gpu_gather_rows_bit_for_bit_with_guards(B, n):
@@ -277,6 +353,31 @@ def test_gpu_update_reproduces_the_recorded_update_of_the_reference(golden):
     tol = pc.forward_tolerances(int(golden["shape"][2]))
     for j, atol in enumerate((4 * pc.EPS * abs(golden["means"][0]), tol[0], tol[1])):
         assert abs(means[j] - golden["means"][j]) <= 8 * abs(means32[j] - golden["means"][j]) + atol, j
+
+
+def test_gpu_update_at_m_400_with_every_coefficient_a_pred_mask_and_two_mini_batch_shapes():
+    """Two PPO.update calls on a synthetic rollout (ppo_cases.UPDATE: M = 400, T N = 38 rows, every coefficient non-zero, a network
+    that returns a pred_mask; 4 and then 3 mini-batches, so two (B, M) entries of the buffer cache).  The reference is the same
+    update in float64 on the CPU through ppo_loss_torch; the margin is the rule of the recorded update above: the float32 CPU twin's
+    distance from the float64 run is measured, the native update gets 8 times it."""
+    from bpp_amd import ppo
+    want_means, want = pc.run_update(torch.float64, "cpu")
+    means32, twin = pc.run_update(torch.float32, "cpu")
+    means, got = pc.run_update(torch.float32, "cuda:0")
+    M = pc.UPDATE["M"]
+    shapes = {(k[1], k[2]) for k in ppo._CACHE if k[2] == M}
+    assert {(38 // mini, M) for mini in pc.UPDATE["mini"]} <= shapes, shapes
+    print("means native", means, "float32 torch", means32, "float64 torch", want_means)
+    init = pc.update_data()["init"]
+    for k in want:
+        d_native, d_torch = np.abs(got[k] - want[k]).max(), np.abs(twin[k] - want[k]).max()
+        print("%s: max |native - float64| = %.3g, max |float32 torch - float64| = %.3g" % (k, d_native, d_torch))
+        assert d_native <= 8 * d_torch, k
+        assert np.abs(want[k] - init[k].numpy()).max() > 1e-3, k           # it did move
+    tol = pc.forward_tolerances(M)
+    for j in range(6):
+        atol = (4 * pc.EPS * abs(want_means[j]), tol[0], tol[1])[j % 3]
+        assert abs(means[j] - want_means[j]) <= 8 * abs(means32[j] - want_means[j]) + atol, j
 
 
 def test_gpu_example_trains_with_ppo():

@@ -61,14 +61,42 @@ def test_the_edge_rows_are_what_their_names_say():
     assert act[row["index A on and best"]] == 100 and K[row["index A on and best"]][:100].min() < hc.BIG
 
 
-@pytest.mark.parametrize("size,rotation", [((10, 10, 10), True), ((20, 20, 20), True), ((7, 13, 8), True)], ids=["10r", "20r", "7x13r"])
+@pytest.mark.parametrize("size,rotation", hc.GEOMS, ids=hc.GEOM_IDS)
+def test_the_edge_rows_are_what_their_names_say_at_every_geometry(size, rotation):
+    """The same properties from the oracle alone, stated for any geometry: at a strip the rotated footprint of an item "wider than
+    the bin" may fit along the other dimension, and a row strip (W, 1) has a rotated footprint only where W <= L."""
+    W, L, H, A, M = hc.dims(size, rotation)
+    names, obs, mask = hc.edge_rows(size, rotation)
+    K = hc.keys(obs, mask, size, rotation)
+    best = K.min(axis=1)
+    act = hc.expected(obs, mask, size, rotation, "lowest_top")[0]
+    row = {n: i for i, n in enumerate(names)}
+    places = lambda fx, fy: max(0, W - fx + 1) * max(0, L - fy + 1)                     # noqa: E731
+    sx, sy = max(1, W // 3), max(1, L // 2)
+    r = row["empty bin: everything ties"]
+    assert (K[r] == best[r]).sum() == places(sx, sy) + (places(sy, sx) if rotation else 0) and act[r] in (0, A)      # a corner
+    assert best[row["full bin, the terminator as item"]] == 2 * H and best[row["mask all off"]] == hc.BIG + 1 and act[row["mask all off"]] == 0
+    r = row["mask on only at out-of-range entries"]
+    assert best[r] == hc.BIG and act[r] == np.flatnonzero(mask[r] > 0.5)[0]
+    assert best[row["item with a zero side"]] == hc.BIG
+    assert (best[row["item wider than the bin"]] == hc.BIG) == (not (rotation and W + 1 <= L))
+    assert (best[row["item longer than the bin"]] == hc.BIG) == (not (rotation and L + 1 <= W))
+    assert best[row["heights and z at their largest"]] == 2 * min(H, 255)
+    if rotation:
+        assert act[row["x = y: the halves tie, the unrotated one wins"]] < A and act[row["x = y on random heights"]] < A
+        if 1 < W <= L:
+            r = row["only the rotated footprint fits"]
+            assert act[r] == A and (mask[r][:A] == 0).all()
+            r = row["index A on and best"]
+            assert act[r] == A and K[r][:A].min() < hc.BIG and K[r][A] == 1 < K[r][:A].min()
+
+
+@pytest.mark.parametrize("size,rotation", hc.BATCH_GEOMS, ids=hc.BATCH_IDS)
 def test_batch_sizes_with_tails_in_a_wave_a_workgroup_and_a_block_of_bins(run, size, rotation):
-    for n in hc.BATCHES:
-        obs, mask = hc.batch_rows(size, rotation, n)
-        hc.check_rows(run, obs, mask, size, rotation)
+    hc.check_batches(run, size, rotation)
 
 
-@pytest.mark.parametrize("size,rotation", [((10, 10, 10), True), ((20, 20, 20), False), ((5, 4, 6), False)], ids=["10r", "20", "5x4"])
+@pytest.mark.parametrize("size,rotation", hc.CARVED_GEOMS, ids=hc.CARVED_IDS)
 def test_rows_carved_from_a_wider_tensor_with_nan_padding_and_top_null(emu_lib, run, size, rotation):
     W, L, H, A, M = hc.dims(size, rotation)
     obs, mask = hc.batch_rows(size, rotation, 21)
@@ -78,6 +106,11 @@ def test_rows_carved_from_a_wider_tensor_with_nan_padding_and_top_null(emu_lib, 
         hc.check_rows(run, wide[:, before:before + 4 * A], mask, size, rotation)
     no_top = hc.host_runner(emu_lib, want_top=False)
     hc.check_rows(lambda *a: (no_top(*a)[0], run(*a)[1]), obs, mask, size, rotation)
+
+
+@pytest.mark.parametrize("levels", [2, 3], ids=["binary-times-footprints", "ternary"])
+def test_a_three_by_three_bin_enumerated_completely(run, levels):
+    hc.check_enumerated(run, levels)
 
 
 # ------------------------------------------------------------------------------------------------------------------- 3. garbage

@@ -3,6 +3,8 @@ SIMT emulator, and the host logic of bpp_amd.ppo / RolloutStorage on CPU tensors
 bpp_masked_evaluate kernels and the header's numpy statement bit for bit, against float64 autograd of the reference's
 expressions, torch's tie rules, the advantages and the gather bit for bit, the mini-batch generator against torch's samplers
 and the live reference's, and PPO.update against the recording of the reference's own (tests/golden/make_ppo_golden.py).
+Every entry point also at the sizes that select its form (ppo_cases.PPO_MS, GATHER_LENS, ADV_EDGES), the loss row against a
+statement that reads nothing of a kernel, and rows with actions and scalars outside the contract.
 Helpers and tolerances: tests/ppo_cases.py."""
 import ctypes
 import os
@@ -17,6 +19,7 @@ from bpp_amd import _lib
 from oracle import ref_shims
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import heuristic_cases as hc  # noqa: E402
 import ppo_cases as pc  # noqa: E402
 from conftest import load_golden  # noqa: E402
 
@@ -71,6 +74,40 @@ def test_loss_at_one_row_more_than_a_workgroup_holds(emu, emu_lib):
     assert out["rc"] == 0 and out["guards"] and pc.info(emu_lib, B, 37)[1] == 2
     pc.check_pieces(out, c, emu.masked_evaluate, emu.masked_evaluate_backward)
     pc.check_terms(out, c, pc.info(emu_lib, B, 37))
+
+
+# ------------------------------------------------------------------------ the sizes that select a form, and off-contract rows
+@pytest.mark.parametrize("M", pc.PPO_MS)
+@pytest.mark.parametrize("B", pc.PPO_BS)
+def test_loss_at_every_form_and_on_both_sides_of_every_edge(emu, emu_lib, results, B, M):
+    c, out = results(B, M)
+    assert c["E"] == B + 5
+    err = pc.check_edge(out, c, pc.info(emu_lib, B, M), emu.masked_evaluate, emu.masked_evaluate_backward)
+    print("ratio: max relative error against float64 exp (emulator) = %.3g" % err)
+    dense = pc.run_host(emu_lib, pc.gathered(c), coefs=pc.ALL_COEFS)
+    null = pc.run_host(emu_lib, pc.gathered(c), coefs=pc.ALL_COEFS, idx="null")
+    for k in ("terms",) + pc.OUT_KEYS:
+        assert np.array_equal(pc.bits(dense[k]), pc.bits(out[k])) and np.array_equal(pc.bits(null[k]), pc.bits(out[k])), k
+    assert pc.ok(dense) and pc.ok(null)
+
+
+@pytest.mark.parametrize("M", pc.PPO_MS)
+def test_the_whole_row_against_a_statement_that_reads_nothing_of_a_kernel(emu_lib, results, M):
+    """The emulator's expf and logf are libm's, as tests/head_normative.py's are: logp, the ratio and everything behind it bit for bit."""
+    c, out = results(5, M)
+    pc.check_normative(out, c, coefs=pc.ALL_COEFS)
+
+
+@pytest.mark.parametrize("M", pc.ACTION_MS)
+def test_actions_outside_the_row_are_no_entry_of_it(emu, emu_lib, M):
+    pc.check_bad_actions(M, lambda c: pc.run_host(emu_lib, c, coefs=pc.ALL_COEFS), pc.info(emu_lib, 9, M), emu.masked_evaluate,
+                         emu.masked_evaluate_backward, normative=True)
+
+
+@pytest.mark.parametrize("B,M", pc.SCALAR_SHAPES)
+def test_off_contract_scalars_stay_in_their_row_and_clips_outside_the_usual_range(emu, emu_lib, B, M):
+    pc.check_off_contract_scalars(B, M, lambda c, clip: pc.run_host(emu_lib, c, clip=clip, coefs=pc.ALL_COEFS), pc.info(emu_lib, B, M),
+                                  emu.masked_evaluate, emu.masked_evaluate_backward)
 
 
 @pytest.mark.parametrize("B,M", [(5, 37), (9, 600)])
@@ -253,7 +290,63 @@ def test_advantages_bit_for_bit_in_the_stated_order(lib, emu_lib):
         assert np.array_equal(pc.bits(runs[0][0]), pc.bits(runs[1][0])) and np.array_equal(runs[0][1], runs[1][1])
 
 
+def emu_advantages(L, ret, vp):
+    """(adv, stats) of one emulated bpp_ppo_advantages, guards checked."""
+    E = ret.size
+    whole, adv = pc.guarded((E,))
+    swhole, stats = pc.guarded((2,), np.float64)
+    ws = np.zeros(int(L.bpp_ppo_advantages_workspace(E)) // 8 + 1, np.float64)
+    assert L.bpp_ppo_advantages(ret.ctypes.data, vp.ctypes.data, adv.ctypes.data, stats.ctypes.data, E, ws.ctypes.data, None) == 0
+    assert pc.guards_intact(whole) and pc.guards_intact(swhole)
+    return adv, stats
+
+
+# every size of the device suite runs on the emulator as well (under a second each)
+@pytest.mark.parametrize("E", pc.ADV_EDGES)
+def test_advantages_at_the_block_shape_change(lib, emu_lib, E):
+    assert adv_info(lib, E) == adv_info(emu_lib, E) == pc.adv_shape_rule(E)
+    C, G, W = adv_info(emu_lib, E)
+    assert (G - 1) * C < E <= G * C and G <= 1024 and emu_lib.bpp_ppo_advantages_workspace(E) == 2 * G * 8
+    ret, vp = pc.advantages_case(E)
+    adv, stats = emu_advantages(emu_lib, ret, vp)
+    pc.check_advantages(adv, stats, ret, vp, C, W)
+
+
+def test_the_shape_changes_where_1024_blocks_of_one_chunk_no_longer_hold_the_rollout(lib, emu_lib):
+    for L in (lib, emu_lib):
+        assert adv_info(L, 256 * 1024) == [256, 1024, 256] and adv_info(L, 256 * 1024 + 1) == [512, 513, 256]
+        assert adv_info(L, 256) == [256, 1, 256] and adv_info(L, 257) == [256, 2, 256] and adv_info(L, 2 * 256 * 1024 + 1) == [768, 683, 256]
+
+
+@pytest.mark.parametrize("E", [320, 256 * 1024])
+def test_advantages_of_equal_raw_values_are_zero_and_a_large_offset_keeps_the_float64_bound(emu_lib, E):
+    C, G, W = adv_info(emu_lib, E)
+    ret, vp = pc.advantages_constant(E)
+    assert np.all(ret - vp == np.float32(0.75))
+    adv, stats = emu_advantages(emu_lib, ret, vp)
+    pc.check_advantages_constant(adv, stats)
+    ret, vp = pc.advantages_offset(E)
+    adv, stats = emu_advantages(emu_lib, ret, vp)
+    pc.check_advantages(adv, stats, ret, vp, C, W)
+
+
 # -------------------------------------------------------------------------------------------------------------------- gather
+@pytest.mark.parametrize("n", pc.GATHER_LENS)
+def test_gather_rows_at_the_part_boundary_behind_an_inaccessible_page(emu_lib, n):
+    """Dense rows and a padded stride, every window of ppo_cases.GATHER_SEQ as the indices.  The dense source and the indices end at
+    an inaccessible page: a read past the last row, or past idx[B - 1], is a host fault."""
+    for pad in (0, 1000):
+        src, stride = pc.gather_edge_case(n, pad)
+        held = hc.Fenced(src) if pad == 0 else None
+        s = held.array if held else src
+        for B in pc.GATHER_BS:
+            for idx in pc.gather_index_vectors(B):
+                fenced = hc.Fenced(idx, np.int64)
+                whole, dst = pc.guarded((B, n))
+                assert emu_lib.bpp_gather_rows(s.ctypes.data, stride, pc.GATHER_ROWS, fenced.array.ctypes.data, B, n, dst.ctypes.data, None) == 0
+                assert pc.same_or_nan(dst, pc.gather_expected(src, idx, n)) and pc.guards_intact(whole), (pad, B, idx)
+
+
 @pytest.mark.parametrize("n", [1, 3, 400, 1600])
 @pytest.mark.parametrize("B", [1, 65])
 def test_gather_rows_bit_for_bit_with_guards(emu_lib, B, n):
