@@ -9,6 +9,7 @@ Nothing leaves the GPU until the summary is printed.
 
     python examples/rollout_with_policy.py --envs 16384 --steps 200
     python examples/rollout_with_policy.py --envs 64 --steps 2000 --graph      # the reference's scale: one HIP-graph launch per lock-step
+    python examples/rollout_with_policy.py --envs 2048 --side 20 --native      # 20 x 20 x 20 bins: the one-image form of the native forward
 
 --graph: policy forward + bpp_masked_act_counter + the fused environment step + the step counter's increment are captured ONCE
 in a HIP graph (torch.cuda.CUDAGraph) and replayed: at 16 ... 1 024 bins a lock-step is ~25 kernel launches of a few
@@ -45,15 +46,15 @@ class Actor(nn.Module):
         return self.linear(self.actor(self.share(x)))
 
 
-def native_from_actor(actor, hidden=256):
+def native_from_actor(actor, hidden=256, form="two_images"):
     """bpp_amd.NativePolicy with the Actor's weights on the Actor's device; the critic and mask heads, which the Actor does
-    not have, are zeros (ask it for logits only)."""
+    not have, are zeros (ask it for logits only).  form: NativePolicy's ("auto" for a side above 15)."""
     n_actions = actor.linear.out_features
     sd = {("dist." if k.startswith("linear.") else "base.") + k: v for k, v in actor.state_dict().items()}
     for name, shape in bpp_amd.policy.layer_shapes(actor.side, hidden, n_actions):
         sd.setdefault(name + ".weight", torch.zeros(shape))
         sd.setdefault(name + ".bias", torch.zeros(shape[0]))
-    return bpp_amd.NativePolicy(actor.side, n_actions, hidden, device=actor.linear.weight.device).load_state_dict(sd)
+    return bpp_amd.NativePolicy(actor.side, n_actions, hidden, device=actor.linear.weight.device, form=form).load_state_dict(sd)
 
 
 def main():
@@ -61,6 +62,7 @@ def main():
     ap.add_argument("--envs", type=int, default=16384)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rotation", action="store_true")
+    ap.add_argument("--side", type=int, choices=(10, 20), default=10, help="the bin is side x side x side")
     ap.add_argument("--bf16", action="store_true", help="run the policy under bf16 autocast")
     ap.add_argument("--native", action="store_true",
                     help="the same network as bpp_amd.NativePolicy: one fused float32 call per lock-step instead of torch layers")
@@ -72,7 +74,7 @@ def main():
                     help="with --stream: the item generator of the supply (the reference's --item-seq; cut1 and rs on the counter generator)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    size = (10, 10, 10)
+    size = (args.side,) * 3
     if args.graph and args.stream:
         raise SystemExit("--graph replays ONE captured lock-step; the stream supply's refills are scheduled by host code between lock-steps")
     if args.stream:
@@ -82,11 +84,11 @@ def main():
     else:
         pool = bpp_amd.sequences.cut2_pool(size, 4096, seed=0)
         envs = bpp_amd.BppVecEnv(args.envs, size, enable_rotation=args.rotation, pool=pool, device=dev)
-    policy = Actor(10, envs.action_space.n).to(dev).eval()
+    policy = Actor(args.side, envs.action_space.n).to(dev).eval()
     if args.native:
         if args.bf16:
             raise SystemExit("--native is float32")
-        full = native_from_actor(policy)
+        full = native_from_actor(policy, form="auto")         # two LDS images per bin up to side 15, one image above
 
         def policy(x, net=full):
             return net(x, want=("logits",))[1]

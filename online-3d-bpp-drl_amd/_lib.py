@@ -76,6 +76,11 @@ KFAC_INFO = ("D", "R", "tile", "rows_per_split", "splits", "chain")
 # include/bpp_policy.h: the same, for the CNNPro policy forward
 POLICY_SYMBOLS = ["bpp_policy_forward", "bpp_policy_forward_workspace", "bpp_policy_weights_floats", "bpp_policy_forward_info"]
 POLICY_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "bins_per_head_tile", "head_groups", "tile", "padded_rows", "path")
+# include/bpp_policy_one_image.h: the same, for the policy forward on one LDS image per bin (sides up to 22)
+POLICY_ONE_IMAGE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy_one_image.h")
+POLICY_ONE_IMAGE_SYMBOLS = ["bpp_policy_forward_one_image", "bpp_policy_forward_one_image_workspace", "bpp_policy_one_image_weights_floats",
+                            "bpp_policy_forward_one_image_info"]
+POLICY_ONE_IMAGE_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "tiles_per_wave", "head_groups", "tile", "padded_rows", "path")
 # include/bpp_policy_train.h: the same, for the training pass of the CNNPro trunk
 POLICY_TRAIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy_train.h")
 POLICY_TRAIN_SYMBOLS = ["bpp_policy_trunk_forward_train", "bpp_policy_trunk_backward", "bpp_policy_trunk_backward_workspace",
@@ -316,6 +321,21 @@ def bind_policy(L):
     return L
 
 
+def bind_policy_one_image(L):
+    """Argument types of the POLICY_ONE_IMAGE_SYMBOLS on library handle L: those of their bind_policy counterparts."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    geom = ctypes.POINTER(i32)
+    L.bpp_policy_forward_one_image.argtypes = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp, vp, vp]
+    L.bpp_policy_forward_one_image.restype = ctypes.c_int
+    L.bpp_policy_forward_one_image_workspace.argtypes = [geom, i32]
+    L.bpp_policy_forward_one_image_workspace.restype = ctypes.c_size_t
+    L.bpp_policy_one_image_weights_floats.argtypes = [geom]
+    L.bpp_policy_one_image_weights_floats.restype = ctypes.c_size_t
+    L.bpp_policy_forward_one_image_info.argtypes = [geom, i32, geom]
+    L.bpp_policy_forward_one_image_info.restype = ctypes.c_int
+    return L
+
+
 def bind_policy_train(L):
     """Argument types of the POLICY_TRAIN_SYMBOLS on library handle L."""
     vp, i32 = ctypes.c_void_p, ctypes.c_int32
@@ -509,6 +529,7 @@ def lib():
         bind_ppo(L)
         bind_kfac(L)
         bind_policy(L)
+        bind_policy_one_image(L)
         bind_policy_train(L)
         bind_stream_kinds(L)
         bind_placements(L)

@@ -44,6 +44,7 @@
 #include "../../include/bpp_ppo.h"
 #include "../../include/bpp_kfac.h"
 #include "../../include/bpp_policy.h"
+#include "../../include/bpp_policy_one_image.h"
 #include "../../include/bpp_policy_train.h"
 #include "../../include/bpp_stream_kinds.h"
 #include "../../include/bpp_placements.h"
@@ -1644,6 +1645,7 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_mfma.inl"
 #include "bpp_kfac.inl"
 #include "bpp_policy.inl"
+#include "bpp_policy_one_image.inl"
 #include "bpp_policy_train.inl"
 #include "bpp_placements.inl"
 #include "bpp_heuristic.inl"

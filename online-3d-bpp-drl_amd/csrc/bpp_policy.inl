@@ -27,6 +27,7 @@ constexpr int kPolStride = kPolT + 1;     // floats between two features of the 
 constexpr int kPolMaxHidden = 512;
 constexpr int kPolLdsBytes = 160 * 1024;
 constexpr int kPolTrunkK = kPolC * 9;
+constexpr int kPolOneImageMaxSide = 22;   // one image [64][(S + 2)^2 | 1] and the tables within kPolLdsBytes: 152 064 B at 22
 
 struct PolShape {
     int S, H, M, A, PW, PP, img;          // img: floats of one image
@@ -283,12 +284,15 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
     }
 }
 
-int policy_shape(const int32_t *g, int32_t n, bool need_n, const ArgCheck &ck, PolShape &s) {
+// images: the LDS images a bin has in the trunk kernel -- 2 for policy_trunk_kernel and the training kernels, 1 for
+// policy_trunk_one_image_kernel (bpp_policy_one_image.inl), which takes two bins only while its workgroup stays within half the LDS.
+int policy_shape(const int32_t *g, int32_t n, bool need_n, const ArgCheck &ck, PolShape &s, int images = 2) {
     if (!g) return ck.bad("NULL geom");
     memset(&s, 0, sizeof s);
     s.S = g[0], s.H = g[1], s.M = g[2], s.n = n;
     if (s.S < 1 || s.H < 1) return ck.bad("S and H must be >= 1");
-    if (s.S > 15) return ck.bad("the two images of a bin do not fit the LDS (S > 15)");
+    if (images == 2 && s.S > 15) return ck.bad("the two images of a bin do not fit the LDS (S > 15)");
+    if (s.S > kPolOneImageMaxSide) return ck.bad("the image of a bin does not fit the LDS (S > 22)");
     s.A = s.S * s.S;
     if (s.M != s.A && s.M != 2 * s.A) return ck.bad("M must be A or 2 A");
     if (s.H % kPolTile != 0 || s.H > kPolMaxHidden) return ck.bad("H must be a multiple of 32 and at most 512");
@@ -296,10 +300,10 @@ int policy_shape(const int32_t *g, int32_t n, bool need_n, const ArgCheck &ck, P
     s.PW = s.S + 2, s.PP = (s.PW * s.PW) | 1, s.img = kPolC * s.PP;
     for (s.P = kPolMaxBins; s.P >= 1; --s.P) {
         s.rows = s.P * s.A, s.tiles = (s.rows + kPolTile - 1) / kPolTile;
-        s.trunk_lds = (2 * s.P * s.img + kPolTrunkK + s.tiles * kPolTile) * 4;
-        if (s.trunk_lds <= kPolLdsBytes) break;
+        s.trunk_lds = (images * s.P * s.img + kPolTrunkK + s.tiles * kPolTile) * 4;
+        if (s.trunk_lds <= (images == 1 && s.P > 1 ? kPolLdsBytes / 2 : kPolLdsBytes)) break;
     }
-    if (s.P < 1) return ck.bad("the two images of a bin do not fit the LDS");
+    if (s.P < 1) return ck.bad("the images of a bin do not fit the LDS");
     s.head_lds = ((s.H + kPolChunk) * kPolStride + kPolT) * 4;
     long long at = 0;
     for (int l = 0; l < 5; ++l) {

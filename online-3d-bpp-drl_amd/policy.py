@@ -6,6 +6,9 @@ workgroup, the Linear layers as products over 64 bins, float32 on the matrix cor
     value, logits, pred = policy(obs)                   # the callable ReorderSearch, MultiBinPacker and MCTSearch take
     value, action, log_prob = policy.act(obs, env.location_masks, deterministic=True)
 
+Sides above 15 (20 x 20 pallets, up to 22) take the one-image form of the trunk kernel (include/bpp_policy_one_image.h):
+`NativePolicy(20, 400, form="auto")`; where both forms accept a side they give the same bits.
+
 NativePolicy is inference only; `refresh(module)` repacks the weights after an optimizer step.  A bin's outputs are the same bits
 whatever batch it is evaluated in.  CPU tensors go through torch_forward, the same layers in plain torch.
 
@@ -27,6 +30,8 @@ from .masks import masked_act
 HEADS = ("value", "logits", "pred")
 TRUNK = tuple("base.share.%d" % i for i in (0, 2, 4, 6, 8))
 MAX_SIDE, HIDDEN_STEP, MAX_HIDDEN = 15, 32, 512      # what bpp_policy_forward accepts (include/bpp_policy.h)
+MAX_SIDE_ONE_IMAGE = 22                              # what bpp_policy_forward_one_image accepts (include/bpp_policy_one_image.h)
+FORMS = ("two_images", "one_image", "auto")          # auto: two images up to MAX_SIDE, one image above
 _WORKSPACE = {}     # (device, stream, geom) -> float32 tensor, grown to the largest n asked for
 
 
@@ -134,17 +139,41 @@ def torch_forward(weights, obs, want=HEADS):
     return value, logits, pred
 
 
-def forward_info(geom, n, L=None):
-    """bpp_policy_forward_info as a dict (_lib.POLICY_INFO)."""
+def resolve_form(form, side):
+    """"two_images" or "one_image": what `form` (one of FORMS) means at this side."""
+    if form not in FORMS:
+        raise ValueError("form must be one of %r" % (FORMS,))
+    if form == "auto":
+        return "two_images" if int(side) <= MAX_SIDE else "one_image"
+    return form
+
+
+def max_side(form):
+    """The largest side NativePolicy / policy_forward accept under `form`."""
+    if form not in FORMS:
+        raise ValueError("form must be one of %r" % (FORMS,))
+    return MAX_SIDE if form == "two_images" else MAX_SIDE_ONE_IMAGE
+
+
+def forward_info(geom, n, L=None, form="two_images"):
+    """bpp_policy_forward_info as a dict (_lib.POLICY_INFO), or bpp_policy_forward_one_image_info (_lib.POLICY_ONE_IMAGE_INFO)
+    where `form` comes to "one_image" at this side."""
     out = (ctypes.c_int32 * 8)()
-    _lib.check((L or _lib.lib()).bpp_policy_forward_info(_lib.kfac_geom(geom), int(n), out))
+    L = L or _lib.lib()
+    if resolve_form(form, geom[0]) == "one_image":
+        _lib.check(L.bpp_policy_forward_one_image_info(_lib.kfac_geom(geom), int(n), out), L)
+        return dict(zip(_lib.POLICY_ONE_IMAGE_INFO, (int(v) for v in out)))
+    _lib.check(L.bpp_policy_forward_info(_lib.kfac_geom(geom), int(n), out), L)
     return dict(zip(_lib.POLICY_INFO, (int(v) for v in out)))
 
 
-def policy_forward(obs, weights, geom, want=HEADS):
+def policy_forward(obs, weights, geom, want=HEADS, form="two_images"):
     """(value [n], logits [n, M], pred [n, M]) from bpp_policy_forward, None for a head not in `want`: obs float32 [n, >= 4 A]
     on a HIP device with contiguous rows (a view of a storage's rows will do), weights the packed blob on the same device,
     geom = (S, H, M).  Only enqueues on the current stream.
+
+    form (one of FORMS): "two_images" is bpp_policy_forward (S <= 15); "one_image" is bpp_policy_forward_one_image (S <= 22: one
+    LDS image per bin, the same blob, workspace and bits); "auto" takes two images up to S = 15 and one image above.
 
     The workspace is kept per (device, stream, geom) and grown to the largest n asked for.  Inside a stream capture the call
     takes a workspace of its own from the graph's memory pool, as its outputs are, so a captured call keeps its workspace for as
@@ -154,19 +183,24 @@ def policy_forward(obs, weights, geom, want=HEADS):
     want = tuple(want)
     if not want or any(h not in HEADS for h in want):
         raise ValueError("want must name at least one of %r" % (HEADS,))
+    one = resolve_form(form, S) == "one_image"
     n, stride = _check_obs(obs, S, "policy_forward")
     dev = obs.device
     g = _lib.kfac_geom((S, H, M))
     L = _lib.lib()
-    floats = int(L.bpp_policy_weights_floats(g))
+    forward, info, workspace, weights_floats = (
+        (L.bpp_policy_forward_one_image, L.bpp_policy_forward_one_image_info, L.bpp_policy_forward_one_image_workspace,
+         L.bpp_policy_one_image_weights_floats) if one else
+        (L.bpp_policy_forward, L.bpp_policy_forward_info, L.bpp_policy_forward_workspace, L.bpp_policy_weights_floats))
+    floats = int(weights_floats(g))
     if floats == 0:
-        _lib.check(L.bpp_policy_forward_info(g, n, (ctypes.c_int32 * 8)()))
+        _lib.check(info(g, n, (ctypes.c_int32 * 8)()))
     if (not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.device != dev or not weights.is_contiguous()
             or weights.numel() != floats):
         raise ValueError("weights must be the packed float32 blob of %d floats on %s" % (floats, dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        need = (int(L.bpp_policy_forward_workspace(g, n)) + 3) // 4
+        need = (int(workspace(g, n)) + 3) // 4
         if torch.cuda.is_current_stream_capturing():
             ws = torch.empty(need, dtype=torch.float32, device=dev)
         else:
@@ -178,23 +212,26 @@ def policy_forward(obs, weights, geom, want=HEADS):
         logits = torch.empty((n, M), dtype=torch.float32, device=dev) if "logits" in want else None
         pred = torch.empty((n, M), dtype=torch.float32, device=dev) if "pred" in want else None
         ptr = [t.data_ptr() if t is not None else None for t in (value, logits, pred)]
-        _lib.check(L.bpp_policy_forward(obs.data_ptr(), stride, n, g, weights.data_ptr(), ptr[0], ptr[1], ptr[2], ws.data_ptr(),
-                                        ctypes.c_void_p(stream)))
+        _lib.check(forward(obs.data_ptr(), stride, n, g, weights.data_ptr(), ptr[0], ptr[1], ptr[2], ws.data_ptr(), ctypes.c_void_p(stream)))
     return value, logits, pred
 
 
 class NativePolicy:
     """The reference's Policy(CNNPro) for inference: holds the packed weights, `policy(obs) -> (value [n], logits [n, M],
     pred [n, M])`, the contract of the searches' `policy` argument.  side: the pallet side S (the image is S x S), n_actions: S * S
-    or 2 S * S, hidden: 256 in the reference.  What the native call refuses is refused here, wherever the tensors live: a side
-    whose two LDS images per bin do not fit (S > 15; 20 x 20), a hidden size that is no multiple of 32 or above 512."""
+    or 2 S * S, hidden: 256 in the reference, form: one of FORMS -- "two_images" (bpp_policy_forward, S <= 15), "one_image"
+    (bpp_policy_forward_one_image, S <= 22: 20 x 20 pallets) or "auto" (two images up to 15, one above); the weights, act() and
+    the outputs' bits do not depend on it.  What the native call refuses is refused here, wherever the tensors live: a side whose
+    LDS images per bin do not fit under the form (S > 15 with two images, S > 22 with one), a hidden size that is no multiple of
+    32 or above 512."""
 
-    def __init__(self, side, n_actions, hidden=256, device=None):
-        self.side, self.n_actions, self.hidden = int(side), int(n_actions), int(hidden)
+    def __init__(self, side, n_actions, hidden=256, device=None, form="two_images"):
+        self.side, self.n_actions, self.hidden, self.form = int(side), int(n_actions), int(hidden), form
+        most = max_side(form)
         if self.n_actions not in (self.side ** 2, 2 * self.side ** 2):
             raise ValueError("n_actions must be side^2 or 2 side^2")
-        if not 1 <= self.side <= MAX_SIDE:
-            raise ValueError("side must lie in 1 .. %d: the two LDS images of a bin must fit" % MAX_SIDE)
+        if not 1 <= self.side <= most:
+            raise ValueError("side must lie in 1 .. %d: the LDS images of a bin must fit (form=%r)" % (most, form))
         if self.hidden < 1 or self.hidden % HIDDEN_STEP or self.hidden > MAX_HIDDEN:
             raise ValueError("hidden must be a multiple of %d, at most %d" % (HIDDEN_STEP, MAX_HIDDEN))
         self.geom = (self.side, self.hidden, self.n_actions)
@@ -229,12 +266,12 @@ class NativePolicy:
         return self.load_state_dict(state)
 
     @classmethod
-    def from_checkpoint(cls, path, side, n_actions, hidden=256, device=None):
+    def from_checkpoint(cls, path, side, n_actions, hidden=256, device=None, form="two_images"):
         """A reference checkpoint: the (state_dict, ob_rms) pair main.py:186-191 saves.  Observation statistics are refused."""
         state, ob_rms = torch.load(path, map_location="cpu", weights_only=False)
         if ob_rms is not None:
             raise ValueError("checkpoint carries observation statistics (VecNormalize ob=True); the BPP checkpoints do not")
-        return cls(side, n_actions, hidden, device=device).load_state_dict(state)
+        return cls(side, n_actions, hidden, device=device, form=form).load_state_dict(state)
 
     def unpack(self):
         """{name.weight / name.bias: tensor} of every layer under the reference's names, from the blob."""
@@ -249,7 +286,7 @@ class NativePolicy:
         if obs.device.type != "cuda":
             with torch.no_grad():
                 return torch_forward(self.unpack(), obs.to(torch.float32), want)
-        return policy_forward(obs if obs.dtype == torch.float32 else obs.to(torch.float32), self.weights, self.geom, want)
+        return policy_forward(obs if obs.dtype == torch.float32 else obs.to(torch.float32), self.weights, self.geom, want, self.form)
 
     def act(self, obs, location_masks, deterministic=False, **sampler):
         """Policy.act (acktr/model.py:57-68): (value [n, 1], action int64 [n, 1], action_log_probs [n, 1]); the forward, then

@@ -14,6 +14,13 @@ rule of the tests).
 
 --emulator measures the same errors for the kernels compiled for the SIMT emulator of the CPU tests (tests/emu) and merges
 them into the file as `accuracy_on_the_emulator`; a device run keeps that block.
+
+    python tools/bench_policy.py --forms --out profiles/policy_forward_forms.json
+
+--forms compares the two forms of the native forward (form="two_images": bpp_policy_forward; form="one_image":
+bpp_policy_forward_one_image, include/bpp_policy_one_image.h) by the same method, all forms of a row alternated in one run:
+(a) S = 10, H = 256, M = 100: one image against two images against torch_forward; (b) S = 20, H = 256, M = 400, which only the
+one-image form accepts: one image against torch_forward.
 """
 import argparse
 import json
@@ -75,9 +82,62 @@ def emulator_accuracy():
     return out
 
 
+FORMS_SHAPES = [((10, 256, 100), (64, 256, 2100, 16384, 65536), ("one_image", "two_images", "torch")),
+                ((20, 256, 400), (64, 2100, 32768), ("one_image", "torch"))]
+
+
+def bench_forms(args):
+    """The --forms mode: per shape, batch size and set of heads one row with every form's median and p10 - p90."""
+    import policy_cases as pc
+    dev = torch.device("cuda:0")
+    rows, info = [], {}
+    for (S, H, M), sizes, forms in FORMS_SHAPES:
+        plain = pc.real_weights(S, H, M, 11)
+        native = {f: bpp_amd.NativePolicy(S, M, H, form=f).load_state_dict(plain).to(dev) for f in forms if f != "torch"}
+        on_dev = {k: v.to(dev) for k, v in plain.items()}
+        states = torch.from_numpy(pc.synthetic_states(S, 64)).to(dev)
+        info["s%d" % S] = {f: pol.forward_info((S, H, M), 64, form=f) for f in native}
+        for n in sizes:
+            obs = states[torch.arange(n, device=dev) % states.shape[0]].contiguous()
+            for want in (pol.HEADS, ("logits",)):
+                def call(f):
+                    if f == "torch":
+                        with torch.no_grad():
+                            pol.torch_forward(on_dev, obs, want)
+                    else:
+                        native[f](obs, want=want)
+
+                calls = max(1, min(50, 20000 // n))
+                for f in forms:                                                     # warm-up
+                    timed(lambda: call(f), 2)
+                times = {f: [] for f in forms}
+                for r in range(args.rounds):
+                    for k in range(len(forms)):                                     # the order rotates round by round
+                        f = forms[(r + k) % len(forms)]
+                        times[f].append(timed(lambda: call(f), calls))
+                flop = 2.0 * macs(S, H, M) * n
+                row = {"S": S, "H": H, "M": M, "n": n, "heads": "all" if len(want) == 3 else "logits", "calls_per_round": calls, "rounds": args.rounds}
+                for f in forms:
+                    row[f] = dict(summary(times[f]), tflops=flop / float(np.median(times[f])) * 1e-6)
+                row["one_image_over_torch"] = row["one_image"]["median_us"] / row["torch"]["median_us"]
+                if "two_images" in forms:
+                    row["one_image_over_two_images"] = row["one_image"]["median_us"] / row["two_images"]["median_us"]
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    out = {"device": torch.cuda.get_device_name(0), "mflop_per_bin": {"s%d" % g[0]: 2e-6 * macs(*g) for g, _, _ in FORMS_SHAPES},
+           "method": "device events around `calls_per_round` back-to-back calls, the forms of a row alternated (the order rotates), `rounds` rounds; "
+                     "float32, no_grad; TF/s on the network's 2 * MAC whatever heads are asked for",
+           "forward_info_at_n64": info, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="64,256,2100,16384,65536")
+    ap.add_argument("--forms", action="store_true", help="compare the one-image and two-image forms of the native forward (see above)")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "policy_forward.json"))
     ap.add_argument("--emulator", action="store_true", help="measure the emulated kernels' error on the CPU and merge it into --out")
@@ -88,6 +148,9 @@ def main():
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
         print(json.dumps(out["accuracy_on_the_emulator"]))
+        return
+    if args.forms:
+        bench_forms(args)
         return
     dev = torch.device("cuda:0")
     import policy_cases as pc
