@@ -81,6 +81,8 @@ POLICY_ONE_IMAGE_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_polic
 POLICY_ONE_IMAGE_SYMBOLS = ["bpp_policy_forward_one_image", "bpp_policy_forward_one_image_workspace", "bpp_policy_one_image_weights_floats",
                             "bpp_policy_forward_one_image_info"]
 POLICY_ONE_IMAGE_INFO = ("bins_per_trunk_group", "trunk_lds_bytes", "trunk_groups", "tiles_per_wave", "head_groups", "tile", "padded_rows", "path")
+# the forms of the policy forward: name -> ((forward, workspace, weights floats, info) symbols, the info names, the largest side)
+POLICY_FORMS = {"two_images": (POLICY_SYMBOLS, POLICY_INFO, 15), "one_image": (POLICY_ONE_IMAGE_SYMBOLS, POLICY_ONE_IMAGE_INFO, 22)}
 # include/bpp_policy_train.h: the same, for the training pass of the CNNPro trunk
 POLICY_TRAIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy_train.h")
 POLICY_TRAIN_SYMBOLS = ["bpp_policy_trunk_forward_train", "bpp_policy_trunk_backward", "bpp_policy_trunk_backward_workspace",
@@ -306,34 +308,22 @@ def bind_kfac(L):
     return L
 
 
-def bind_policy(L):
-    """Argument types of the POLICY_SYMBOLS on library handle L."""
+def bind_policy(L, form="two_images"):
+    """Argument types of the four symbols of a policy-forward form (POLICY_FORMS; two images: the POLICY_SYMBOLS) on library
+    handle L."""
     vp, i32 = ctypes.c_void_p, ctypes.c_int32
     geom = ctypes.POINTER(i32)
-    L.bpp_policy_forward.argtypes = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp, vp, vp]
-    L.bpp_policy_forward.restype = ctypes.c_int
-    L.bpp_policy_forward_workspace.argtypes = [geom, i32]
-    L.bpp_policy_forward_workspace.restype = ctypes.c_size_t
-    L.bpp_policy_weights_floats.argtypes = [geom]
-    L.bpp_policy_weights_floats.restype = ctypes.c_size_t
-    L.bpp_policy_forward_info.argtypes = [geom, i32, geom]
-    L.bpp_policy_forward_info.restype = ctypes.c_int
+    forward, workspace, weights_floats, info = (getattr(L, name) for name in POLICY_FORMS[form][0])
+    forward.argtypes, forward.restype = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp, vp, vp], ctypes.c_int
+    workspace.argtypes, workspace.restype = [geom, i32], ctypes.c_size_t
+    weights_floats.argtypes, weights_floats.restype = [geom], ctypes.c_size_t
+    info.argtypes, info.restype = [geom, i32, geom], ctypes.c_int
     return L
 
 
 def bind_policy_one_image(L):
     """Argument types of the POLICY_ONE_IMAGE_SYMBOLS on library handle L: those of their bind_policy counterparts."""
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    geom = ctypes.POINTER(i32)
-    L.bpp_policy_forward_one_image.argtypes = [vp, ctypes.c_int64, i32, geom, vp, vp, vp, vp, vp, vp]
-    L.bpp_policy_forward_one_image.restype = ctypes.c_int
-    L.bpp_policy_forward_one_image_workspace.argtypes = [geom, i32]
-    L.bpp_policy_forward_one_image_workspace.restype = ctypes.c_size_t
-    L.bpp_policy_one_image_weights_floats.argtypes = [geom]
-    L.bpp_policy_one_image_weights_floats.restype = ctypes.c_size_t
-    L.bpp_policy_forward_one_image_info.argtypes = [geom, i32, geom]
-    L.bpp_policy_forward_one_image_info.restype = ctypes.c_int
-    return L
+    return bind_policy(L, "one_image")
 
 
 def bind_policy_train(L):
@@ -396,18 +386,22 @@ def bind_heuristic(L):
     return L
 
 
+def info_dict(fn, names, slots, *args, L=None):
+    """{name: int} of what the *_info entry point `fn` (a symbol's name) of library handle L writes into its last argument,
+    int32 [slots], when called with `args` in front of it."""
+    out = (ctypes.c_int32 * slots)()
+    check(getattr(L or lib(), fn)(*args, out), L)
+    return dict(zip(names, (int(v) for v in out)))
+
+
 def heuristic_info(size, rotation, n, L=None):
     """bpp_heuristic_act_info: the launch shape of the heuristic for a geometry and n bins, as a dict."""
-    out = (ctypes.c_int32 * 4)()
-    check((L or lib()).bpp_heuristic_act_info(int(size[0]), int(size[1]), int(bool(rotation)), int(n), out), L)
-    return dict(zip(HEURISTIC_INFO, (int(v) for v in out)))
+    return info_dict("bpp_heuristic_act_info", HEURISTIC_INFO, 4, int(size[0]), int(size[1]), int(bool(rotation)), int(n), L=L)
 
 
 def placements_info(E, capacity, A, L=None):
     """bpp_placements_info: the launch shapes of the plan kernels, as a dict."""
-    out = (ctypes.c_int32 * 6)()
-    check((L or lib()).bpp_placements_info(int(E), int(capacity), int(A), out), L)
-    return dict(zip(PLACEMENTS_INFO, (int(v) for v in out)))
+    return info_dict("bpp_placements_info", PLACEMENTS_INFO, 6, int(E), int(capacity), int(A), L=L)
 
 
 def box_range_arg(box_range):
@@ -417,10 +411,8 @@ def box_range_arg(box_range):
 
 def stream_kinds_info(stream, kind, box_range=None, L=None):
     """bpp_stream_kinds_info: the form a refill of `kind` ("cut1" / "rs") takes for struct bpp_stream `stream`, as a dict."""
-    out = (ctypes.c_int32 * 4)()
-    check((L or lib()).bpp_stream_kinds_info(ctypes.byref(stream), STREAM_KINDS[kind], box_range_arg(box_range) if box_range is not None else None,
-                                             out), L)
-    return dict(zip(STREAM_KINDS_INFO, (int(v) for v in out)))
+    return info_dict("bpp_stream_kinds_info", STREAM_KINDS_INFO, 4, ctypes.byref(stream), STREAM_KINDS[kind],
+                     box_range_arg(box_range) if box_range is not None else None, L=L)
 
 
 def kfac_geom(values):

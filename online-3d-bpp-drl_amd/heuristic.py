@@ -1,11 +1,10 @@
 """The lowest-top packing heuristic on the device (include/bpp_heuristic.h): per bin the placement whose
 resulting top is lowest, then the one that leaves the smoothest surface, then the lowest index -- the baseline packer a checkpoint
 is compared with.  One HIP kernel (`bpp_heuristic_act`), integer arithmetic throughout; there is no CPU fallback."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._front import obs_rows, stream_ptr
 
 RULES = tuple(_lib.HEURISTIC_RULES)
 
@@ -42,19 +41,13 @@ def heuristic_act(obs, location_masks, container_size, enable_rotation=False, ru
     r = rule_id(rule)
     if not torch.is_tensor(obs) or not torch.is_tensor(location_masks):
         raise ValueError("obs and location_masks must be tensors")
-    if obs.device.type != "cuda" or location_masks.device != obs.device:
+    (n, stride), dev = obs_rows(obs, A, "heuristic_act"), obs.device
+    if location_masks.device != dev:
         raise RuntimeError("heuristic_act needs its tensors on a HIP device")
-    if obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
-        raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
-    n, dev = int(obs.shape[0]), obs.device
-    if obs.shape[1] < 4 * A or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * A):
-        raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * A))
-    stride = int(obs.stride(0)) if n > 1 else int(obs.shape[1])
     if location_masks.dtype != torch.float32 or tuple(location_masks.shape) != (n, M) or not location_masks.is_contiguous():
         raise ValueError("location_masks must be a contiguous float32 [n, M = %d] tensor" % M)
     out, top = check_outputs(n, dev, out, top)
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().bpp_heuristic_act(obs.data_ptr(), stride, location_masks.data_ptr(), n, W, L, int(bool(enable_rotation)), r,
-                                                out.data_ptr(), top.data_ptr() if top is not None else None, stream))
+                                                out.data_ptr(), top.data_ptr() if top is not None else None, stream_ptr(dev)))
     return out

@@ -24,10 +24,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._front import Workspace, raw_stream
 
 PATCH, ROWS, NCHW = _lib.KFAC_PATCH, _lib.KFAC_ROWS, _lib.KFAC_NCHW
 _LAYOUTS = {"patch": PATCH, "rows": ROWS, "nchw": NCHW, PATCH: PATCH, ROWS: ROWS, NCHW: NCHW}
-_WORKSPACE = {}     # (device, stream) -> float64 tensor, grown to the largest request
+_WORKSPACE = Workspace()    # (device, stream) -> float64 tensor, grown to the largest request; a captured call takes its own
 
 
 def _pair(v):
@@ -91,7 +92,8 @@ def kfac_factor(src, layout, m, stat_decay, first, scale, kernel_size=(1, 1), st
     """m <- running average of scale * X^T X (bpp_kfac_factor): src the float32 device tensor the rows X are read from in
     `layout` ('patch': [B, C, H, W] with kernel_size / stride / padding, 'rows': [R, D], 'nchw': [B, D, ...]), m float32 [D, D]
     on the same device, updated in place and returned; first: m is set to the factor before the update (kfac.py:159-162).
-    Only enqueues on the current stream.  The result is symmetric bit for bit and the same bits on every run."""
+    Only enqueues on the current stream; inside a stream capture the call takes a workspace of its own from the graph's pool.
+    The result is symmetric bit for bit and the same bits on every run."""
     layout, geom, D, R, _ = factor_geometry(src, layout, kernel_size, stride, padding)
     if src.device.type != "cuda":
         raise RuntimeError("kfac_factor needs its tensors on a HIP device")
@@ -102,11 +104,9 @@ def kfac_factor(src, layout, m, stat_decay, first, scale, kernel_size=(1, 1), st
     x = src.detach().contiguous()
     g = _lib.kfac_geom(geom)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = raw_stream(dev)
         need = (int(_lib.lib().bpp_kfac_factor_workspace(layout, g)) + 7) // 8
-        ws = _WORKSPACE.get((dev, stream))
-        if ws is None or ws.numel() < need:
-            ws = _WORKSPACE[(dev, stream)] = torch.empty(need, dtype=torch.float64, device=dev)
+        ws = _WORKSPACE.take((dev, stream), need, torch.float64, dev)
         _lib.check(_lib.lib().bpp_kfac_factor(x.data_ptr(), layout, g, m.data_ptr(), float(scale), float(stat_decay), int(bool(first)),
                                               ws.data_ptr(), ctypes.c_void_p(stream)))
     return m

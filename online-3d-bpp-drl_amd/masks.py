@@ -1,22 +1,17 @@
 """Drop-in replacements for the mask helpers the ACKTR loop calls per observation row
 (acktr/utils.py:37-94), plus batched device versions.  All of them run the HIP kernel
 `bpp_mask_from_obs` / `bpp_mask_from_hmap`; there is no host fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._front import stream_ptr
 
 
 def _dev():
     if not torch.cuda.is_available():
         raise RuntimeError("mask kernels need a HIP device; there is no CPU fallback")
     return torch.device("cuda", torch.cuda.current_device())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def batched_mask_from_obs(obs, container_size, enable_rotation=False, rule="utils", out=None):
@@ -33,7 +28,7 @@ def batched_mask_from_obs(obs, container_size, enable_rotation=False, rule="util
     r = {"utils": _lib.RULE_UTILS, "space": _lib.RULE_SPACE}[rule]
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().bpp_mask_from_obs(o.data_ptr(), out.data_ptr(), E, W, L, H, int(bool(enable_rotation)), r,
-                                                _stream(dev)))
+                                                stream_ptr(dev)))
     return out
 
 
@@ -52,7 +47,7 @@ def batched_mask_from_hmap(hmap, items, container_size, enable_rotation=False, r
     r = {"utils": _lib.RULE_UTILS, "space": _lib.RULE_SPACE}[rule]
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().bpp_mask_from_hmap(h.data_ptr(), it.data_ptr(), out.data_ptr(), E, W, L, H,
-                                                 int(bool(enable_rotation)), r, _stream(dev)))
+                                                 int(bool(enable_rotation)), r, stream_ptr(dev)))
     return out
 
 
@@ -110,14 +105,13 @@ class _RowHelper(object):
         A = W * L
         M = A * (2 if rotation else 1)
         lib = _lib.lib()
-        if torch.cuda.current_device() != self.dev.index:
-            torch.cuda.set_device(self.dev)
-        sp = _stream(self.dev)
         self.serial = (self.serial + 1) & 0xffffffff or 1
         flag = self.base + 4 * self.cap
-        _lib.check(lib.bpp_mask_from_obs(observation.data_ptr(), self.base, 1, W, L, H, int(bool(rotation)), _lib.RULE_UTILS, sp))
-        _lib.check(lib.bpp_mark(flag, self.serial, sp))
-        _lib.check(lib.bpp_wait_mark(flag, self.serial, sp))
+        with torch.cuda.device(self.dev):
+            sp = stream_ptr(self.dev)
+            _lib.check(lib.bpp_mask_from_obs(observation.data_ptr(), self.base, 1, W, L, H, int(bool(rotation)), _lib.RULE_UTILS, sp))
+            _lib.check(lib.bpp_mark(flag, self.serial, sp))
+            _lib.check(lib.bpp_wait_mark(flag, self.serial, sp))
         return self.host[:4 * M].view("<f4")
 
 
@@ -216,10 +210,10 @@ def masked_act(logits, location_masks, seed=0, step=0, deterministic=False, env_
             if counter.device != dev or counter.numel() != 2 or counter.dtype not in (torch.int64, torch.uint64) or not counter.is_contiguous():
                 raise ValueError("counter must be a contiguous int64 / uint64 [2] tensor (seed, step) on the logits' device")
             _lib.check(_lib.lib().bpp_masked_act_counter(x.data_ptr(), m.data_ptr(), action.data_ptr(), logp.data_ptr(), E, M,
-                                                         int(env_id_base), counter.data_ptr(), int(bool(deterministic)), _stream(dev)))
+                                                         int(env_id_base), counter.data_ptr(), int(bool(deterministic)), stream_ptr(dev)))
         else:
             _lib.check(_lib.lib().bpp_masked_act(x.data_ptr(), m.data_ptr(), action.data_ptr(), logp.data_ptr(), E, M,
-                                                 int(env_id_base), int(seed), int(step), int(bool(deterministic)), _stream(dev)))
+                                                 int(env_id_base), int(seed), int(step), int(bool(deterministic)), stream_ptr(dev)))
     return action, logp
 
 
@@ -236,7 +230,7 @@ class _MaskedEvaluate(torch.autograd.Function):
         bad = torch.empty(E, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().bpp_masked_evaluate(logits.data_ptr(), location_masks.data_ptr(), action.data_ptr(),
-                                                      logp.data_ptr(), ent.data_ptr(), bad.data_ptr(), E, M, _stream(dev)))
+                                                      logp.data_ptr(), ent.data_ptr(), bad.data_ptr(), E, M, stream_ptr(dev)))
         ctx.save_for_backward(logits, location_masks, action)
         return logp, ent, bad
 
@@ -251,7 +245,7 @@ class _MaskedEvaluate(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().bpp_masked_evaluate_backward(logits.data_ptr(), location_masks.data_ptr(), action.data_ptr(),
                                                                g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(),
-                                                               grad.data_ptr(), E, M, _stream(dev)))
+                                                               grad.data_ptr(), E, M, stream_ptr(dev)))
         return grad, None, None
 
 

@@ -5,12 +5,11 @@ PlacementLog    the device log of an env that records (BppVecEnv.record_placemen
 PackingPlans    what BppVecEnv.placements() returns: compact rows of records, their counts and episode indices.
 replay_plans    heightmaps rebuilt from plans, every box checked (bpp_placements_replay): the verifier.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._front import stream_ptr
 
 RECORD_DTYPE = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("lz", "u1"), ("cell", "<u2"), ("rotated", "u1"), ("pad", "u1")])
 
@@ -177,7 +176,7 @@ def replay_plans(plans, size=None, upto=None, count=None, device=None, lib=None)
             volume.data_ptr())
     if dev.type == "cuda":
         with torch.cuda.device(dev):        # (launches target the calling thread's current device)
-            _lib.check(lib.bpp_placements_replay(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), lib)
+            _lib.check(lib.bpp_placements_replay(*args, stream_ptr(dev)), lib)
     else:
         _lib.check(lib.bpp_placements_replay(*args, None), lib)
     return hmap, status, volume

@@ -25,14 +25,16 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._front import Workspace, obs_rows, raw_stream, stream_ptr
 from .masks import masked_act
 
 HEADS = ("value", "logits", "pred")
 TRUNK = tuple("base.share.%d" % i for i in (0, 2, 4, 6, 8))
-MAX_SIDE, HIDDEN_STEP, MAX_HIDDEN = 15, 32, 512      # what bpp_policy_forward accepts (include/bpp_policy.h)
-MAX_SIDE_ONE_IMAGE = 22                              # what bpp_policy_forward_one_image accepts (include/bpp_policy_one_image.h)
-FORMS = ("two_images", "one_image", "auto")          # auto: two images up to MAX_SIDE, one image above
-_WORKSPACE = {}     # (device, stream, geom) -> float32 tensor, grown to the largest n asked for
+HIDDEN_STEP, MAX_HIDDEN = 32, 512                    # what bpp_policy_forward accepts (include/bpp_policy.h)
+MAX_SIDE = _lib.POLICY_FORMS["two_images"][2]        # the same: 15
+MAX_SIDE_ONE_IMAGE = _lib.POLICY_FORMS["one_image"][2]      # what bpp_policy_forward_one_image accepts (include/bpp_policy_one_image.h): 22
+FORMS = tuple(_lib.POLICY_FORMS) + ("auto",)         # auto: two images up to MAX_SIDE, one image above
+_WORKSPACE = Workspace()    # (device, stream, geom) -> float32 tensor, grown to the largest n asked for
 
 
 def layer_shapes(side, hidden, n_actions):
@@ -149,22 +151,15 @@ def resolve_form(form, side):
 
 
 def max_side(form):
-    """The largest side NativePolicy / policy_forward accept under `form`."""
-    if form not in FORMS:
-        raise ValueError("form must be one of %r" % (FORMS,))
-    return MAX_SIDE if form == "two_images" else MAX_SIDE_ONE_IMAGE
+    """The largest side NativePolicy / policy_forward accept under `form`: that of the form it comes to at the largest side."""
+    return _lib.POLICY_FORMS[resolve_form(form, MAX_SIDE_ONE_IMAGE)][2]
 
 
 def forward_info(geom, n, L=None, form="two_images"):
     """bpp_policy_forward_info as a dict (_lib.POLICY_INFO), or bpp_policy_forward_one_image_info (_lib.POLICY_ONE_IMAGE_INFO)
     where `form` comes to "one_image" at this side."""
-    out = (ctypes.c_int32 * 8)()
-    L = L or _lib.lib()
-    if resolve_form(form, geom[0]) == "one_image":
-        _lib.check(L.bpp_policy_forward_one_image_info(_lib.kfac_geom(geom), int(n), out), L)
-        return dict(zip(_lib.POLICY_ONE_IMAGE_INFO, (int(v) for v in out)))
-    _lib.check(L.bpp_policy_forward_info(_lib.kfac_geom(geom), int(n), out), L)
-    return dict(zip(_lib.POLICY_INFO, (int(v) for v in out)))
+    symbols, names, _ = _lib.POLICY_FORMS[resolve_form(form, geom[0])]
+    return _lib.info_dict(symbols[3], names, 8, _lib.kfac_geom(geom), int(n), L=L)
 
 
 def policy_forward(obs, weights, geom, want=HEADS, form="two_images"):
@@ -183,15 +178,12 @@ def policy_forward(obs, weights, geom, want=HEADS, form="two_images"):
     want = tuple(want)
     if not want or any(h not in HEADS for h in want):
         raise ValueError("want must name at least one of %r" % (HEADS,))
-    one = resolve_form(form, S) == "one_image"
-    n, stride = _check_obs(obs, S, "policy_forward")
+    symbols = _lib.POLICY_FORMS[resolve_form(form, S)][0]
+    n, stride = obs_rows(obs, S * S, "policy_forward")
     dev = obs.device
     g = _lib.kfac_geom((S, H, M))
     L = _lib.lib()
-    forward, info, workspace, weights_floats = (
-        (L.bpp_policy_forward_one_image, L.bpp_policy_forward_one_image_info, L.bpp_policy_forward_one_image_workspace,
-         L.bpp_policy_one_image_weights_floats) if one else
-        (L.bpp_policy_forward, L.bpp_policy_forward_info, L.bpp_policy_forward_workspace, L.bpp_policy_weights_floats))
+    forward, workspace, weights_floats, info = (getattr(L, name) for name in symbols)
     floats = int(weights_floats(g))
     if floats == 0:
         _lib.check(info(g, n, (ctypes.c_int32 * 8)()))
@@ -199,15 +191,8 @@ def policy_forward(obs, weights, geom, want=HEADS, form="two_images"):
             or weights.numel() != floats):
         raise ValueError("weights must be the packed float32 blob of %d floats on %s" % (floats, dev))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        need = (int(workspace(g, n)) + 3) // 4
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(need, dtype=torch.float32, device=dev)
-        else:
-            key = (dev, stream, (S, H, M))
-            ws = _WORKSPACE.get(key)
-            if ws is None or ws.numel() < need:
-                ws = _WORKSPACE[key] = torch.empty(need, dtype=torch.float32, device=dev)
+        stream = raw_stream(dev)
+        ws = _WORKSPACE.take((dev, stream, (S, H, M)), (int(workspace(g, n)) + 3) // 4, torch.float32, dev)
         value = torch.empty(n, dtype=torch.float32, device=dev) if "value" in want else None
         logits = torch.empty((n, M), dtype=torch.float32, device=dev) if "logits" in want else None
         pred = torch.empty((n, M), dtype=torch.float32, device=dev) if "pred" in want else None
@@ -339,21 +324,12 @@ def unpack_trunk_gradient(gw):
 
 def trunk_backward_info(geom, n, L=None):
     """bpp_policy_trunk_backward_info as a dict (_lib.POLICY_TRAIN_INFO)."""
-    out = (ctypes.c_int32 * 8)()
-    _lib.check((L or _lib.lib()).bpp_policy_trunk_backward_info(_lib.kfac_geom(geom), int(n), out), L)
-    return dict(zip(_lib.POLICY_TRAIN_INFO, (int(v) for v in out)))
+    return _lib.info_dict("bpp_policy_trunk_backward_info", _lib.POLICY_TRAIN_INFO, 8, _lib.kfac_geom(geom), int(n), L=L)
 
 
-def _check_obs(obs, S, who="the native trunk"):
-    """(n, floats between two rows) of an obs the native calls take; `who`: the subject of the wrong-device error."""
-    if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[0] < 1:
-        raise ValueError("obs must be a float32 [n, 4 A] tensor with n >= 1")
-    if obs.device.type != "cuda":
-        raise RuntimeError("%s needs its tensors on a HIP device" % who)
-    n = int(obs.shape[0])
-    if obs.shape[1] < 4 * S * S or obs.stride(1) != 1 or (n > 1 and obs.stride(0) < 4 * S * S):
-        raise ValueError("obs rows must be contiguous and hold 4 A = %d floats" % (4 * S * S))
-    return n, int(obs.stride(0)) if n > 1 else int(obs.shape[1])
+def _check_obs(obs, S):
+    """_front.obs_rows for the trunk's calls."""
+    return obs_rows(obs, S * S, "the native trunk")
 
 
 def trunk_forward_train(obs, blob, geom, feat=None, acts=None):
@@ -369,7 +345,7 @@ def trunk_forward_train(obs, blob, geom, feat=None, acts=None):
     acts = torch.empty((5, n, 64, S, S), dtype=torch.float32, device=dev) if acts is None else acts
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().bpp_policy_trunk_forward_train(obs.data_ptr(), stride, n, _lib.kfac_geom((S, H, M)), blob.data_ptr(), feat.data_ptr(),
-                                                             acts.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                             acts.data_ptr(), stream_ptr(dev)))
     return feat, acts
 
 
@@ -394,7 +370,7 @@ def trunk_backward(obs, geom, blob_bwd, feat, acts, grad_feat, grads=None, grad_
     with torch.cuda.device(dev):
         _lib.check(L.bpp_policy_trunk_backward(obs.data_ptr(), stride, n, g, blob_bwd.data_ptr(), feat.data_ptr(), acts.data_ptr(),
                                                grad_feat.data_ptr(), grads.data_ptr(), grad_weights.data_ptr(), workspace.data_ptr(),
-                                               workspace.numel() * 4, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                               workspace.numel() * 4, stream_ptr(dev)))
     return grads, grad_weights
 
 

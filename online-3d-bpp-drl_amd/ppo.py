@@ -13,87 +13,33 @@ thing gathered per mini-batch is the observation rows the network reads (bpp_gat
 `ppo_loss_torch` states the same expressions in plain torch on any device and dtype: the path of a CPU storage (an explicit twin,
 not a fallback -- ppo_loss itself refuses tensors that are not on a HIP device) and the baseline of tools/bench_ppo.py.
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._front import NativeLoss, dense_f32, dense_i64, loss_buffers, stream_ptr
 
 _CACHE = {}     # (device, B, M) -> workspace and gradient buffers: static addresses for a captured region
 PROB_EPS = 1.1920928955078125e-7        # torch.finfo(float32).eps: the clamp of probs_to_logits the kernels use
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _buffers(dev, B, M):
-    key = (dev, B, M)
-    buf = _CACHE.get(key)
-    if buf is None:
-        n = int(_lib.lib().bpp_ppo_loss_workspace(B, M))
-        buf = _CACHE[key] = {"workspace": torch.empty((n + 7) // 8, dtype=torch.float64, device=dev),
-                             "grad_logits": torch.empty((B, M), dtype=torch.float32, device=dev),
-                             "grad_values": torch.empty(B, dtype=torch.float32, device=dev), "grad_pred_mask": None}
-    return buf
-
-
-class PPOLoss(object):
+class PPOLoss(NativeLoss):
     """Result of ppo_loss / ppo_loss_torch: `terms` [7] = (value_loss, action_loss, dist_entropy, prob_loss, graph_loss, loss,
     clip_fraction), detached, each also a 0-dim view by name; `rows` [B, 7] = per-row (value term, action term, entropy, bad mass,
     squared mask error, ratio, clipped flag) when asked for; backward() sends the gradients into the graph the network outputs hang
     on.  The native gradient buffers belong to a cache per (device, B, M): the next ppo_loss of the same shape overwrites them, so
     call backward() first."""
 
+    TERMS = _lib.PPO_TERMS
+
     def __init__(self, terms, rows, outputs=None, grads=None, inputs=None, total=None):
-        self.terms, self.rows = terms, rows
-        self.inputs = inputs            # native: the dense tensors the kernel reads (views of the caller's wherever those are dense)
-        self._outputs, self._grads, self._total = outputs, grads, total
-
-    @property
-    def grad_logits(self):
-        return self._grads[0] if self._grads else None
-
-    @property
-    def grad_values(self):
-        return self._grads[1] if self._grads else None
-
-    @property
-    def grad_pred_mask(self):
-        return self._grads[2] if self._grads and len(self._grads) > 2 else None
+        NativeLoss.__init__(self, terms, rows, outputs, grads, inputs)
+        self._total = total
 
     def backward(self):
         if self._total is not None:     # ppo_loss_torch: autograd of the expressions
             self._total.backward()
-            return
-        pairs = [(t, g.view(t.shape)) for t, g in zip(self._outputs, self._grads) if t.requires_grad]
-        if not pairs:
-            raise RuntimeError("none of logits, values and pred_mask requires grad")
-        torch.autograd.backward([t for t, _ in pairs], [g for _, g in pairs])
-
-
-for _i, _name in enumerate(_lib.PPO_TERMS):
-    setattr(PPOLoss, _name, property(lambda self, _i=_i: self.terms[_i]))
-
-
-def _f32(t, shape, what, dev):
-    """The dense float32 tensor the kernel reads: `t` detached, viewed as `shape`."""
-    if not torch.is_tensor(t) or t.dtype != torch.float32:
-        raise ValueError("%s must be a float32 tensor" % what)
-    if t.device != dev:
-        raise ValueError("%s is on %s, the logits on %s" % (what, t.device, dev))
-    n = 1
-    for s in shape:
-        n *= s
-    if t.numel() != n:
-        raise ValueError("%s has %d elements, expected %s" % (what, t.numel(), "x".join(str(s) for s in shape)))
-    return t.detach().reshape(shape).contiguous()
-
-
-def _i64(t, n, what, dev):
-    if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != dev or t.numel() != n:
-        raise ValueError("%s must be an int64 tensor of %d entries on the logits' device" % (what, n))
-    return t.reshape(n).contiguous()
+        else:
+            NativeLoss.backward(self)
 
 
 def ppo_loss(logits, values, pred_mask, location_masks, action, value_preds, returns, old_log_probs, advantages, indices=None,
@@ -118,19 +64,17 @@ def ppo_loss(logits, values, pred_mask, location_masks, action, value_preds, ret
     if location_masks.numel() % M or location_masks.numel() < M:
         raise ValueError("location_masks must be [E, M]")
     E = location_masks.numel() // M
-    x = _f32(logits, (B, M), "logits", dev)
-    v = _f32(values, (B,), "values", dev)
-    p = _f32(pred_mask, (B, M), "pred_mask", dev) if pred_mask is not None else None
-    m = _f32(location_masks, (E, M), "location_masks", dev)
-    vp, r, old, adv = (_f32(t, (E,), what, dev) for t, what in ((value_preds, "value_preds"), (returns, "returns"),
-                                                                 (old_log_probs, "old_log_probs"), (advantages, "advantages")))
-    a = _i64(action, E, "action", dev)
-    idx = _i64(indices, B, "indices", dev) if indices is not None else None
+    x = dense_f32(logits, (B, M), "logits", dev)
+    v = dense_f32(values, (B,), "values", dev)
+    p = dense_f32(pred_mask, (B, M), "pred_mask", dev) if pred_mask is not None else None
+    m = dense_f32(location_masks, (E, M), "location_masks", dev)
+    vp, r, old, adv = (dense_f32(t, (E,), what, dev) for t, what in ((value_preds, "value_preds"), (returns, "returns"),
+                                                                      (old_log_probs, "old_log_probs"), (advantages, "advantages")))
+    a = dense_i64(action, E, "action", dev)
+    idx = dense_i64(indices, B, "indices", dev) if indices is not None else None
     if idx is None and B > E:
         raise ValueError("without indices the mini-batch is rows 0 .. B - 1 of the rollout: B > E")
-    buf = _buffers(dev, B, M)
-    if p is not None and buf["grad_pred_mask"] is None:
-        buf["grad_pred_mask"] = torch.empty((B, M), dtype=torch.float32, device=dev)
+    buf = loss_buffers(_CACHE, _lib.lib().bpp_ppo_loss_workspace, dev, B, M, pred_mask=p is not None)
     terms = torch.empty(7, dtype=torch.float32, device=dev)
     row_terms = torch.empty((B, 7), dtype=torch.float32, device=dev) if rows else None
     with torch.cuda.device(dev):
@@ -139,7 +83,7 @@ def ppo_loss(logits, values, pred_mask, location_masks, action, value_preds, ret
             m.data_ptr(), a.data_ptr(), vp.data_ptr(), r.data_ptr(), old.data_ptr(), adv.data_ptr(), float(clip_param),
             float(value_loss_coef), float(entropy_coef), float(invalid_coef), float(mask_coef), int(bool(use_clipped_value_loss)),
             buf["grad_logits"].data_ptr(), buf["grad_values"].data_ptr(), buf["grad_pred_mask"].data_ptr() if p is not None else None,
-            row_terms.data_ptr() if rows else None, terms.data_ptr(), buf["workspace"].data_ptr(), B, E, M, _stream(dev)))
+            row_terms.data_ptr() if rows else None, terms.data_ptr(), buf["workspace"].data_ptr(), B, E, M, stream_ptr(dev)))
     outputs, grads = [logits, values], [buf["grad_logits"], buf["grad_values"]]
     if p is not None:
         outputs.append(pred_mask)
@@ -203,13 +147,13 @@ def normalized_advantages(returns, value_preds):
     if dev.type != "cuda":
         raise RuntimeError("normalized_advantages needs its tensors on a HIP device")
     E = returns.numel()
-    r, vp = _f32(returns, (E,), "returns", dev), _f32(value_preds, (E,), "value_preds", dev)
+    r, vp = dense_f32(returns, (E,), "returns", dev), dense_f32(value_preds, (E,), "value_preds", dev)
     L = _lib.lib()
     adv = torch.empty(tuple(returns.shape), dtype=torch.float32, device=dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
     ws = torch.empty((int(L.bpp_ppo_advantages_workspace(E)) + 7) // 8 or 1, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.bpp_ppo_advantages(r.data_ptr(), vp.data_ptr(), adv.data_ptr(), stats.data_ptr(), E, ws.data_ptr(), _stream(dev)))
+        _lib.check(L.bpp_ppo_advantages(r.data_ptr(), vp.data_ptr(), adv.data_ptr(), stats.data_ptr(), E, ws.data_ptr(), stream_ptr(dev)))
     return adv, stats
 
 
@@ -222,12 +166,12 @@ def gather_rows(src, indices, out=None):
     if src.dtype != torch.float32 or src.dim() != 2 or src.stride(1) != 1 or src.stride(0) < src.shape[1]:
         raise ValueError("src must be float32 [rows, len] with dense rows")
     B = int(indices.numel())
-    idx = _i64(indices, B, "indices", dev)
+    idx = dense_i64(indices, B, "indices", dev)
     rows, n = (int(v) for v in src.shape)
     if out is None:
         out = torch.empty((B, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().bpp_gather_rows(src.data_ptr(), int(src.stride(0)), rows, idx.data_ptr(), B, n, out.data_ptr(), _stream(dev)))
+        _lib.check(_lib.lib().bpp_gather_rows(src.data_ptr(), int(src.stride(0)), rows, idx.data_ptr(), B, n, out.data_ptr(), stream_ptr(dev)))
     return out
 
 

@@ -5,11 +5,10 @@ ever crosses xGMI: bins are independent, so a multi-GPU job shards bins by globa
 this 32-byte record (sum of episode returns, sum of final ratios, sum of episode lengths, episode
 count) once per logging interval -- `torch.distributed` backend "nccl" (= RCCL) on GPUs, "gloo" in
 CPU tests."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._front import stream_ptr
 
 
 def shard_range(total_envs, rank, world_size):
@@ -37,9 +36,8 @@ class EpisodeStats(object):
         if self.device.type != "cuda":
             raise RuntimeError("EpisodeStats.update runs the HIP kernel; device tensors required")
         with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(_lib.lib().bpp_episode_stats(res.done.data_ptr(), res.ep_ret.data_ptr(), res.ratio.data_ptr(),
-                                                    res.ep_len.data_ptr(), res.done.numel(), self.acc.data_ptr(), s))
+                                                    res.ep_len.data_ptr(), res.done.numel(), self.acc.data_ptr(), stream_ptr(self.device)))
 
     def all_reduce(self, group=None):
         """Sum the record over all ranks (no-op without an initialised process group; with one the collective

@@ -16,12 +16,11 @@ which is where the reference's update reads them.
 A storage on the CPU takes the reference's insert() path and the host entry point of the same native recurrence: an explicit
 twin, not a fallback -- a storage on a device without the library's kernels does not exist.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from .vec_env import StepTensors, _RAW_STREAM
+from ._front import stream_ptr
+from .vec_env import StepTensors
 
 _SMALL = (("rewards", torch.float32), ("done", torch.uint8), ("counter", torch.int32), ("ratio", torch.float64),
           ("ep_ret", torch.float64), ("ep_len", torch.int32))
@@ -179,8 +178,7 @@ class RolloutStorage(object):
                 float(gamma), float(gae_lambda)]
         if dev.type == "cuda":
             with torch.cuda.device(dev):
-                raw = _RAW_STREAM(dev.index) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(_lib.lib().bpp_compute_returns(*args, ctypes.c_void_p(raw)))
+                _lib.check(_lib.lib().bpp_compute_returns(*args, stream_ptr(dev)))
         elif dev.type == "cpu":
             _lib.check(_lib.lib().bpp_compute_returns_host(*args))
         else:

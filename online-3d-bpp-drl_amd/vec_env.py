@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._front import stream_ptr
 from .branch import BranchOps
 from .placements import PlacementLog, default_capacity
 from .sequences import check_pool
@@ -25,7 +26,6 @@ from .supply import STREAM_LAYOUT  # noqa: F401 -- a streaming checkpoint's layo
 from .supply import StreamSupply, check_checkpoint, copy_stream_records, release_handle, resolve_stream_spec
 
 
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 STATE_FORMAT = 1      # state_dict()["format"]: 1 = 48-byte records whose last word is hmax, per-bin ep_acc rows
 # rollout_uniform_sets: chains of step-kernel launches the bins are split over (include/bpp_pipeline.h), where nothing is asked for.
 # Measured (profiles/pipelined_rollout_ab.json, pipelined_rollout_groups.json): two chains win on every workload,
@@ -90,7 +90,7 @@ class StepTensors(object):
         if self._stage is not None and self._flat is not None:
             host = self._stage()
             if stream is None:
-                stream = ctypes.c_void_p(torch.cuda.current_stream(self._flat.device).cuda_stream)
+                stream = stream_ptr(self._flat.device)
             rc = _lib.lib().bpp_fetch_to_host(self._flat.data_ptr() + self._layout["_small"][0], host.ctypes.data, int(nbytes), stream)
             if rc:
                 _lib.check(rc)
@@ -557,12 +557,8 @@ class BppVecEnv(BranchOps):
         return out
 
     def _stream_ptr(self):
-        """The calling thread's current HIP stream on the env's device as a c_void_p (raw handle straight from torch's
-        stream table -- a third of the cost of building a torch.cuda.Stream object per step)."""
-        raw = _RAW_STREAM
-        if raw is not None:
-            return ctypes.c_void_p(raw(self.device.index))
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        """The calling thread's current HIP stream on the env's device as a c_void_p."""
+        return stream_ptr(self.device)
 
     def refill(self):
         """Streaming supply: cut new sequences for the episodes the bins have consumed (four kernels, no host sync)."""
