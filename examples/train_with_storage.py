@@ -4,6 +4,7 @@
     python examples/train_with_storage.py --envs 4096 --updates 4
     python examples/train_with_storage.py --envs 4096 --updates 4 --acktr
     python examples/train_with_storage.py --envs 64 --updates 4 --native-trunk [--fused-loss]
+    python examples/train_with_storage.py --envs 64 --updates 4 --native-heads [--fused-loss]
 
 Per update: `--steps` lock-steps in which the policy's logits go through bpp_masked_act and `storage.step` lets the step kernel
 write observation, mask, reward and done straight into the storage (no insert, no copy of an environment output); then ONE
@@ -18,7 +19,9 @@ The network is a plain-torch stand-in shaped like the reference's CNNPro (acktr/
 --native-trunk it is bpp_amd.TrainablePolicy instead: CNNPro under the reference's names, whose five 3x3 layers and 1x1 head
 convolutions run forward and backward through the native trunk kernels (include/bpp_policy_train.h), and the rollouts act on
 bpp_amd.NativePolicy refreshed from it after every update.  K-FAC finds its layers by module hooks, which the native trunk does
-not have yet: --native-trunk with --acktr is refused.
+not have yet: --native-trunk with --acktr is refused.  --native-heads (which implies --native-trunk) also runs the six Linear
+layers of the heads forward and backward in native kernels (include/bpp_policy_heads_train.h): nothing of the network is torch's
+then, and --acktr is refused in the same way.
 """
 import argparse
 import os
@@ -57,9 +60,9 @@ class ActorCritic(nn.Module):
 class NativeTrunkNet(nn.Module):
     """bpp_amd.TrainablePolicy behind the stand-in's interface: forward -> (logits, values, pred_mask)."""
 
-    def __init__(self, side, n_actions):
+    def __init__(self, side, n_actions, heads="torch"):
         super().__init__()
-        self.policy = bpp_amd.TrainablePolicy(side, n_actions)
+        self.policy = bpp_amd.TrainablePolicy(side, n_actions, heads=heads)
 
     def forward(self, obs):
         value, logits, pred = self.policy(obs)
@@ -107,12 +110,16 @@ COEFS, MAX_GRAD_NORM = (0.5, 0.01, 2.0, 0.5 * 10), 0.5      # value, entropy, in
 
 
 def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, seed=0, device="cuda:0", verbose=True, fused_loss=False,
-          acktr=False, native_trunk=False):
+          acktr=False, native_trunk=False, native_heads=False):
     """Runs `updates` updates; returns one (value_loss, action_loss, dist_entropy, prob_loss, graph_loss) tuple of floats per update.
     fused_loss: the five terms and the gradients at the network's outputs from ONE native call (storage.a2c_loss) instead of
     bpp_masked_evaluate + torch expressions + their autograd backward.  acktr: K-FAC (bpp_amd.KFACOptimizer) with the Fisher pass
     of acktr_pipeline.py:68-84 instead of RMSprop with gradient clipping.  native_trunk: train bpp_amd.TrainablePolicy and roll
-    out on bpp_amd.NativePolicy."""
+    out on bpp_amd.NativePolicy.  native_heads: the same with TrainablePolicy(heads="native"), the Linear layers native as well."""
+    if acktr and native_heads:
+        raise ValueError("K-FAC hooks into torch modules, which the native network does not have yet: --native-heads goes with RMSprop, "
+                         "not with --acktr")
+    native_trunk = native_trunk or native_heads
     if acktr and native_trunk:
         raise ValueError("K-FAC hooks into torch modules, which the native trunk does not have yet: --native-trunk goes with RMSprop, "
                          "not with --acktr")
@@ -122,7 +129,10 @@ def train(envs=4096, steps=5, updates=4, rotation=False, gamma=1.0, lr=7e-4, see
     size = (10, 10, 10)
     torch.manual_seed(seed)
     env = bpp_amd.BppVecEnv(envs, size, enable_rotation=rotation, pool=bpp_amd.sequences.cut2_pool(size, 1024, seed=seed), device=dev)
-    net = (NativeTrunkNet if native_trunk else ActorCritic)(size[0], env.action_space.n).to(dev)
+    if native_trunk:
+        net = NativeTrunkNet(size[0], env.action_space.n, heads="native" if native_heads else "torch").to(dev)
+    else:
+        net = ActorCritic(size[0], env.action_space.n).to(dev)
     actor = bpp_amd.NativePolicy(size[0], env.action_space.n, device=dev).refresh(net.policy) if native_trunk else None
     # acktr/algo/acktr_pipeline.py:33 with acktr=False; coefficients of the reference's defaults
     optimizer = bpp_amd.KFACOptimizer(net) if acktr else torch.optim.RMSprop(net.parameters(), lr, eps=1e-5, alpha=0.99)
@@ -203,9 +213,10 @@ def main():
     ap.add_argument("--fused-loss", action="store_true", help="loss terms and output gradients from one native call (bpp_amd.a2c_loss)")
     ap.add_argument("--acktr", action="store_true", help="K-FAC with the sampled-Fisher pass (bpp_amd.KFACOptimizer) instead of RMSprop")
     ap.add_argument("--native-trunk", action="store_true", help="train bpp_amd.TrainablePolicy: the trunk forward and backward in native kernels")
+    ap.add_argument("--native-heads", action="store_true", help="--native-trunk, and the heads' Linear layers in native kernels as well")
     args = ap.parse_args()
     train(args.envs, args.steps, args.updates, args.rotation, args.gamma, fused_loss=args.fused_loss, acktr=args.acktr,
-          native_trunk=args.native_trunk)
+          native_trunk=args.native_trunk, native_heads=args.native_heads)
 
 
 if __name__ == "__main__":

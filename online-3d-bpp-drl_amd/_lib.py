@@ -89,6 +89,11 @@ POLICY_TRAIN_SYMBOLS = ["bpp_policy_trunk_forward_train", "bpp_policy_trunk_back
                         "bpp_policy_trunk_backward_weights_floats", "bpp_policy_trunk_backward_info"]
 POLICY_TRAIN_INFO = ("bins_per_group", "grad_lds_bytes", "bins_per_split", "splits", "chain_rows", "wgrad_lds_bytes", "path", "blocks")
 POLICY_TRUNK_FLOATS, POLICY_TRUNK_BWD_FLOATS = 151380, 148736
+# include/bpp_policy_heads_train.h: the same, for the training pass of the heads' six Linear layers
+POLICY_HEADS_TRAIN_HDR = os.path.join(os.path.dirname(HERE), "include", "bpp_policy_heads_train.h")
+POLICY_HEADS_TRAIN_SYMBOLS = ["bpp_policy_heads_forward_train", "bpp_policy_heads_backward", "bpp_policy_heads_backward_workspace",
+                              "bpp_policy_heads_backward_weights_floats", "bpp_policy_heads_backward_info"]
+POLICY_HEADS_TRAIN_INFO = ("bins_per_group", "grad_lds_bytes", "bins_per_split", "splits", "chain_rows", "wgrad_lds_bytes", "path", "blocks")
 # include/bpp_stream_kinds.h: the same, for the CUT-1 and RS ring refills
 STREAM_KIND_SYMBOLS = ["bpp_stream_refill_cut1", "bpp_stream_refill_rs", "bpp_stream_kinds_info", "bpp_rollout_uniform_stream_kind"]
 STREAM_KINDS = {"cut1": 1, "rs": 2}                  # BPP_STREAM_KIND_*
@@ -343,6 +348,23 @@ def bind_policy_train(L):
     return L
 
 
+def bind_policy_heads_train(L):
+    """Argument types of the POLICY_HEADS_TRAIN_SYMBOLS on library handle L."""
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    geom = ctypes.POINTER(i32)
+    L.bpp_policy_heads_forward_train.argtypes = [vp, i32, geom] + [vp] * 6
+    L.bpp_policy_heads_forward_train.restype = ctypes.c_int
+    L.bpp_policy_heads_backward.argtypes = [vp] * 6 + [i32, geom] + [vp] * 6 + [ctypes.c_size_t, vp]
+    L.bpp_policy_heads_backward.restype = ctypes.c_int
+    L.bpp_policy_heads_backward_workspace.argtypes = [geom, i32]
+    L.bpp_policy_heads_backward_workspace.restype = ctypes.c_size_t
+    L.bpp_policy_heads_backward_weights_floats.argtypes = [geom]
+    L.bpp_policy_heads_backward_weights_floats.restype = ctypes.c_size_t
+    L.bpp_policy_heads_backward_info.argtypes = [geom, i32, geom]
+    L.bpp_policy_heads_backward_info.restype = ctypes.c_int
+    return L
+
+
 def bind_stream_kinds(L, batch=None, step_out=None, stream=None):
     """Argument types of the STREAM_KIND_SYMBOLS on library handle L (`batch`, `step_out`, `stream`: the ctypes classes of struct
     bpp_batch, bpp_step_out and bpp_stream)."""
@@ -523,6 +545,7 @@ def lib():
         bind_policy(L)
         bind_policy_one_image(L)
         bind_policy_train(L)
+        bind_policy_heads_train(L)
         bind_stream_kinds(L)
         bind_placements(L)
         bind_heuristic(L)

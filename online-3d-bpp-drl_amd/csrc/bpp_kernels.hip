@@ -1647,5 +1647,6 @@ int bpp_copy_bins(const bpp_batch *b, const bpp_stream *s, const int64_t *src, c
 #include "bpp_policy.inl"
 #include "bpp_policy_one_image.inl"
 #include "bpp_policy_train.inl"
+#include "bpp_policy_heads_train.inl"
 #include "bpp_placements.inl"
 #include "bpp_heuristic.inl"

@@ -49,6 +49,7 @@ struct PolHeadArgs {
     const float *feat;
     const float *w;
     float *out[3];                        // logits, pred, value
+    float *hidden;                        // training forward only (bpp_policy_heads_train.inl): [3][n][H]
     int heads[3], nheads;
     PolShape s;
 };
@@ -62,7 +63,8 @@ struct PolHeadArgs {
 // Two k go into one mfma_step (bpp_mfma.inl): lane l passes A[l & 31][k + (l >> 5)] and B[k + (l >> 5)][l & 31].  On the device
 // the operands of U instructions per column tile are fetched while the U before them issue: with one wave per SIMD nothing else
 // hides the latency of the weights.  What that loop leaves of K goes through the plain loop behind it; emulated, all of K does.
-// Both walk k in pairs, so K must be even as stated above: every caller's is (36, 576, 64, 20, H, and 4 A or 8 A in chunks of 64).
+// Both walk k in pairs, so K must be even as stated above: every caller's is (36, 576, 64, 20, H, and 4 A or 8 A in chunks of 64;
+// bpp_policy_heads_train.inl makes an odd chunk even with a row of zeros).
 template <int NB, int U>
 __device__ __forceinline__ void policy_chain(MfmaAcc (&acc)[NB], const float *img, const int *rt, int ro, const int *ftab, int kstride, int K,
                                              const float *__restrict__ w, int ldw, int col0, int ncol, int lane) {
@@ -222,7 +224,9 @@ __global__ __launch_bounds__(256) void policy_trunk_kernel(PolTrunkArgs a) {
         if (bin0 + idx / F < s.n) a.feat[(size_t)bin0 * (size_t)F + (size_t)idx] = dst[idx];
 }
 
-// grid = ceil(n / 64) * heads asked for: workgroup g takes bin tile g / heads and head g % heads
+// grid = ceil(n / 64) * heads asked for: workgroup g takes bin tile g / heads and head g % heads.  HID: the hidden vector also
+// goes to a.hidden in rows, copied from the LDS it was written to.
+template <bool HID>
 __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const PolShape &s = a.s;
@@ -265,6 +269,13 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolHeadArgs a) {
         }
     }
     __syncthreads();
+    if (HID) {
+        float *out = a.hidden + ((size_t)head * (size_t)s.n + (size_t)bin0) * (size_t)s.H;
+        for (int idx = tid; idx < kPolT * s.H; idx += 256) {
+            const int b = idx / s.H;
+            if (bin0 + b < s.n) out[idx] = hid[(idx - b * s.H) * kPolStride + b];
+        }
+    }
     // second Linear: a wave takes 32 bins by 64 outputs at a time
     float *out = a.out[head];
     for (int col0 = cgroup * 2 * kPolTile; col0 < Mh; col0 += 4 * kPolTile) {
@@ -365,13 +376,13 @@ int bpp_policy_forward(const float *obs, int64_t obs_stride, int32_t n, const in
                                                                     kPolLdsBytes, st, t))
         return rc;
     PolHeadArgs h;
-    h.feat = (const float *)workspace, h.w = weights, h.s = s, h.nheads = 0;
+    h.feat = (const float *)workspace, h.w = weights, h.hidden = nullptr, h.s = s, h.nheads = 0;
     h.out[0] = logits, h.out[1] = pred, h.out[2] = value;
     for (int k = 0; k < 3; ++k) {
         h.heads[k] = 0;
         if (h.out[k]) h.heads[h.nheads++] = k;
     }
-    return launch_large_lds<policy_head_kernel>(dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), s.head_lds,
+    return launch_large_lds<policy_head_kernel<false>>(dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), s.head_lds,
                                                 kPolLdsBytes, st, h);
 }
 

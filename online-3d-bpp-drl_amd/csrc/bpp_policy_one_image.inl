@@ -159,13 +159,13 @@ int bpp_policy_forward_one_image(const float *obs, int64_t obs_stride, int32_t n
     }
     if (rc) return rc;
     PolHeadArgs h;
-    h.feat = (const float *)workspace, h.w = weights, h.s = s, h.nheads = 0;
+    h.feat = (const float *)workspace, h.w = weights, h.hidden = nullptr, h.s = s, h.nheads = 0;
     h.out[0] = logits, h.out[1] = pred, h.out[2] = value;
     for (int k = 0; k < 3; ++k) {
         h.heads[k] = 0;
         if (h.out[k]) h.heads[h.nheads++] = k;
     }
-    return launch_large_lds<policy_head_kernel>(dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), s.head_lds,
+    return launch_large_lds<policy_head_kernel<false>>(dim3((unsigned)(((long long)n + kPolT - 1) / kPolT) * (unsigned)h.nheads), dim3(256), s.head_lds,
                                                 kPolLdsBytes, st, h);
 }
 

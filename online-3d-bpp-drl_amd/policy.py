@@ -14,7 +14,8 @@ whatever batch it is evaluated in.  CPU tensors go through torch_forward, the sa
 
 Training (include/bpp_policy_train.h): TrainablePolicy is the same network as an nn.Module whose five 3x3 layers
 and 1x1 head convolutions run forward and backward through the native trunk kernels (policy_trunk, an autograd Function); its
-Linear layers are torch.
+Linear layers are torch, or with heads="native" the native head kernels (include/bpp_policy_heads_train.h; DESIGN.md 3.18;
+policy_heads, a second autograd Function), so that nothing of the network runs in torch.
 
     net = bpp_amd.TrainablePolicy(10, env.action_space.n).to("cuda:0")
     value, logits, pred = net(obs); loss.backward(); optimizer.step(); policy.refresh(net)
@@ -458,16 +459,228 @@ def policy_trunk(obs, trunk_parameters, side, cache=None):
     return _PolicyTrunk.apply(obs, S, _TRUNK_BUFFERS if cache is None else cache, keep, *trunk_parameters)
 
 
+# ------------------------------------------------------------------------------- training of the heads (bpp_policy_heads_train.h)
+HEAD_LINEARS = ("base.actor.3", "dist.linear", "base.mask.3", "base.mask.5", "base.critic.3", "base.critic_linear")    # the blob's order
+HEAD_PARAMETERS = tuple(n + k for n in HEAD_LINEARS for k in (".weight", ".bias"))               # the order policy_heads takes
+HEADS_MODES = ("torch", "native")
+
+
+def pack_heads(weights):
+    """pack_weights' blob from float 151 380 on -- the six Linear layers, all that the head kernels read -- from plain tensors
+    under the reference's names: every matrix [k][oc], its bias behind it."""
+    parts = []
+    for n in HEAD_LINEARS:
+        parts.extend([weights[n + ".weight"].t().reshape(-1), weights[n + ".bias"].reshape(-1)])
+    return torch.cat([p.to(torch.float32) for p in parts], 0).contiguous()
+
+
+def pack_heads_backward(weights):
+    """The float32 blob `weights_bwd` of bpp_policy_heads_backward, from plain tensors under the reference's names: the six
+    matrices in torch's own [out][in] layout, per head (actor, mask, critic) the second Linear in front of the first."""
+    order = (HEAD_LINEARS[1], HEAD_LINEARS[0], HEAD_LINEARS[3], HEAD_LINEARS[2], HEAD_LINEARS[5], HEAD_LINEARS[4])
+    return torch.cat([weights[n + ".weight"].to(torch.float32).reshape(-1) for n in order], 0).contiguous()
+
+
+def unpack_heads_gradient(gw, side, hidden, n_actions):
+    """{name: gradient in torch's shape} from bpp_policy_heads_backward's grad_weights: [out][in] is a view of [k][oc]
+    transposed."""
+    out, at = {}, 0
+    for name, (oc, k) in layer_shapes(side, hidden, n_actions)[8:]:
+        out[name + ".weight"], out[name + ".bias"] = gw[at:at + k * oc].reshape(k, oc).t(), gw[at + k * oc:at + (k + 1) * oc]
+        at += (k + 1) * oc
+    if at != gw.numel():
+        raise ValueError("grad_weights has %d floats, the six Linear layers %d" % (gw.numel(), at))
+    return out
+
+
+def heads_backward_info(geom, n, L=None):
+    """bpp_policy_heads_backward_info as a dict (_lib.POLICY_HEADS_TRAIN_INFO)."""
+    return _lib.info_dict("bpp_policy_heads_backward_info", _lib.POLICY_HEADS_TRAIN_INFO, 8, _lib.kfac_geom(geom), int(n), L=L)
+
+
+def _heads_tensor(name, t, numel, dev):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError("%s must be a contiguous float32 tensor of %d elements on %s" % (name, numel, dev))
+    return t
+
+
+def _check_feat(feat, A):
+    if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 2 or feat.shape[0] < 1 or feat.shape[1] != 20 * A:
+        raise ValueError("feat must be a float32 [n, 20 A] tensor with n >= 1")
+    if feat.device.type != "cuda":
+        raise RuntimeError("the native heads need their tensors on a HIP device")
+    if not feat.is_contiguous():
+        raise ValueError("feat must be contiguous")
+    return int(feat.shape[0])
+
+
+def heads_forward_train(feat, blob, geom, value=None, logits=None, pred=None, hidden=None):
+    """(value [n], logits [n, M], pred [n, M], hidden [3, n, H]) from bpp_policy_heads_forward_train: feat float32 [n, 20 A] as
+    trunk_forward_train wrote it, blob the whole packed blob of pack_weights (only the floats from 151 380 on are read).
+    value / logits / pred / hidden: buffers to write into.  Only enqueues on the current stream."""
+    S, H, M = (int(v) for v in geom)
+    n = _check_feat(feat, S * S)
+    dev = feat.device
+    g = _lib.kfac_geom((S, H, M))
+    L = _lib.lib()
+    floats = int(L.bpp_policy_one_image_weights_floats(g))
+    if floats == 0:
+        _lib.check(L.bpp_policy_heads_backward_info(g, n, (ctypes.c_int32 * 8)()))
+    _heads_tensor("blob", blob, floats, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+    value = new(n) if value is None else _heads_tensor("value", value, n, dev)
+    logits = new(n, M) if logits is None else _heads_tensor("logits", logits, n * M, dev)
+    pred = new(n, M) if pred is None else _heads_tensor("pred", pred, n * M, dev)
+    hidden = new(3, n, H) if hidden is None else _heads_tensor("hidden", hidden, 3 * n * H, dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.bpp_policy_heads_forward_train(feat.data_ptr(), n, g, blob.data_ptr(), value.data_ptr(), logits.data_ptr(), pred.data_ptr(),
+                                                    hidden.data_ptr(), stream_ptr(dev)))
+    return value, logits, pred, hidden
+
+
+def heads_backward(feat, hidden, pred, grad_value, grad_logits, grad_pred, geom, blob_bwd, grad_feat=None, grad_hidden=None,
+                   grad_out_mask=None, grad_weights=None, workspace=None):
+    """(grad_feat [n, 20 A], grad_hidden [3, n, H], grad_out_mask [n, M], grad_weights) from bpp_policy_heads_backward.
+    grad_value [n] / grad_logits [n, M] / grad_pred [n, M]: None for a head that contributes nothing (zeros are written for it).
+    The other keyword arguments: buffers to use (workspace: float32, at least bpp_policy_heads_backward_workspace bytes)."""
+    S, H, M = (int(v) for v in geom)
+    n = _check_feat(feat, S * S)
+    dev, A = feat.device, S * S
+    g = _lib.kfac_geom((S, H, M))
+    L = _lib.lib()
+    need = int(L.bpp_policy_heads_backward_workspace(g, n))
+    if need == 0:
+        _lib.check(L.bpp_policy_heads_backward_info(g, n, (ctypes.c_int32 * 8)()))
+    if grad_value is None and grad_logits is None and grad_pred is None:
+        raise ValueError("at least one of grad_value, grad_logits and grad_pred must be given")
+    floats = int(L.bpp_policy_one_image_weights_floats(g)) - TRUNK_FLOATS
+    for name, t, numel in (("hidden", hidden, 3 * n * H), ("pred", pred, n * M), ("grad_value", grad_value, n), ("grad_logits", grad_logits, n * M),
+                           ("grad_pred", grad_pred, n * M), ("blob_bwd", blob_bwd, int(L.bpp_policy_heads_backward_weights_floats(g))),
+                           ("grad_feat", grad_feat, n * 20 * A), ("grad_hidden", grad_hidden, 3 * n * H), ("grad_out_mask", grad_out_mask, n * M),
+                           ("grad_weights", grad_weights, floats)):
+        if t is not None or name in ("hidden", "pred", "blob_bwd"):
+            _heads_tensor(name, t, numel, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+    grad_feat = new(n, 20 * A) if grad_feat is None else grad_feat
+    grad_hidden = new(3, n, H) if grad_hidden is None else grad_hidden
+    grad_out_mask = new(n, M) if grad_out_mask is None else grad_out_mask
+    grad_weights = new(floats) if grad_weights is None else grad_weights
+    workspace = new(max(1, need // 4)) if workspace is None else workspace
+    if not torch.is_tensor(workspace) or workspace.dtype != torch.float32 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous float32 tensor on %s" % dev)
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(L.bpp_policy_heads_backward(feat.data_ptr(), hidden.data_ptr(), pred.data_ptr(), ptr(grad_value), ptr(grad_logits), ptr(grad_pred),
+                                               n, g, blob_bwd.data_ptr(), grad_feat.data_ptr(), grad_hidden.data_ptr(), grad_out_mask.data_ptr(),
+                                               grad_weights.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, stream_ptr(dev)))
+    return grad_feat, grad_hidden, grad_out_mask, grad_weights
+
+
+class _HeadsBuffers:
+    """What one (n, device, side, H, M) needs between a forward and its backward passes, and both blobs with the parameter
+    versions they were packed from."""
+
+    def __init__(self):
+        self.versions = self.blob = self.blob_bwd = self.hidden = self.grad_hidden = self.grad_out_mask = self.workspace = None
+        self.forwards = 0
+
+
+_HEADS_BUFFERS = {}     # (n, device, side, H, M) -> _HeadsBuffers: policy_heads' default cache (a module brings its own)
+
+
+def clear_heads_buffers():
+    """Release what policy_heads' default cache holds."""
+    _HEADS_BUFFERS.clear()
+
+
+class _PolicyHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, geom, cache, keep, *params):
+        S, H, M = geom
+        n, dev = int(feat.shape[0]), feat.device
+        ctx.set_materialize_grads(False)            # an output that takes no part reaches the backward as None: that head's NULL
+        key = (n, dev, S, H, M)
+        buf = cache.get(key)
+        if buf is None:
+            buf = cache[key] = _HeadsBuffers()
+        versions = tuple((p.data_ptr(), p._version) for p in params)
+        if buf.versions != versions:
+            plain = {name: p.detach() for name, p in zip(HEAD_PARAMETERS, params)}
+            tail = pack_heads(plain)
+            if buf.blob is None:                    # the trunk's part of the blob is never read by the head kernels
+                buf.blob = torch.zeros(TRUNK_FLOATS + tail.numel(), dtype=torch.float32, device=dev)
+            buf.blob[TRUNK_FLOATS:] = tail
+            buf.blob_bwd, buf.versions = pack_heads_backward(plain), versions
+        if not keep:                                # nothing will be differentiated: the kept hidden vectors stay as they are
+            return heads_forward_train(feat, buf.blob, geom)[:3]
+        if buf.hidden is None:
+            need = int(_lib.lib().bpp_policy_heads_backward_workspace(_lib.kfac_geom(geom), n))
+            buf.hidden = torch.empty((3, n, H), dtype=torch.float32, device=dev)
+            buf.grad_hidden = torch.empty((3, n, H), dtype=torch.float32, device=dev)
+            buf.grad_out_mask = torch.empty((n, M), dtype=torch.float32, device=dev)
+            buf.workspace = torch.empty(max(1, need // 4), dtype=torch.float32, device=dev)
+        value, logits, pred, _ = heads_forward_train(feat, buf.blob, geom, hidden=buf.hidden)
+        ctx.save_for_backward(feat, pred)
+        buf.forwards += 1
+        ctx.buf, ctx.geom, ctx.blob_bwd, ctx.stamp = buf, geom, buf.blob_bwd, buf.forwards
+        return value, logits, pred
+
+    @staticmethod
+    def backward(ctx, grad_value, grad_logits, grad_pred):
+        feat, pred = ctx.saved_tensors
+        buf = ctx.buf
+        if buf.forwards != ctx.stamp:
+            raise RuntimeError("policy_heads: another forward of the same batch size has overwritten the hidden vectors of this graph")
+        dense = lambda g: None if g is None else g.to(torch.float32).contiguous()      # noqa: E731
+        grad_feat, _, _, gw = heads_backward(feat, buf.hidden, pred, dense(grad_value), dense(grad_logits), dense(grad_pred), ctx.geom, ctx.blob_bwd,
+                                             grad_hidden=buf.grad_hidden, grad_out_mask=buf.grad_out_mask, workspace=buf.workspace)
+        named = unpack_heads_gradient(gw, *ctx.geom)
+        return (grad_feat if ctx.needs_input_grad[0] else None, None, None, None) + tuple(
+            named[name] if ctx.needs_input_grad[4 + i] else None for i, name in enumerate(HEAD_PARAMETERS))
+
+
+def policy_heads(feat, head_parameters, side, n_actions, hidden, cache=None):
+    """(value [n], logits [n, M], pred [n, M]) = the six Linear layers of CNNPro's three heads on feat float32 [n, 20 A] on a
+    HIP device (what policy_trunk returns), differentiable with respect to feat and to head_parameters: the 12 tensors of
+    HEAD_PARAMETERS (a dict under those names, or a sequence in that order), in torch's shapes.  Forward and backward are the
+    native calls of include/bpp_policy_heads_train.h; the backward hands grad_feat on to whatever produced feat.
+
+    policy_trunk's rules hold: the hidden vectors of a forward are kept per (n, device, side) until the next differentiable
+    forward of the same key; backward passes over one graph may be repeated and give the same bits, a backward after a newer
+    such forward is refused; a forward under no_grad, or with nothing that requires grad, keeps nothing.  The buffers and both
+    blobs (re-packed when a parameter's version changes) live in `cache`, a dict the caller owns; the default is one dict for
+    the process, which clear_heads_buffers() empties.  An output that takes no part in the loss contributes zeros."""
+    if isinstance(head_parameters, dict):
+        head_parameters = [head_parameters[name] for name in HEAD_PARAMETERS]
+    head_parameters = list(head_parameters)
+    if len(head_parameters) != len(HEAD_PARAMETERS):
+        raise ValueError("policy_heads takes the %d tensors of HEAD_PARAMETERS" % len(HEAD_PARAMETERS))
+    geom = (int(side), int(hidden), int(n_actions))
+    if not 1 <= geom[0] <= MAX_SIDE_ONE_IMAGE:
+        raise ValueError("side must lie in 1 .. %d" % MAX_SIDE_ONE_IMAGE)
+    _check_feat(feat, geom[0] ** 2)
+    for name, p in zip(HEAD_PARAMETERS, head_parameters):
+        if not torch.is_tensor(p) or p.device != feat.device:
+            raise ValueError("%s is on %s, feat on %s" % (name, getattr(p, "device", None), feat.device))
+    keep = torch.is_grad_enabled() and (feat.requires_grad or any(p.requires_grad for p in head_parameters))
+    return _PolicyHeads.apply(feat, geom, _HEADS_BUFFERS if cache is None else cache, keep, *head_parameters)
+
+
 class TrainablePolicy(torch.nn.Module):
     """The reference's Policy(CNNPro) for training: parameters under the reference's names (`base.share.0.weight` ...
-    `dist.linear.bias`), the trunk and the head convolutions through policy_trunk, the Linear layers in torch.
+    `dist.linear.bias`), the trunk and the head convolutions through policy_trunk.  heads="torch" (the default): the Linear
+    layers in torch; heads="native": through policy_heads, so that nothing of the network runs in torch.
     forward(obs) -> (value [n], logits [n, M], pred [n, M]) as NativePolicy returns them.  On CPU tensors the forward is
     torch_forward on the same parameters (no native code, for inspection only)."""
 
-    def __init__(self, side, n_actions, hidden=256):
+    def __init__(self, side, n_actions, hidden=256, heads="torch"):
         super().__init__()
+        if heads not in HEADS_MODES:
+            raise ValueError("heads must be one of %r" % (HEADS_MODES,))
         NativePolicy(side, n_actions, hidden)                 # its refusals
         self._trunk_cache = {}                                # policy_trunk's buffers, per batch size: released with the module
+        self._heads_cache, self._last = {}, None              # policy_heads' buffers; the keys of the last differentiable forward
+        self.heads = heads
         self.side, self.n_actions, self.hidden = int(side), int(n_actions), int(hidden)
         relu = torch.nn.init.calculate_gain("relu")
         for name, shape in layer_shapes(self.side, self.hidden, self.n_actions):
@@ -487,6 +700,23 @@ class TrainablePolicy(torch.nn.Module):
     def release_buffers(self):
         """Drop the activations, gradients and workspaces kept for the batch sizes seen so far (21 GB at n = 65 536)."""
         self._trunk_cache.clear()
+        self._heads_cache.clear()
+        self._last = None
+
+    def kept(self):
+        """The dense tensors the last differentiable forward (and its backward, once it has run) left on the device, as views of
+        the module's buffers, None before such a forward: `acts` [5, n, 64, S, S] and `grads` (flat: G_1 .. G_5 [n, 64, A] each,
+        then the masked head gradient [n, 20 A]) of the trunk -- the sources of BPP_KFAC_PATCH and BPP_KFAC_NCHW -- and, with
+        heads="native", `hidden` [3, n, H], `grad_hidden` [3, n, H] and `grad_out_mask` [n, M], which with the gradients at
+        logits and value are the BPP_KFAC_ROWS sources of the six Linear layers.  This is what a K-FAC hook-up of the native
+        network will read; nothing uses it yet."""
+        if self._last is None:
+            return None
+        trunk, heads = (c.get(k) for c, k in zip((self._trunk_cache, self._heads_cache), self._last))
+        out = dict(acts=trunk.acts, grads=trunk.grads) if trunk is not None else {}
+        if heads is not None:
+            out.update(hidden=heads.hidden, grad_hidden=heads.grad_hidden, grad_out_mask=heads.grad_out_mask)
+        return out
 
     def load_state_dict(self, state, strict=True, assign=False):
         """A state dict in any of the three forms plain_weights takes (the reference's names, the K-FAC-split checkpoint form,
@@ -512,6 +742,11 @@ class TrainablePolicy(torch.nn.Module):
             return torch_forward(w, obs.to(torch.float32))
         A = self.side ** 2
         feat = policy_trunk(obs if obs.dtype == torch.float32 else obs.to(torch.float32), w, self.side, cache=self._trunk_cache)
+        if feat.requires_grad:
+            n = int(feat.shape[0])
+            self._last = ((n, feat.device, self.side), (n, feat.device, self.side, self.hidden, self.n_actions))
+        if self.heads == "native":
+            return policy_heads(feat, w, self.side, self.n_actions, self.hidden, cache=self._heads_cache)
 
         def head(name, lo, hi):
             return F.relu(F.linear(feat[:, lo * A:hi * A], w[name + ".3.weight"], w[name + ".3.bias"]))
